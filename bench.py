@@ -159,6 +159,33 @@ def verify_fastq(torch, scan, n_rec, base, first_record):
     return ok
 
 
+DUMP_ROWS = 1 << 18    # rows of the --dump-outputs sample: 4 columns x 4 float64 each = 32 MiB, plus the row indices and validity
+DUMP_SEED = 20240611
+
+
+def dump_fastq_outputs(torch, scan, res, n_rec, out_dir):
+    """--dump-outputs: what the last timed launch handed its caller, as float64 .npy files under out_dir.  `result`: the
+    ScanResult fields in their declared order.  The columns name / description / sequence / quality_scores (duckdb::string_t,
+    two 64-bit words a row) become [rows, 4] arrays of their 32-bit halves (length, prefix, inline bytes or pointer low,
+    high), exact in float64; `description_validity` holds one validity bit per row.  Rows: every row up to DUMP_ROWS, else a
+    fixed sample (DUMP_SEED) that always holds the first and last row, listed in `rows`."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    if n_rec <= DUMP_ROWS:
+        rows = np.arange(n_rec, dtype=np.int64)
+    else:
+        pick = np.random.default_rng(DUMP_SEED).choice(n_rec - 2, size=DUMP_ROWS - 2, replace=False) + 1
+        rows = np.sort(np.concatenate([[0, n_rec - 1], pick])).astype(np.int64)
+    idx = torch.from_numpy(rows).to(scan.validity.device)
+    out = {"rows": rows.astype(np.float64),
+           "result": np.array([float(getattr(res, f)) for f, _ in res._fields_], dtype=np.float64)}
+    for name, col in zip(["name", "description", "sequence", "quality_scores"], scan.cols):
+        out[name] = col[idx].cpu().numpy().view(np.uint32).reshape(-1, 4).astype(np.float64)
+    out["description_validity"] = ((scan.validity[idx >> 6] >> (idx & 63)) & 1).cpu().numpy().astype(np.float64)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def timed_launches(torch, fn, reps, warm=2):
     """average device time of fn() in ms, HIP events on the launch stream"""
     for _ in range(warm):
@@ -1107,9 +1134,14 @@ def main():
     ap.add_argument("--shape-gb", type=float, default=4.0, help="record_shapes legs: GB of each shape tiled in HBM")
     ap.add_argument("--backend", default="nccl", help="nccl (= RCCL; default) | gloo (functional test of the N>1 path)")
     ap.add_argument("--single-device", action="store_true", help="test only: every rank uses cuda:0 (needs --backend gloo)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed launch computed (rank 0's shard) as DIR/<name>.npy, float64: "
+                         "the scan result, a fixed sample of rows of the four string_t columns and the description validity")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
 
     # --gpus N is the number of ranks.  Without a launcher (no WORLD_SIZE in the environment) and N > 1 this process starts the N
     # ranks itself — as a CHILD `python -m torch.distributed.run` with the same arguments, before torch is imported or any
@@ -1226,6 +1258,8 @@ def main():
     dt = time.perf_counter() - t0
     res = scan.fetch()
     assert res.error_code == 0 and int(res.n_records) == n_rec_local and not (res.flags & abi.EXG_RF_FALLBACK)
+    if args.dump_outputs and rank == 0:
+        dump_fastq_outputs(torch, scan, res, n_rec_local, args.dump_outputs)
     if world > 1:
         exact = sharding.first_line_index_from_counts([int(c.item()) for c in line_counts], rank)
         assert sharding.phase_is_consistent(first_line_index % 4, exact), "phase guess contradicted by the exact counts"

@@ -2,6 +2,9 @@ import os
 import sys
 
 import pytest
+# torch first, before any test dlopens libexon_gpu.so: the library then binds to torch's HIP runtime.  Loaded the other way
+# round (a CPU test that loads the library, then a GPU test) the process holds two HIP runtimes and the second sees no device.
+import torch  # noqa: F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
