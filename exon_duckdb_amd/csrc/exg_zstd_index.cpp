@@ -105,6 +105,9 @@ static bool build_index_walk(S &src, uint64_t n, Index &idx, uint64_t stop_est =
             const int last = bh & 1, type = (bh >> 1) & 3;
             const uint32_t bsize = bh >> 3;
             if (type == 3 || bsize > kBlockMax) return fail(idx, kCorrupt, pos - 3);
+            // Block_Maximum_Size is the smaller of Window_Size and 128 KiB (3.1.1.2.3): a raw or compressed block's stored size
+            // may not exceed it (libzstd: "Block Size Exceeds Maximum"; an RLE block stores one byte)
+            if (type != 1 && bsize > fr.window) return fail(idx, kCorrupt, pos - 3);
             if (idx.blocks.size() >= 0xFFFFFFF0u) return fail(idx, "too many blocks", pos);
             Block b;
             memset(&b, 0, sizeof b);

@@ -26,15 +26,25 @@ def bgzf(data, block):
     return b"".join(out)
 
 
-def test_host_parsers_under_asan_ubsan(tmp_path):
-    if not os.path.isdir("/opt/rocm/include"):
-        pytest.skip("HIP headers not found")
-    exe = tmp_path / "host_asan"
+def build_driver(exe):
+    """tests/host_asan_driver.cpp with the host parsers it drives, under AddressSanitizer + UBSan"""
     cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-D__HIP_PLATFORM_AMD__",
            "-I", "/opt/rocm/include", "-I", CSRC, "-I", os.path.join(ROOT, "include"), "-o", str(exe),
            os.path.join(ROOT, "tests", "host_asan_driver.cpp"), os.path.join(CSRC, "exg_gzip.cpp"), os.path.join(CSRC, "exg_zstd_index.cpp"),
            os.path.join(CSRC, "exg_rd_bgzf.cpp"), os.path.join(CSRC, "exg_vcf_header.cpp"), os.path.join(CSRC, "exg_rd_plan.cpp"), os.path.join(CSRC, "exg_rd_fanout.cpp"), os.path.join(CSRC, "exg_map_guard.cpp"), "-lpthread"]
     subprocess.check_call(cmd)
+
+
+def run_driver(exe, paths):
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0:handle_sigbus=0", UBSAN_OPTIONS="print_stacktrace=1")
+    return subprocess.run([str(exe)] + paths, env=env, capture_output=True, text=True)
+
+
+def test_host_parsers_under_asan_ubsan(tmp_path):
+    if not os.path.isdir("/opt/rocm/include"):
+        pytest.skip("HIP headers not found")
+    exe = tmp_path / "host_asan"
+    build_driver(exe)
     text = fastq_text(3000, 4)
     files = {
         "a.gz": gzip.compress(text, 6, mtime=0),
@@ -48,7 +58,6 @@ def test_host_parsers_under_asan_ubsan(tmp_path):
     for name, data in files.items():
         (tmp_path / name).write_bytes(data)
         paths.append(str(tmp_path / name))
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0:handle_sigbus=0", UBSAN_OPTIONS="print_stacktrace=1")
-    res = subprocess.run([str(exe)] + paths, env=env, capture_output=True, text=True)
+    res = run_driver(exe, paths)
     assert res.returncode == 0, res.stdout + res.stderr
     assert "runs" in res.stdout
