@@ -10,6 +10,11 @@ phase from the shard-local structure, verified by an all_gather of the newline c
 the data path; one all_reduce of the record counts per launch (the COUNT(*) of config 5).  After the timed loop the
 output of the last launch is verified on the device against the generator's closed forms (`verified`).
 
+A plain run does that and nothing more: it sets up, warms up, times the steps, writes --dump-outputs, verifies and prints the line.
+Everything below takes runs of its own and comes only with --full (`extra_legs`); --no-configs, --no-cpu-baseline, --no-traffic and
+--legs then leave parts of it out, as they always did.
+
+`roofline`: per-launch device time from HIP events, the read-only stream rate of the same buffer, the HBM traffic of one launch.
 Beside it (rank 0, N=1, skipped with --no-configs): `configs` — BASELINE configs[0] (SELECT COUNT(*) on a 1 MB FASTA
 through the reader: latency), configs[2] (8-column VCF scan, 5 GB generated in HBM by exg_synth_vcf) and configs[3]
 (read_fastq on BGZF: members deflated on the host cores, inflated + scanned on the device, COUNT(*) through the reader) —
@@ -103,7 +108,7 @@ def measure_traffic_in_run(n_bytes_expected, timeout_s=240):
         for c in ("FETCH_SIZE", "WRITE_SIZE"):
             d = os.path.join(tmp, c)
             cmd = [prof, "--kernel-trace", "--pmc", c, "-d", d, "-o", "pmc", "--output-format", "csv", "--",
-                   "python3", os.path.abspath(__file__), "--steps", "1", "--warmup", "1", "--launches-per-step", "2", "--no-configs", "--no-cpu-baseline"]
+                   "python3", os.path.abspath(__file__), "--steps", "1", "--warmup", "1", "--launches-per-step", "2", "--full", "--no-configs", "--no-cpu-baseline"]
             left = timeout_s - (time.perf_counter() - t0)
             if left < 30:
                 return None
@@ -132,7 +137,7 @@ def measure_traffic_in_run(n_bytes_expected, timeout_s=240):
     rd, wr = out["FETCH_SIZE"][0] * 2.0, out["WRITE_SIZE"][0]
     return {"traffic": rd + wr, "read_bytes": rd, "write_bytes": wr, "dispatches": out["FETCH_SIZE"][1], "seconds": time.perf_counter() - t0,
             "source": "measured in this run: rocprofv3 --kernel-trace --pmc FETCH_SIZE / --pmc WRITE_SIZE, two passes over a child `python3 bench.py "
-                      "--steps 1 --warmup 1 --launches-per-step 2 --no-configs` started before the timed run (KiB x 1024; FETCH_SIZE x 2: gfx950 correction); "
+                      "--steps 1 --warmup 1 --launches-per-step 2 --full --no-configs` started before the timed run (KiB x 1024; FETCH_SIZE x 2: gfx950 correction); "
                       f"average of {out['FETCH_SIZE'][1]} dispatches of {kernel}"}
 
 
@@ -1114,7 +1119,28 @@ def run_configs(torch, lib, args):
     return out
 
 
-def main():
+def extra_legs(args, world):
+    """what a run measures beside its headline -> a set of names: nothing without --full; with it, what today's flags leave in
+    (`traffic`: the in-run counter passes, N = 1 at the headline size and algo; `roofline`; N = 1: `configs`, `record_shapes`,
+    `cpu_baseline`; N > 1: `reader_sharded`)"""
+    if not args.full:
+        return set()
+    legs = {"roofline"}
+    if world == 1:
+        if not args.no_traffic and args.gb is None and args.algo == 2:
+            legs.add("traffic")
+        if not args.no_configs:
+            legs.add("configs")
+            if not args.legs or "record_shapes" in args.legs.split(","):
+                legs.add("record_shapes")
+        if not args.no_cpu_baseline:
+            legs.add("cpu_baseline")
+    elif not args.no_configs:
+        legs.add("reader_sharded")
+    return legs
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
@@ -1123,6 +1149,8 @@ def main():
     ap.add_argument("--gb", type=float, default=None, help="shard size per GPU in GB (1e9 bytes); default 10 (N=1), 12.5 (N>1: N=8 is 100 GB)")
     ap.add_argument("--algo", type=int, default=2, help="2 = the fused scan, which is what the reader launches per batch (EXG_RF_FALLBACK asserted clear); 3 = the any-shape "
                     "scan alone (what a reader switches to on long / very short reads); 0 = fused + the gated general-path launches")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: roofline, the configs / end_to_end / "
+                    "record_shapes legs and cpu_baseline (N=1), the sharded reader leg (N>1); the --no-* flags and --legs below act on these")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-configs", action="store_true", help="skip the configs / end_to_end legs")
     ap.add_argument("--legs", default="", help="only these configs legs (comma separated keys of the line's `configs` object; default: all)")
@@ -1137,7 +1165,11 @@ def main():
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed launch computed (rank 0's shard) as DIR/<name>.npy, float64: "
                          "the scan result, a fixed sample of rows of the four string_t columns and the description validity")
-    args = ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def main():
+    args = parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
     if args.steps < 1:
@@ -1155,10 +1187,11 @@ def main():
               f"itself) or with --nproc-per-node {args.gpus}", file=sys.stderr)
         raise SystemExit(2)
 
+    extras = extra_legs(args, world_env)
     # roofline.traffic, measured by two counter passes over a child of this script BEFORE this process touches the GPU
-    # (N = 1 at the headline size only; ~40 s; --no-traffic skips it and the line falls back to the committed counters)
+    # (--full, N = 1 at the headline size only; ~40 s; --no-traffic skips it and the line falls back to the committed counters)
     traffic_run = None
-    if world_env == 1 and not args.no_traffic and args.gb is None and args.algo == 2:
+    if "traffic" in extras:
         traffic_run = measure_traffic_in_run(int(10.0 * 1e9) // REC * REC)
 
     import torch
@@ -1265,7 +1298,9 @@ def main():
         assert sharding.phase_is_consistent(first_line_index % 4, exact), "phase guess contradicted by the exact counts"
     # per-launch device time of the scan from HIP events on the launch stream, outside the wall-clock region (recording
     # 2 x steps x launches events inside it would sit in the measured loop); the dominant kernel is k_fused<FastqFormat>
-    avg_ms, min_ms = timed_launches(torch, launch, 20, warm=0)
+    avg_ms = min_ms = None
+    if "roofline" in extras:
+        avg_ms, min_ms = timed_launches(torch, launch, 20, warm=0)
 
     # the columns the last launch left in HBM, every row, against the generator's closed forms: records owned by this
     # shard are those whose LAST line ends in it
@@ -1276,7 +1311,10 @@ def main():
     ver = torch.tensor([1 if verified else 0], dtype=torch.int64, device=coll_dev)
     if world > 1:
         per_rank = [None] * world
-        dist.all_gather_object(per_rank, {"rank": rank, "timed_s": dt, "avg_launch_ms": avg_ms, "records": n_rec_local})
+        mine = {"rank": rank, "timed_s": dt, "records": n_rec_local}
+        if avg_ms is not None:
+            mine["avg_launch_ms"] = avg_ms
+        dist.all_gather_object(per_rank, mine)
         for pr in per_rank:
             if coll.get("ranks") and coll["ranks"][pr["rank"]] is not None:
                 coll["ranks"][pr["rank"]].update({k: v for k, v in pr.items() if k != "rank"})
@@ -1292,29 +1330,10 @@ def main():
 
     # reader level, sharded: every rank opens the same file with its rank (file -> COUNT(*) per shard, PCIe inclusive)
     reader_sharded = None
-    if world > 1 and not args.no_configs:
+    if "reader_sharded" in extras:
         reader_sharded = sharded_reader_leg(torch, dist, lib, device, world, rank, local_rank, coll_dev, args)
 
     if rank == 0:
-        achieved = n_bytes / (avg_ms * 1e-3) / 1e9
-        # the same box's read-only stream rate: exg_count_newlines over the same buffer — every
-        # byte leaves HBM once, nothing is written
-        cnt = torch.zeros(1, dtype=torch.int64, device="cuda")
-        ro_ms, _ = timed_launches(torch, lambda: device.check(lib.exg_count_newlines(C.c_void_p(d_in.data_ptr()), halo, n_bytes,
-                                                                                     C.c_void_p(cnt.data_ptr()), device.stream_ptr())), 5, warm=1)
-        read_only = (n_bytes - halo) / (ro_ms * 1e-3) / 1e9
-        traffic, traffic_src = None, None
-        pmc = os.path.join(ROOT, "profiles", "pmc_fastq_fused.json")
-        if traffic_run:
-            traffic, traffic_src = traffic_run["traffic"], traffic_run["source"]
-        elif os.path.exists(pmc):
-            with open(pmc) as f:
-                j = json.load(f)
-            # (counters were taken on the 10 GB launch of config 2: only that launch is priced with them)
-            traffic = j.get("hbm_bytes_per_launch_10GB") if abs(n_bytes - 9999999692) < 1e8 else None
-            age_h = (time.time() - os.path.getmtime(pmc)) / 3600.0
-            traffic_src = (f"profiles/pmc_fastq_fused.json, tag {j.get('tag')}, file {age_h:.1f} h old (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this "
-                           "command, gfx950 corrections; NOT re-measured in this run: --no-traffic, no rocprofv3, or the in-run passes failed)")
         out = {
             "metric": "FASTQ records/sec into DataChunks",
             "value": total_records * L * args.steps / dt,
@@ -1342,7 +1361,28 @@ def main():
                 "columns": "name,description,sequence,quality_scores as duckdb::string_t + validity",
                 "verification": "every row of the last launch's four columns + validity against the generator's closed forms, on the device",
             },
-            "roofline": {
+        }
+        if "roofline" in extras:
+            achieved = n_bytes / (avg_ms * 1e-3) / 1e9
+            # the same box's read-only stream rate: exg_count_newlines over the same buffer — every
+            # byte leaves HBM once, nothing is written
+            cnt = torch.zeros(1, dtype=torch.int64, device="cuda")
+            ro_ms, _ = timed_launches(torch, lambda: device.check(lib.exg_count_newlines(C.c_void_p(d_in.data_ptr()), halo, n_bytes,
+                                                                                         C.c_void_p(cnt.data_ptr()), device.stream_ptr())), 5, warm=1)
+            read_only = (n_bytes - halo) / (ro_ms * 1e-3) / 1e9
+            traffic, traffic_src = None, None
+            pmc = os.path.join(ROOT, "profiles", "pmc_fastq_fused.json")
+            if traffic_run:
+                traffic, traffic_src = traffic_run["traffic"], traffic_run["source"]
+            elif os.path.exists(pmc):
+                with open(pmc) as f:
+                    j = json.load(f)
+                # (counters were taken on the 10 GB launch of config 2: only that launch is priced with them)
+                traffic = j.get("hbm_bytes_per_launch_10GB") if abs(n_bytes - 9999999692) < 1e8 else None
+                age_h = (time.time() - os.path.getmtime(pmc)) / 3600.0
+                traffic_src = (f"profiles/pmc_fastq_fused.json, tag {j.get('tag')}, file {age_h:.1f} h old (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this "
+                               "command, gfx950 corrections; NOT re-measured in this run: --no-traffic, no rocprofv3, or the in-run passes failed)")
+            out["roofline"] = {
                 "bound": "hbm",
                 "achieved": achieved,
                 "peak": HBM_PEAK_GBPS,
@@ -1359,11 +1399,10 @@ def main():
                 "min_launch_ms": min_ms,
                 "read_only_stream_GBps": read_only,
                 "frac_of_read_only_stream": achieved / read_only,
-            },
-        }
+            }
         if reader_sharded:
             out["reader_sharded"] = reader_sharded
-        if world == 1 and not args.no_configs:
+        if "configs" in extras:
             del scan, d_in
             torch.cuda.empty_cache()
             # side legs: a failure in one of them (no scratch space, ...) is reported in its object, never at the cost of the line
@@ -1375,11 +1414,11 @@ def main():
             out["end_to_end_arrow"] = cfg.pop("end_to_end_arrow", None)
             out["configs"] = cfg
             try:
-                if not args.legs or "record_shapes" in args.legs.split(","):
+                if "record_shapes" in extras:
                     out["record_shapes"] = run_record_shapes(torch, lib, args)
             except Exception as e:  # noqa: BLE001
                 out["record_shapes"] = {"error": f"{type(e).__name__}: {e}"}
-        if world == 1 and not args.no_cpu_baseline:
+        if "cpu_baseline" in extras:
             try:
                 out["cpu_baseline"] = cpu_baseline()
             except Exception as e:  # noqa: BLE001

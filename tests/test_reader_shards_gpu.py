@@ -314,7 +314,7 @@ def _free_port():
 def test_bench_two_ranks_on_one_gpu(gpu):
     """bench.py as the driver launches it for N > 1 (torch.distributed.run, one rank per GPU), here with two ranks sharing
     cuda:0 over gloo: the byte-range shards, the phase all_gather, the COUNT(*) all_reduce, the closed-form verification of
-    both shards and the reader-level leg must produce one JSON line with the whole-job numbers."""
+    both shards and the reader-level leg (--full) must produce one JSON line with the whole-job numbers."""
     import json
     import os
     import subprocess
@@ -323,7 +323,7 @@ def test_bench_two_ranks_on_one_gpu(gpu):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--launches-per-step", "2", "--gb", "0.5", "--e2e-gb", "0.25", "--backend", "gloo", "--single-device"]
+           "--launches-per-step", "2", "--gb", "0.5", "--e2e-gb", "0.25", "--backend", "gloo", "--single-device", "--full"]
     res = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
@@ -339,7 +339,7 @@ def test_bench_two_ranks_on_one_gpu(gpu):
 def test_bench_launches_its_own_ranks(gpu):
     """`python3 bench.py --gpus 2 ...` with NO launcher (what the driver's 1-GPU command line looks like with another N): the
     script starts the two ranks itself, as a child torch.distributed.run, and its one JSON line says n_gpus = 2; the sharded
-    reader leg is verified by digest (every row of every shard, with its index in the file)."""
+    reader leg (--full) is verified by digest (every row of every shard, with its index in the file)."""
     import json
     import os
     import subprocess
@@ -347,7 +347,7 @@ def test_bench_launches_its_own_ranks(gpu):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo", "--single-device", "--steps", "2",
-           "--warmup", "1", "--launches-per-step", "2", "--gb", "0.5", "--e2e-gb", "0.25"]
+           "--warmup", "1", "--launches-per-step", "2", "--gb", "0.5", "--e2e-gb", "0.25", "--full"]
     res = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
@@ -362,7 +362,7 @@ def test_bench_eight_ranks_on_one_gpu(gpu):
     """BASELINE config 5's process layout on a one-GPU box: `python3 bench.py --gpus 8` with no launcher starts EIGHT ranks (eight
     processes' pinned / device pools and ports on one box), each scans its byte-range shard of the 8-shard file (middle shards:
     halo, no BOF / EOF, guessed phase), the 8-way all_gather verifies the phases, the all_reduce gives COUNT(*), and the
-    reader-level leg has eight readers of ONE shared file whose digests must add up to the generator's.  gloo + --single-device:
+    reader-level leg (--full) has eight readers of ONE shared file whose digests must add up to the generator's.  gloo + --single-device:
     the collectives' world size is printed in the line."""
     import json
     import os
@@ -371,7 +371,7 @@ def test_bench_eight_ranks_on_one_gpu(gpu):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--backend", "gloo", "--single-device", "--steps", "2",
-           "--warmup", "1", "--launches-per-step", "2", "--gb", "0.25", "--e2e-gb", "0.1"]
+           "--warmup", "1", "--launches-per-step", "2", "--gb", "0.25", "--e2e-gb", "0.1", "--full"]
     res = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=840)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]

@@ -9,18 +9,18 @@ OUT=$ROOT/gpurun_out
 mkdir -p $OUT
 export TMPDIR=/tmp
 cd $ROOT
-# the bench line as the driver takes it (all configs, cpu baseline)
+# the full bench line (roofline, all configs, cpu baseline)
 T0=$(date +%s)
-python3 bench.py > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
-echo "bench.py (default flags): $(( $(date +%s) - T0 )) s"
+python3 bench.py --full > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
+echo "bench.py --full: $(( $(date +%s) - T0 )) s"
 cd /tmp
 # headline kernel: per-kernel times of the same command (without the side legs), then the HBM counters in passes of their own
-rocprofv3 --kernel-trace --stats -d $OUT/${TAG}_kt -o kt --output-format csv -- python3 $ROOT/bench.py --no-configs --no-cpu-baseline > $OUT/${TAG}_kt.log 2>&1
+rocprofv3 --kernel-trace --stats -d $OUT/${TAG}_kt -o kt --output-format csv -- python3 $ROOT/bench.py --full --no-configs --no-cpu-baseline > $OUT/${TAG}_kt.log 2>&1
 for c in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --kernel-trace --pmc $c -d $OUT/${TAG}_pmc_$c -o pmc --output-format csv -- python3 $ROOT/bench.py --steps 2 --warmup 1 --launches-per-step 2 --no-configs --no-cpu-baseline > $OUT/${TAG}_pmc_$c.log 2>&1
+  rocprofv3 --kernel-trace --pmc $c -d $OUT/${TAG}_pmc_$c -o pmc --output-format csv -- python3 $ROOT/bench.py --steps 2 --warmup 1 --launches-per-step 2 --full --no-configs --no-cpu-baseline > $OUT/${TAG}_pmc_$c.log 2>&1
 done
 # the configs legs (config 1 FASTA, config 3 VCF, config 4 BGZF inflate + CRC-32, end to end): every kernel of them
-rocprofv3 --kernel-trace --stats -d $OUT/${TAG}_kt_configs -o kt --output-format csv -- python3 $ROOT/bench.py --steps 2 --warmup 1 --launches-per-step 2 --no-cpu-baseline --gz-gb 2 --e2e-gb 2 > $OUT/${TAG}_kt_configs.log 2>&1
+rocprofv3 --kernel-trace --stats -d $OUT/${TAG}_kt_configs -o kt --output-format csv -- python3 $ROOT/bench.py --steps 2 --warmup 1 --launches-per-step 2 --full --no-cpu-baseline --gz-gb 2 --e2e-gb 2 > $OUT/${TAG}_kt_configs.log 2>&1
 # records of other shapes (long reads, 36 bp reads, multi-sample VCF): the any-shape scan k_fused<.., 1>, the lean scan + redo run, k_*_far
 rocprofv3 --kernel-trace --stats -d $OUT/${TAG}_kt_shapes -o kt --output-format csv -- python3 $ROOT/tools/shapes_probe.py 4 > $OUT/${TAG}_kt_shapes.log 2>&1
 # zstd through the reader (a 4 GB single frame, level 3, no Content_Checksum: three timed passes + the warm-up; the probe reads its knobs from the environment)
