@@ -195,8 +195,9 @@ static int open_source(exg_reader *r, std::shared_ptr<PinnedBlock> &blk, const s
     r->gz_header_prefix = 0;
     const size_t queued = getenv("EXG_SOURCE_QUEUE") ? (size_t)std::max(1, atoi(getenv("EXG_SOURCE_QUEUE"))) : r->mem_cap ? 1 : 2;
     auto make = [&](uint64_t c_begin, uint64_t c_end, bool bgzf_only, const uint64_t *marks) {
-        std::unique_ptr<SegmentProducer> prod = r->compression == kGzip ? make_gzip_producer(r, fd, c_begin, c_end, target, path, bgzf_only, reserve, marks)
-                                                                        : make_zstd_producer(r, fd, n, c_begin, c_end, target, path, reserve, marks);
+        std::unique_ptr<SegmentProducer> prod = r->compression == kGzip    ? make_gzip_producer(r, fd, c_begin, c_end, target, path, bgzf_only, reserve, marks)
+                                                : r->compression == kBzip2 ? make_bzip2_producer(r, fd, n, target, path, reserve)
+                                                                           : make_zstd_producer(r, fd, n, c_begin, c_end, target, path, reserve, marks);
         // (EXG_OPEN_CHUNKS: the caller said it will pull chunks — the segments travel to the host from the first one on)
         const bool mirror0 = r->expect_chunks && !r->arrow_emit && payload_route(r) == kPayloadMirror;
         return std::unique_ptr<DecodedSource>(new DecodedSource(r->device, r->stream, std::move(prod), reserve, queued, &r->meter, mirror0));
@@ -204,6 +205,8 @@ static int open_source(exg_reader *r, std::shared_ptr<PinnedBlock> &blk, const s
     if (r->compression == kGzip && n == 0) return fail(r, EXG_E_PARSE, "empty gzip file '" + path + "'");
     r->fa_shard = false;
     r->fa_end = ~0ull;
+    if (r->shard_count > 1 && r->compression == kBzip2)
+        return fail(r, EXG_E_UNSUPPORTED, "shards of a bzip2 input are not supported (one file is one shard): '" + path + "'");
     if (r->shard_count > 1) {
         // VCF: every rank needs the header (schema, and where the data begins): read from the start of the file by a
         // source of its own, kept on the host like in the unsharded case
@@ -317,6 +320,7 @@ static int count_newlines_in_front(exg_reader *r, uint64_t *out) {
     struct stat st;
     if (fstat(fd, &st)) return fail(r, EXG_E_IO, "cannot stat '" + path + "'");
     const uint64_t reserve = source_reserve(r), target = r->device_batch_bytes;
+    if (r->compression == kBzip2) return fail(r, EXG_E_UNSUPPORTED, "shards of a bzip2 input are not supported: '" + path + "'");
     std::unique_ptr<SegmentProducer> prod = r->compression == kGzip
                                                 ? make_gzip_producer(r, fd, 0, r->own_c_begin, target, path, true, reserve, nullptr)
                                                 : make_zstd_producer(r, fd, (uint64_t)st.st_size, 0, r->own_c_begin, target, path, reserve, nullptr);

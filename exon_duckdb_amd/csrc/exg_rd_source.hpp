@@ -170,6 +170,9 @@ std::unique_ptr<SegmentProducer> make_gzip_producer(exg_reader *r, int fd, uint6
 std::unique_ptr<SegmentProducer> make_zstd_producer(exg_reader *r, int fd, uint64_t n, uint64_t c_begin, uint64_t c_end, uint64_t target,
                                                     const std::string &path, uint64_t reserve, const uint64_t mark_at[2] = nullptr);
 
+// exg_rd_bzip2.cpp: every bzip2 stream of file bytes [0, n) of fd (one file is one shard's: no marks)
+std::unique_ptr<SegmentProducer> make_bzip2_producer(exg_reader *r, int fd, uint64_t n, uint64_t target, const std::string &path, uint64_t reserve);
+
 int plan_zstd_shard(exg_reader *r, int fd, uint64_t n, const std::string &path, uint64_t halo_want, uint64_t header_bytes, uint64_t *c_begin,
                     uint64_t *c_end, uint64_t *own_lo, uint64_t *own_hi, bool *bytes_follow);
 

@@ -76,8 +76,12 @@ extern "C" int exg_open(const exg_open_args *args, exg_reader **out) {
     }
     int rc = list_files(r.get(), path);
     if (rc) return rc;
-    if (r->compression != kNone && r->compression != kGzip && r->compression != kZstd) {
-        exg::set_error("compression is not supported: gzip and zstd have device decoders, bzip2 / xz do not, and there is no CPU fallback");
+    if (r->compression != kNone && r->compression != kGzip && r->compression != kZstd && r->compression != kBzip2) {
+        exg::set_error("compression is not supported: gzip, zstd and bzip2 have device decoders, xz does not, and there is no CPU fallback");
+        return EXG_E_UNSUPPORTED;
+    }
+    if (r->compression == kBzip2 && r->shard_count > 1) {  // (one bzip2 file is one shard: blocks are not split among readers)
+        exg::set_error("exg_open: shards of a bzip2 input are not supported (shard_count %u): one file is one shard", r->shard_count);
         return EXG_E_UNSUPPORTED;
     }
     const int n_dev = exg_device_count();
@@ -433,7 +437,7 @@ extern "C" int exg_reader_stats_of(exg_reader *r, exg_reader_stats *out) {
         struct stat sb;
         if (stat(f.c_str(), &sb) == 0 && S_ISREG(sb.st_mode)) out->input_bytes += (uint64_t)sb.st_size;
     }
-    out->input_compression = r->compression == exg_rd::kNone ? 0 : r->compression == exg_rd::kZstd ? 2 : 1;
+    out->input_compression = r->compression == exg_rd::kNone ? 0 : r->compression == exg_rd::kZstd ? 2 : r->compression == exg_rd::kBzip2 ? 3 : 1;
     if (r->fan) {
         // the front of a fan-out holds next to nothing itself: its stripes' readers (their own meters, on the workers' threads) do
         const exg_rd::FanOut::Stats fs = r->fan->stats();

@@ -71,7 +71,7 @@ struct ExonTableFunction {
         std::vector<std::string> all_names;
         std::vector<LogicalType> all_types;
         uint64_t input_bytes = 0;        // size of the input files on disk (exg_reader_stats.input_bytes at bind)
-        uint64_t input_compression = 0;  // 0 text, 1 gzip, 2 zstd
+        uint64_t input_compression = 0;  // 0 text, 1 gzip, 2 zstd, 3 bzip2
     };
 
     struct GlobalState : public D::GlobalTableFunctionState {

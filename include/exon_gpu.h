@@ -55,7 +55,7 @@ extern "C" {
 #define EXG_E_NO_DEVICE (-2)   /* HIP runtime / GPU missing: the product path fails loudly */
 #define EXG_E_HIP (-3)         /* a HIP call failed; see exg_last_error_message() */
 #define EXG_E_IO (-4)
-#define EXG_E_UNSUPPORTED (-5) /* e.g. bzip2 / xz: no device decoder, and there is no CPU fallback */
+#define EXG_E_UNSUPPORTED (-5) /* e.g. xz: no device decoder, and there is no CPU fallback */
 #define EXG_E_PARSE (-6)       /* reader level: a record failed to parse */
 #define EXG_E_CAPACITY (-7)    /* output arrays too small */
 #define EXG_E_NOMEM (-8)
@@ -351,7 +351,7 @@ typedef struct exg_inflate_round_args {
     int need_more;
 } exg_inflate_round_args;
 int exg_inflate_round(exg_inflate_round_args *args);
-/* Give a device block the library handed out (exg_inflate_stream, exg_inflate_round, exg_zstd_decode) back to its pool. */
+/* Give a device block the library handed out (exg_inflate_stream, exg_inflate_round, exg_zstd_decode, exg_bzip2_decode) back to its pool. */
 void exg_free_device(void *d_ptr, uint64_t bytes);
 
 /* ---- device zstd (RFC 8878 frames; replaces zstd 0.12.3 / libzstd 1.5.2 behind rust/src/arrow_reader.rs:73, :87-88;
@@ -367,6 +367,16 @@ void exg_free_device(void *d_ptr, uint64_t bytes);
  * 128 MiB and dictionaries are refused like libzstd's defaults do.  Synchronises the stream.
  * Errors: EXG_E_PARSE, libzstd's wording in exg_last_error_message(). */
 int exg_zstd_decode(const uint8_t *h_comp, const void *d_comp, uint64_t n, void **d_out, uint64_t *produced, void *stream);
+
+/* ---- device bzip2 (replaces libbz2 behind compression='bzip2', rust/src/arrow_reader.rs:87-88) ----------------------
+ * Every concatenated stream of d_comp[0, n) (device memory), as bz2.decompress reads them: blocks are found on the device
+ * by their 48-bit magic and chained (a block counts only where the one in front ends), decoded one wavefront each, and
+ * every block CRC and stream CRC is verified.  On success *d_out is a block of the library's device pool (*produced
+ * bytes + 64 zeroed): exg_free_device(*d_out, *produced + 64).  Synchronises the stream; on an error nothing stays
+ * allocated.  Errors: EXG_E_PARSE with libbz2's categories in exg_last_error_message() — "not a bzip2 stream",
+ * "data error in block N: <reason>" (a CRC mismatch included), "unexpected end of stream".  Randomised blocks
+ * (bzip2 < 0.9.5) are refused as a data error. */
+int exg_bzip2_decode(const void *d_comp, uint64_t n, void **d_out, uint64_t *produced, void *stream);
 
 /* ---- (2) reader level ----------------------------------------------------------- */
 typedef struct exg_reader exg_reader;
@@ -494,7 +504,7 @@ typedef struct exg_reader_stats {
                                   * EXG_ALGO_FUSED_FULL for the rest of the input (a fan-out reader: 0) */
     uint64_t input_bytes;        /* ABI 8: size of the reader's input files on disk (all files of a directory; a shard: the whole
                                   * files), what TableFunction::cardinality estimates rows from (module.cpp:307) */
-    uint64_t input_compression;  /* ABI 8: 0 plain text, 1 gzip / BGZF, 2 zstd (input_bytes are compressed bytes then) */
+    uint64_t input_compression;  /* ABI 8: 0 plain text, 1 gzip / BGZF, 2 zstd, 3 bzip2 (input_bytes are compressed bytes then) */
     uint64_t nested_ns;          /* ABI 9: read_vcf — wall time the reader's thread spent making the nested columns (id / alt / filter /
                                   * info / formats) of its batches on the device, counting passes, prefix sums and children, up to the
                                   * point where their vectors start for the host (exg_vcf_nested.hpp) */
