@@ -24,11 +24,7 @@ namespace {
 class Bzip2Producer : public SegmentProducer {
 public:
     Bzip2Producer(exg_reader *r, int fd, uint64_t n, uint64_t target, const std::string &path, uint64_t reserve)
-        : device_(r->device), fd_(fd), n_(n), cap_(r->mem_cap), target_(std::max<uint64_t>(target, 128u << 10)), path_(path), reserve_((reserve + 15) & ~15ull) {
-        // (without a cap a round decodes ~1 GiB: its kernels are many short dependent launches whose cost does not grow with it)
-        if (!cap_ && target_ >= (128ull << 20)) target_ = std::max<uint64_t>(target_, 1ull << 30);
-        if (const char *e = getenv("EXG_STREAM_ROUND_OUT")) target_ = std::max<uint64_t>(128u << 10, strtoull(e, nullptr, 10));
-    }
+        : device_(r->device), fd_(fd), n_(n), cap_(r->mem_cap), target_(round_out_bytes(target, 128u << 10, r->mem_cap != 0)), path_(path), reserve_((reserve + 15) & ~15ull) {}
     int run(SegmentSink &sink, std::string *err) override;
 
 private:
@@ -39,16 +35,11 @@ private:
 };
 
 int Bzip2Producer::run(SegmentSink &sink, std::string *err) {
-    hipStream_t st = nullptr;
-    if (stream_pool()->take(device_, &st) != hipSuccess) {
+    StreamLease st(device_);
+    if (!st.acquire()) {
         *err = "cannot create a stream for the bzip2 decoder";
         return EXG_E_HIP;
     }
-    struct StreamBack {
-        int dev;
-        hipStream_t s;
-        ~StreamBack() { stream_pool()->give(dev, s); }
-    } stream_back{device_, st};
     int level = 9;
     if (n_ >= 4) {
         uint8_t head[4];
@@ -59,11 +50,7 @@ int Bzip2Producer::run(SegmentSink &sink, std::string *err) {
         if (head[3] >= '1' && head[3] <= '9') level = head[3] - '0';
     }
     PoolBuf d_win(device_, st);
-    struct Pin {
-        char *p = nullptr;
-        size_t cap = 0;
-        ~Pin() { if (p) global_pool()->give(p, cap); }
-    } pin;
+    PinBuf pin;
     uint64_t bit = 0, d_pos = 0, blocks = 0;  // where the next round begins (file bit), decoded bytes so far, blocks so far
     bool at_header = true, first = true, pushed_last = false;
     uint32_t scrc = 0;
@@ -86,21 +73,12 @@ int Bzip2Producer::run(SegmentSink &sink, std::string *err) {
                 return EXG_E_HIP;
             }
         }
-        if (pin.cap < wcap) {
-            if (pin.p) global_pool()->give(pin.p, pin.cap);
-            size_t w = wcap + wcap / 4;
-            pin.p = global_pool()->take(&w);
-            pin.cap = pin.p ? w : 0;
-            if (!pin.p) {
-                *err = "out of pinned host memory for the compressed bytes of '" + path_ + "'";
-                return EXG_E_HIP;
-            }
+        if (pin.cap < wcap && !pin.ensure(wcap + wcap / 4)) {
+            *err = "out of pinned host memory for the compressed bytes of '" + path_ + "'";
+            return EXG_E_HIP;
         }
-        bool hip_failed = false;
-        if (len && !pread_parallel(device_, fd_, lo, (size_t)len, pin.p, (char *)d_win.p, st, &hip_failed)) {
-            *err = hip_failed ? "hipMemcpyAsync failed" : "short read of '" + path_ + "'";
-            return hip_failed ? EXG_E_HIP : EXG_E_IO;
-        }
+        if (len)
+            if (int rc = read_to_device(device_, fd_, lo, (size_t)len, pin.p, (char *)d_win.p, st, path_, err)) return rc;
         if (hipMemsetAsync((char *)d_win.p + len, 0, 128, st) != hipSuccess) {
             *err = "hipMemsetAsync failed";
             return EXG_E_HIP;
@@ -133,7 +111,7 @@ int Bzip2Producer::run(SegmentSink &sink, std::string *err) {
             return sink.push(std::move(seg));
         };
         if (rc) {
-            const std::string msg = std::string(exg_last_error_message()) + " in '" + path_ + "'";
+            const std::string msg = std::string(exg_last_error_message()) + in_file(path_);
             if (R.d_out && good) (void)push(good, false);  // the rows in front of the damage first
             else if (R.d_out) sink.give(R.d_out, R.alloc);
             *err = msg;
@@ -146,7 +124,7 @@ int Bzip2Producer::run(SegmentSink &sink, std::string *err) {
                 scrc = bz::fold_crc(scrc, e.value);
             } else {
                 if (e.value != scrc && crc_error.empty())
-                    crc_error = "bzip2: data error: stream CRC mismatch (combined CRC " + std::to_string(scrc) + ", stored " + std::to_string(e.value) + ") in '" + path_ + "'";
+                    crc_error = "bzip2: data error: stream CRC mismatch (combined CRC " + std::to_string(scrc) + ", stored " + std::to_string(e.value) + ")" + in_file(path_);
                 scrc = 0;
             }
         }
@@ -171,30 +149,12 @@ int Bzip2Producer::run(SegmentSink &sink, std::string *err) {
         }
         if (R.done) break;
         if (!progress && lo + len >= n_) {
-            *err = "bzip2: unexpected end of stream in '" + path_ + "'";
+            *err = "bzip2: unexpected end of stream" + in_file(path_);
             return EXG_E_PARSE;
         }
     }
-    if (!pushed_last && !sink.cancelled()) {  // (the consumer expects a last segment, even an empty one)
-        Segment seg;
-        seg.cap = (size_t)(reserve_ + 16 + 64);
-        seg.buf = sink.take(seg.cap);
-        if (!seg.buf) {
-            *err = "out of device memory";
-            return EXG_E_HIP;
-        }
-        seg.org = (int64_t)(d_pos & ~15ull) - (int64_t)reserve_;
-        seg.lo = seg.start = seg.hi = d_pos;
-        seg.last = true;
-        hipError_t he = hipMemsetAsync((char *)seg.buf + reserve_, 0, 16 + 64, st);
-        if (he == hipSuccess) he = hipStreamSynchronize(st);
-        if (he != hipSuccess) {
-            sink.give(seg.buf, seg.cap);
-            *err = std::string("hipMemsetAsync failed: ") + hipGetErrorString(he);
-            return EXG_E_HIP;
-        }
-        (void)sink.push(std::move(seg));
-    }
+    // (the consumer expects a last segment, even an empty one)
+    if (!pushed_last && !sink.cancelled()) return push_empty_last(sink, d_pos, reserve_, st, err);
     return EXG_OK;
 }
 

@@ -30,33 +30,7 @@ static uint32_t rd_le32(const uint8_t *p) { return p[0] | ((uint32_t)p[1] << 8) 
 
 namespace {
 
-#define GZ_HIP(expr)                                                                               \
-    do {                                                                                           \
-        hipError_t _e = (expr);                                                                    \
-        if (_e != hipSuccess) {                                                                    \
-            *err = std::string(#expr " failed: ") + hipGetErrorString(_e);                         \
-            return EXG_E_HIP;                                                                      \
-        }                                                                                          \
-    } while (0)
-
-// pinned host memory / device memory that grows on demand and goes back to its pool at the end
-struct PinBuf {
-    char *p = nullptr;
-    size_t cap = 0;
-    bool ensure(size_t n) {
-        if (n <= cap) return true;
-        release();
-        size_t want = n;
-        p = global_pool()->take(&want);
-        cap = p ? want : 0;
-        return p != nullptr;
-    }
-    void release() {
-        if (p) global_pool()->give(p, cap);
-        p = nullptr, cap = 0;
-    }
-    ~PinBuf() { release(); }
-};
+// device memory that grows on demand and goes back to its pool at the end
 struct DevBlock {
     int dev;
     void *p = nullptr;
@@ -87,14 +61,12 @@ public:
         // chunks on: rounds of one device batch (256 MiB) ran at 11 GB/s where rounds of 1 GiB run at 20+.  So without a
         // memory cap (and without a deliberately small device batch) a round decodes 1 GiB; the segment is scanned in
         // batches as usual.
-        member_round_ = target_;
-        if (!r->mem_cap && target_ >= (128ull << 20)) member_round_ = std::max<uint64_t>(target_, 1ull << 30);
-        if (const char *e = getenv("EXG_STREAM_ROUND_OUT")) member_round_ = std::max<uint64_t>(64u << 10, strtoull(e, nullptr, 10));
+        member_round_ = round_out_bytes(target_, 64u << 10, r->mem_cap != 0);
     }
     ~GzipProducer() override {
         for (auto &l : lanes_) l->join_read();
         for (auto &l : lanes_) {
-            if (l->st) stream_pool()->give(device_, l->st);  // (synchronises it: the blocks below are idle afterwards)
+            l->st.release();  // (synchronises it: the blocks below are idle afterwards)
             if (l->ev) (void)hipEventDestroy(l->ev);
         }
     }
@@ -104,7 +76,7 @@ public:
 
 private:
     struct Lane {
-        hipStream_t st = nullptr;
+        StreamLease st;
         hipEvent_t ev = nullptr;
         PinBuf pin, tab;  // the compressed window; the member table + what comes back (statuses, checksums)
         DevBlock d_comp, d_tab;
@@ -116,7 +88,7 @@ private:
         std::thread ra;
         bool ra_valid = false, ra_ok = false, ra_hip_failed = false;
         uint64_t ra_a0 = 0, ra_len = 0;
-        explicit Lane(int dev) : d_comp(dev), d_tab(dev) {}
+        explicit Lane(int dev) : st(dev), d_comp(dev), d_tab(dev) {}
         void join_read() {
             if (ra.joinable()) ra.join();
         }
@@ -162,9 +134,8 @@ private:
 GzipProducer::Lane *GzipProducer::lane(size_t i, std::string *err) {
     while (lanes_.size() <= i) {
         std::unique_ptr<Lane> l(new Lane(device_));
-        if (stream_pool()->take(device_, &l->st) != hipSuccess || hipEventCreateWithFlags(&l->ev, hipEventDisableTiming) != hipSuccess) {
+        if (!l->st.acquire() || hipEventCreateWithFlags(&l->ev, hipEventDisableTiming) != hipSuccess) {
             *err = "cannot create a stream for the gzip decoder";
-            if (l->st) stream_pool()->give(device_, l->st);
             return nullptr;
         }
         lanes_.push_back(std::move(l));
@@ -197,7 +168,7 @@ int GzipProducer::read_trailer(uint64_t at, uint32_t *crc, uint32_t *isize, std:
         got += (size_t)k;
     }
     if (got < 8) {
-        *err = "truncated gzip member (no trailer) in '" + path_ + "'";
+        *err = "truncated gzip member (no trailer)" + in_file(path_);
         return EXG_E_PARSE;
     }
     *crc = rd_le32(t);
@@ -219,15 +190,15 @@ int GzipProducer::crc_of(const void *d, uint64_t n, hipStream_t st, uint32_t *cr
         return EXG_E_HIP;
     }
     uint32_t *d_crc = (uint32_t *)((char *)dt + n_seg * sizeof(exg_crc_segment));
-    GZ_HIP(hipMemcpyAsync(dt, segs.data(), n_seg * sizeof(exg_crc_segment), hipMemcpyHostToDevice, st));
+    PRODUCER_HIP(hipMemcpyAsync(dt, segs.data(), n_seg * sizeof(exg_crc_segment), hipMemcpyHostToDevice, st));
     const int rc = exg_crc32_segments(d, (const exg_crc_segment *)dt, (uint32_t)n_seg, d_crc, st);
     if (rc) {
         *err = exg_last_error_message();
         return rc;
     }
     std::vector<uint32_t> c(n_seg);
-    GZ_HIP(hipMemcpyAsync(c.data(), d_crc, n_seg * 4, hipMemcpyDeviceToHost, st));
-    GZ_HIP(hipStreamSynchronize(st));
+    PRODUCER_HIP(hipMemcpyAsync(c.data(), d_crc, n_seg * 4, hipMemcpyDeviceToHost, st));
+    PRODUCER_HIP(hipStreamSynchronize(st));
     uint32_t total = c[0];
     for (uint64_t i = 1; i < n_seg; i++) total = exg_crc32_combine(total, c[i], segs[i].len);
     *crc = total;
@@ -259,11 +230,7 @@ int GzipProducer::bgzf_issue(SegmentSink &sink, Lane &l, bool *not_bgzf, std::st
             *err = "out of memory for a window of compressed bytes of '" + path_ + "'";
             return EXG_E_HIP;
         }
-        bool hip_failed = false;
-        if (!pread_parallel(device_, fd_, a0, (size_t)len, l.pin.p, (char *)l.d_comp.p, l.st, &hip_failed)) {
-            *err = hip_failed ? "hipMemcpyAsync failed" : "short read of '" + path_ + "'";
-            return hip_failed ? EXG_E_HIP : EXG_E_IO;
-        }
+        if (int rc = read_to_device(device_, fd_, a0, (size_t)len, l.pin.p, (char *)l.d_comp.p, l.st, path_, err)) return rc;
     }
     // the members that are complete in the window, up to a segment's worth of output
     Peek pk((const uint8_t *)l.pin.p, -1, len);
@@ -290,7 +257,7 @@ int GzipProducer::bgzf_issue(SegmentSink &sink, Lane &l, bool *not_bgzf, std::st
         const uint8_t *h = pk.at(rel, 18);
         const bool looks_bgzf = h && h[0] == 0x1f && h[1] == 0x8b && h[2] == 8 && (h[3] & 4) && h[12] == 'B' && h[13] == 'C';
         if (looks_bgzf || !h) {
-            *err = "truncated gzip member at byte " + std::to_string(c_pos_) + " in '" + path_ + "'";
+            *err = "truncated gzip member at byte " + std::to_string(c_pos_) + in_file(path_);
             return EXG_E_PARSE;
         }
         *not_bgzf = true;
@@ -367,13 +334,13 @@ void GzipProducer::start_read(Lane &l, uint64_t a0, uint64_t len) {
 }
 
 int GzipProducer::bgzf_finish(Lane &l, std::string *err) {
-    GZ_HIP(hipEventSynchronize(l.ev));
+    PRODUCER_HIP(hipEventSynchronize(l.ev));
     const exg_inflate_member *m = (const exg_inflate_member *)l.tab.p;
     const exg_inflate_status *s = (const exg_inflate_status *)(l.tab.p + l.k * sizeof(exg_inflate_member));
     const uint32_t *c = (const uint32_t *)((const char *)s + l.k * sizeof(exg_inflate_status));
     for (uint64_t i = 0; i < l.k; i++) {
         if (s[i].code || s[i].produced != m[i].out_cap) {
-            *err = "corrupt deflate stream (member " + std::to_string(l.first_member + i) + ", code " + std::to_string(s[i].code) + ") in '" + path_ + "'";
+            *err = "corrupt deflate stream (member " + std::to_string(l.first_member + i) + ", code " + std::to_string(s[i].code) + ")" + in_file(path_);
             return EXG_E_PARSE;
         }
         if (c[i] != l.crc_expect[i]) {
@@ -478,12 +445,12 @@ int GzipProducer::plain_member(SegmentSink &sink, std::string *err) {
     int open_ended = 0;
     const int rc = exg_gzip_index(head.data(), got, 0, &m, 1, &k, &total, &open_ended);
     if (rc == EXG_E_CAPACITY) {  // (a sized member first: BGZF in a window the walk above could not finish — a truncated file)
-        *err = "truncated gzip member at byte " + std::to_string(c_pos_) + " in '" + path_ + "'";
+        *err = "truncated gzip member at byte " + std::to_string(c_pos_) + in_file(path_);
         return EXG_E_PARSE;
     }
     if (rc || k == 0) {
         const std::string what = rc ? exg_last_error_message() : "invalid gzip header";
-        *err = what + " (member at byte " + std::to_string(c_pos_) + ") in '" + path_ + "'";
+        *err = what + " (member at byte " + std::to_string(c_pos_) + ")" + in_file(path_);
         return EXG_E_PARSE;
     }
     n_members_++;
@@ -506,11 +473,7 @@ int GzipProducer::small_member(SegmentSink &sink, uint64_t stream_off, std::stri
         *err = "out of memory for the compressed bytes of '" + path_ + "'";
         return EXG_E_HIP;
     }
-    bool hip_failed = false;
-    if (!pread_parallel(device_, fd_, a0, (size_t)len, l.pin.p, (char *)l.d_comp.p, l.st, &hip_failed)) {
-        *err = hip_failed ? "hipMemcpyAsync failed" : "short read of '" + path_ + "'";
-        return hip_failed ? EXG_E_HIP : EXG_E_IO;
-    }
+    if (int rc = read_to_device(device_, fd_, a0, (size_t)len, l.pin.p, (char *)l.d_comp.p, l.st, path_, err)) return rc;
     const uint64_t comp_size = c_end_ - stream_off;
     // DEFLATE expands at most 1032:1; `cat a.vcf.gz b.vcf.gz` of highly compressible members must not be reported as
     // corrupt for outgrowing a guessed ratio.  A big member (only with the chunked decoder off) gets 8:1 + its ISIZE.
@@ -545,7 +508,7 @@ int GzipProducer::small_member(SegmentSink &sink, uint64_t stream_off, std::stri
         rc = EXG_E_HIP;
     }
     if (!rc && h->s.code) {
-        *err = "corrupt deflate stream (member " + std::to_string(n_members_ - 1) + ", code " + std::to_string(h->s.code) + ") in '" + path_ + "'";
+        *err = "corrupt deflate stream (member " + std::to_string(n_members_ - 1) + ", code " + std::to_string(h->s.code) + ")" + in_file(path_);
         rc = EXG_E_PARSE;
     }
     uint32_t crc = 0, isize = 0;
@@ -627,11 +590,7 @@ int GzipProducer::big_member(SegmentSink &sink, uint64_t stream_off, std::string
                 *err = "out of memory for a window of compressed bytes of '" + path_ + "'";
                 return EXG_E_HIP;
             }
-            bool hip_failed = false;
-            if (!pread_parallel(device_, fd_, a0, (size_t)len, l.pin.p, (char *)l.d_comp.p, l.st, &hip_failed)) {
-                *err = hip_failed ? "hipMemcpyAsync failed" : "short read of '" + path_ + "'";
-                return hip_failed ? EXG_E_HIP : EXG_E_IO;
-            }
+            if (int rc = read_to_device(device_, fd_, a0, (size_t)len, l.pin.p, (char *)l.d_comp.p, l.st, path_, err)) return rc;
         }
         if (ahead && partial) {
             // the round ends at a block boundary at or in front of the last block start it finds: the next window begins a few
@@ -641,7 +600,7 @@ int GzipProducer::big_member(SegmentSink &sink, uint64_t stream_off, std::string
             const uint64_t na0 = (a0 + len > slack ? a0 + len - slack : 0) & ~15ull;
             if (na0 > a0) start_read(*lanes2[li ^ 1], na0, std::min<uint64_t>(want + slack, c_end_ - na0));
         }
-        GZ_HIP(hipMemsetAsync((char *)l.d_comp.p + len, 0, 64, l.st));
+        PRODUCER_HIP(hipMemsetAsync((char *)l.d_comp.p + len, 0, 64, l.st));
         exg_inflate_round_args a;
         memset(&a, 0, sizeof a);
         a.d_comp = l.d_comp.p;
@@ -664,12 +623,12 @@ int GzipProducer::big_member(SegmentSink &sink, uint64_t stream_off, std::string
             rc = exg_inflate_round(&a);
         }
         if (rc) {
-            *err = std::string(exg_last_error_message()) + " in '" + path_ + "'";
+            *err = std::string(exg_last_error_message()) + in_file(path_);
             return rc;
         }
         if (a.need_more) {
             if (!partial) {
-                *err = "corrupt deflate stream (no block start in the rest of the member) in '" + path_ + "'";
+                *err = "corrupt deflate stream (no block start in the rest of the member)" + in_file(path_);
                 return EXG_E_PARSE;
             }
             grow *= 2;
@@ -726,7 +685,7 @@ int GzipProducer::big_member(SegmentSink &sink, uint64_t stream_off, std::string
         }
         if (used_bits == 0 && a.produced == 0) {
             sink.give(seg.buf, seg.cap);
-            *err = "corrupt deflate stream (the chunked decoder makes no progress) in '" + path_ + "'";
+            *err = "corrupt deflate stream (the chunked decoder makes no progress)" + in_file(path_);
             return EXG_E_PARSE;
         }
         pushed_last_ = false;
@@ -751,7 +710,7 @@ int GzipProducer::run(SegmentSink &sink, std::string *err) {
             const uint8_t *h = pk.at(c_pos_, 18);
             const bool looks_bgzf = h && h[0] == 0x1f && h[1] == 0x8b && h[2] == 8 && (h[3] & 4) && h[12] == 'B' && h[13] == 'C';
             if (looks_bgzf) {  // a BGZF header whose member does not fit the file: the walk above says why
-                *err = "truncated gzip member at byte " + std::to_string(c_pos_) + " in '" + path_ + "'";
+                *err = "truncated gzip member at byte " + std::to_string(c_pos_) + in_file(path_);
                 rc = EXG_E_PARSE;
             } else {
                 rc = plain_member(sink, err);
@@ -761,23 +720,9 @@ int GzipProducer::run(SegmentSink &sink, std::string *err) {
     }
     marks(sink);
     if (!pushed_last_ && !sink.cancelled()) {  // an empty range (a shard without members): the stream still ends
-        Segment seg;
-        int rc = new_segment(sink, 0, &seg, err);
-        if (rc) return rc;
         Lane *l = lane(0, err);
-        if (!l) {
-            sink.give(seg.buf, seg.cap);
-            return EXG_E_HIP;
-        }
-        hipError_t he = hipMemsetAsync((char *)seg.buf + ((int64_t)d_pos_ - seg.org), 0, 64, l->st);
-        if (he == hipSuccess) he = hipStreamSynchronize(l->st);
-        if (he != hipSuccess) {
-            sink.give(seg.buf, seg.cap);
-            *err = std::string("hipMemsetAsync failed: ") + hipGetErrorString(he);
-            return EXG_E_HIP;
-        }
-        seg.last = true;
-        (void)sink.push(std::move(seg));
+        if (!l) return EXG_E_HIP;
+        return push_empty_last(sink, d_pos_, reserve_, l->st, err);
     }
     return EXG_OK;
 }

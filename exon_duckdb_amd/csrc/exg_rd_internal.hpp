@@ -2,8 +2,11 @@
 //   exg_rd_io.cpp      pinned blocks, NUMA pinning, page cache -> pinned -> HBM uploads, the reader's device buffers
 //   exg_rd_bgzf.cpp    host only: the BGZF / gzip member walk (no HIP call; under ASan in tests/host_asan_driver.cpp)
 //   exg_rd_plan.cpp    host only: compression inference, shard planning, replacement_scan
-//   exg_rd_source.cpp  compressed inputs as a bounded stream of decoded segments in HBM (DecodedSource)
-//   exg_rd_gzip.cpp    the gzip / BGZF producer of such a stream;  exg_rd_zstd.cpp  the zstd producer
+//   exg_rd_source.cpp  compressed inputs as a bounded stream of decoded segments in HBM (DecodedSource), and what the
+//                      producers of such a stream share (exg_rd_source.hpp)
+//   exg_rd_gzip.cpp    the gzip / BGZF producer;  exg_rd_zstd.cpp  the zstd producer;  exg_rd_bzip2.cpp  the bzip2 producer
+//   exg_zstd_index.cpp host only: the zstd frame / block walk and a round's block list (no HIP call; under ASan as above)
+//   exg_rd_fanout.cpp  host only: stripes of one input read by worker threads on N devices (exg_rd_fanout.hpp)
 //   exg_rd_batch.cpp   open_next_file, next_batch: one device batch -> host vectors
 //   exg_reader.cpp     the C entry points (exg_open ... exg_close) and the chunk slicing
 #pragma once

@@ -8,6 +8,44 @@
 
 namespace exg_rd {
 
+uint64_t round_out_bytes(uint64_t target, uint64_t floor, bool capped, bool *forced) {
+    uint64_t out = std::max<uint64_t>(target, floor);
+    if (!capped && out >= (128ull << 20)) out = std::max<uint64_t>(out, 1ull << 30);
+    const char *e = getenv("EXG_STREAM_ROUND_OUT");
+    if (e) out = std::max<uint64_t>(floor, strtoull(e, nullptr, 10));
+    if (forced) *forced = e != nullptr;
+    return out;
+}
+
+int read_to_device(int device, int fd, uint64_t off, size_t n, char *dst, char *d_dst, hipStream_t st, const std::string &path, std::string *err) {
+    bool hip_failed = false;
+    if (pread_parallel(device, fd, off, n, dst, d_dst, st, &hip_failed)) return EXG_OK;
+    *err = hip_failed ? "hipMemcpyAsync failed" : "short read of '" + path + "'";
+    return hip_failed ? EXG_E_HIP : EXG_E_IO;
+}
+
+int push_empty_last(SegmentSink &sink, uint64_t d_pos, uint64_t reserve, hipStream_t stream, std::string *err) {
+    Segment seg;
+    seg.cap = (size_t)(reserve + 16 + 64);
+    seg.buf = sink.take(seg.cap);
+    if (!seg.buf) {
+        *err = "out of device memory";
+        return EXG_E_HIP;
+    }
+    seg.org = (int64_t)(d_pos & ~15ull) - (int64_t)reserve;
+    seg.lo = seg.start = seg.hi = d_pos;
+    seg.last = true;
+    hipError_t he = hipMemsetAsync((char *)seg.buf + reserve, 0, 16 + 64, stream);
+    if (he == hipSuccess) he = hipStreamSynchronize(stream);
+    if (he != hipSuccess) {
+        sink.give(seg.buf, seg.cap);
+        *err = std::string("hipMemsetAsync failed: ") + hipGetErrorString(he);
+        return EXG_E_HIP;
+    }
+    (void)sink.push(std::move(seg));
+    return EXG_OK;
+}
+
 bool SegmentSink::cancelled() const {
     std::lock_guard<std::mutex> g(src->mu_);
     return src->closed_;

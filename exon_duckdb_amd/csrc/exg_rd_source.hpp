@@ -159,6 +159,70 @@ private:
     std::mutex mirror_mu_;
 };
 
+// ---- what the producers share (exg_rd_gzip.cpp, exg_rd_zstd.cpp, exg_rd_bzip2.cpp)
+
+// inside a function that reports through `std::string *err` and an EXG_* code
+#define PRODUCER_HIP(expr)                                                                         \
+    do {                                                                                           \
+        hipError_t _e = (expr);                                                                    \
+        if (_e != hipSuccess) {                                                                    \
+            *err = std::string(#expr " failed: ") + hipGetErrorString(_e);                         \
+            return EXG_E_HIP;                                                                      \
+        }                                                                                          \
+    } while (0)
+
+// pinned host memory that grows on demand (to exactly what its caller asks for: slack is the caller's argument) and goes
+// back to its pool at the end
+struct PinBuf {
+    char *p = nullptr;
+    size_t cap = 0;
+    bool ensure(size_t n) {
+        if (n <= cap) return true;
+        release();
+        size_t want = n;
+        p = global_pool()->take(&want);
+        cap = p ? want : 0;
+        return p != nullptr;
+    }
+    void release() {
+        if (p) global_pool()->give(p, cap);
+        p = nullptr, cap = 0;
+    }
+    ~PinBuf() { release(); }
+};
+
+// a stream of stream_pool() for the life of its holder (it may hold none); giving it back synchronises it
+struct StreamLease {
+    int dev;
+    hipStream_t s = nullptr;
+    explicit StreamLease(int d, bool acquire_now = false) : dev(d) {
+        if (acquire_now) (void)acquire();
+    }
+    StreamLease(const StreamLease &) = delete;
+    StreamLease &operator=(const StreamLease &) = delete;
+    bool acquire() {
+        if (!s && stream_pool()->take(dev, &s) != hipSuccess) s = nullptr;
+        return s != nullptr;
+    }
+    void release() {
+        if (s) stream_pool()->give(dev, s);
+        s = nullptr;
+    }
+    operator hipStream_t() const { return s; }
+    ~StreamLease() { release(); }
+};
+
+// decoded bytes a round of a decoder aims at: `target` (a device batch; at least `floor`), without a memory cap ~1 GiB from
+// 128 MiB on — a round's kernels are dependent launches whose cost does not grow with it — and EXG_STREAM_ROUND_OUT over both
+// (*forced: that switch is set)
+uint64_t round_out_bytes(uint64_t target, uint64_t floor, bool capped, bool *forced = nullptr);
+// file bytes [off, off + n) of `path` -> pinned `dst`, each slice sent on to d_dst on `st` as soon as it is read (pread_parallel)
+int read_to_device(int device, int fd, uint64_t off, size_t n, char *dst, char *d_dst, hipStream_t st, const std::string &path, std::string *err);
+// the empty last segment a stream without output (or whose last round pushed none) still ends with: [reserve | 16 + 64 zero
+// bytes] at decoded offset d_pos, zeroed on `stream`
+int push_empty_last(SegmentSink &sink, uint64_t d_pos, uint64_t reserve, hipStream_t stream, std::string *err);
+inline std::string in_file(const std::string &path) { return " in '" + path + "'"; }
+
 // exg_rd_gzip.cpp: file bytes [c_begin, c_end) of fd are gzip members (BGZF or not, any mixture); `target` = decoded bytes per
 // segment.  bgzf_only: a member without the BGZF size field is an error (shards of a BGZF file).
 // reserve: bytes of room every segment leaves in front of its first byte (DecodedSource's `reserve`)

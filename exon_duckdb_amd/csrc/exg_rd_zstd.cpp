@@ -33,6 +33,24 @@ namespace zst = exg::zst;
 
 namespace {
 
+// The producer's environment switches, read once per stream (the tests set them inside one process; tools/README.md lists them
+// as the A/B partners of what they switch off)
+struct Switches {
+    bool no_readahead = getenv("EXG_ZSTD_NO_READAHEAD") != nullptr;
+    bool no_overlap = getenv("EXG_ZSTD_NO_OVERLAP") != nullptr;
+    bool no_index_overlap = getenv("EXG_ZSTD_NO_INDEX_OVERLAP") != nullptr;
+    // the file size from which a whole file begins on a prefix of its index (the tests' prefix-index cases: 0)
+    uint64_t index_overlap_min = getenv("EXG_ZSTD_INDEX_OVERLAP_MIN") ? strtoull(getenv("EXG_ZSTD_INDEX_OVERLAP_MIN"), nullptr, 10) : (256ull << 20);
+    uint64_t first_round_div = getenv("EXG_ZSTD_FIRST_ROUND_DIV") ? std::max<uint64_t>(1, strtoull(getenv("EXG_ZSTD_FIRST_ROUND_DIV"), nullptr, 10)) : 0;  // (0: not set)
+    // A frame inside one round is hashed on the device up to this size, one wavefront per frame at ~0.55 GB/s: the round waits
+    // for the slowest of them.  1 MiB = 2 ms of a ~30 ms round; frames of 8 MiB cost 78 ms per 4 GB and frames of 64 MiB 610 ms
+    // (5.4 instead of 30.9 GB/s) when this was the decoder's 64 MiB.  Larger frames go to the hasher threads behind the decoder.
+    uint64_t verify_max = getenv("EXG_ZSTD_VERIFY_MAX") ? zst::default_verify_max() : std::min<uint64_t>(zst::default_verify_max(), 1u << 20);
+    int hash_queue = getenv("EXG_ZSTD_HASH_QUEUE") ? std::max(1, atoi(getenv("EXG_ZSTD_HASH_QUEUE"))) : 0;      // (0: not set)
+    int hash_helpers = getenv("EXG_ZSTD_HASH_HELPERS") ? std::max(1, atoi(getenv("EXG_ZSTD_HASH_HELPERS"))) : 0;  // (0: not set)
+    bool trace = getenv("EXG_TRACE") != nullptr;
+};
+
 // The stage behind the decoder: XXH64 of the frames that span rounds (or are too large for the device's serial hash), then the
 // segment goes to the consumer — on a thread of its own, so that round n + 1 is decoded while round n's bytes come back
 // over PCIe (32 MiB pieces, two pinned buffers in turn, a stream of its own) and are hashed (~27 GB/s on a core of the GPU
@@ -50,11 +68,11 @@ public:
         Segment seg;
         std::vector<Part> parts;
     };
-    FrameHasher(int device, SegmentSink *sink, MemMeter *meter)
-        : device_(device), sink_(sink), meter_(meter),
+    FrameHasher(int device, SegmentSink *sink, MemMeter *meter, const Switches &sw)
+        : device_(device), sink_(sink), meter_(meter), helpers_max_(sw.hash_helpers ? (size_t)sw.hash_helpers : kHelpers), trace_(sw.trace),
           // segments that may wait behind the one being hashed: one (two or three measured nothing on a 4 GB checksummed frame —
           // 250 / 264 against 247 / 284 ms, inside the boxes' noise — and each is a segment of device memory)
-          depth_(getenv("EXG_ZSTD_HASH_QUEUE") && !(meter && meter->cap) ? std::max(1, atoi(getenv("EXG_ZSTD_HASH_QUEUE"))) : 1),
+          depth_(sw.hash_queue && !(meter && meter->cap) ? (size_t)sw.hash_queue : 1),
           thread_([this] { loop(); }) {}
     ~FrameHasher() {
         {
@@ -113,17 +131,16 @@ private:
                    hipEventRecord(ev[k & 1], st) == hipSuccess;
         };
         if (n_pieces && !issue(0)) return false;
-        static const bool trace = getenv("EXG_TRACE") != nullptr;
         double t_wait = 0, t_hash = 0;
         for (uint64_t k = 0; k < n_pieces; k++) {
-            const double t0 = trace ? now_s() : 0;
+            const double t0 = trace_ ? now_s() : 0;
             if (hipEventSynchronize(ev[k & 1]) != hipSuccess) return false;
             if (k + 1 < n_pieces && !issue(k + 1)) return false;
-            const double t1 = trace ? now_s() : 0;
+            const double t1 = trace_ ? now_s() : 0;
             h_.update((const uint8_t *)pin[k & 1], (size_t)std::min<uint64_t>(kPiece, part.len - k * kPiece));
-            if (trace) t_wait += t1 - t0, t_hash += now_s() - t1;
+            if (trace_) t_wait += t1 - t0, t_hash += now_s() - t1;
         }
-        if (trace && part.len >= (64u << 20))
+        if (trace_ && part.len >= (64u << 20))
             fprintf(stderr, "[exg] zstd hasher: %.1f MB of frame %u: %.1f ms waiting for the copies, %.1f ms hashing (%.1f GB/s)\n", part.len / 1e6, part.frame,
                     t_wait * 1e3, t_hash * 1e3, part.len / t_hash / 1e9);
         if (part.ends && (uint32_t)h_.digest() != part.expect) {
@@ -157,7 +174,7 @@ private:
         (void)hipSetDevice(device_);
         pin_to_device_node(device_);
         MeterScope meter_scope(meter_);
-        hipStream_t st = nullptr;
+        StreamLease st(device_);
         hipEvent_t ev[2] = {nullptr, nullptr};
         char *pin[2] = {nullptr, nullptr};
         size_t pin_cap[2] = {0, 0};
@@ -182,7 +199,7 @@ private:
             // reads it — otherwise the bytes come back through this stage's own two buffers, as before
             const bool from_mirror = !job.parts.empty() && sink_->mirror_now(job.seg, kPiece) && job.seg.mirror && job.seg.mirror->piece_bytes;
             if (!job.parts.empty() && !ready && !from_mirror) {
-                ok = stream_pool()->take(device_, &st) == hipSuccess;
+                ok = st.acquire();
                 for (int i = 0; i < 2 && ok; i++) {
                     ok = hipEventCreateWithFlags(&ev[i], hipEventDisableTiming) == hipSuccess;
                     pin_cap[i] = kPiece + 64;
@@ -202,14 +219,13 @@ private:
             std::atomic<bool> helpers_ok{true};
             std::atomic<uint32_t> bad_frame{~0u};
             if (ok && whole.size() >= 2) {
-                static const size_t helpers_max = getenv("EXG_ZSTD_HASH_HELPERS") ? std::max(1, atoi(getenv("EXG_ZSTD_HASH_HELPERS"))) : kHelpers;
-                const size_t nh = std::min<size_t>(helpers_max, whole.size());
+                const size_t nh = std::min<size_t>(helpers_max_, whole.size());
                 for (size_t t = 0; t < nh; t++)
                     helpers.emplace_back([&, this] {
                         (void)hipSetDevice(device_);
                         pin_to_device_node(device_);
                         MeterScope scope(meter_);
-                        hipStream_t hst = nullptr;
+                        StreamLease hst(device_);  // (goes back behind the pinned blocks, at the end of the helper)
                         hipEvent_t hev[2] = {nullptr, nullptr};
                         char *hpin[2] = {nullptr, nullptr};
                         size_t hcap[2] = {kPiece + 64, kPiece + 64};
@@ -224,7 +240,7 @@ private:
                                 }
                             return;
                         }
-                        bool up = stream_pool()->take(device_, &hst) == hipSuccess;
+                        bool up = hst.acquire();
                         for (int i = 0; i < 2 && up; i++)
                             up = hipEventCreateWithFlags(&hev[i], hipEventDisableTiming) == hipSuccess && (hpin[i] = global_pool()->take(&hcap[i])) != nullptr;
                         for (size_t k; up && (k = next.fetch_add(1)) < whole.size();)
@@ -234,7 +250,6 @@ private:
                             if (hpin[i]) global_pool()->give(hpin[i], hcap[i]);
                             if (hev[i]) (void)hipEventDestroy(hev[i]);
                         }
-                        if (hst) stream_pool()->give(device_, hst);
                     });
             }
             for (size_t i = 0; i < job.parts.size() && ok; i++) {
@@ -268,11 +283,12 @@ private:
             if (pin[i]) global_pool()->give(pin[i], pin_cap[i]);
             if (ev[i]) (void)hipEventDestroy(ev[i]);
         }
-        if (st) stream_pool()->give(device_, st);
     }
     int device_;
     SegmentSink *sink_;
     MemMeter *meter_;
+    size_t helpers_max_;
+    bool trace_;
     size_t depth_;
     exg::Xxh64 h_;
     std::mutex mu_;
@@ -283,69 +299,36 @@ private:
     std::thread thread_;
 };
 
-class ZstdProducer : public SegmentProducer {
-public:
-    ZstdProducer(exg_reader *r, int fd, uint64_t n, uint64_t c_begin, uint64_t c_end, uint64_t target, const std::string &path, uint64_t reserve,
-                 const uint64_t mark_at[2])
-        : device_(r->device), fd_(fd), n_(n), c_begin_(c_begin), c_end_(c_end), target_(std::max<uint64_t>(target, 128u << 10)), path_(path),
-          reserve_((reserve + 15) & ~15ull) {
-        if (mark_at) mark_at_[0] = mark_at[0], mark_at_[1] = mark_at[1];
-        // A round's kernels are dependent launches, each as long as its slowest block's chain (~10 ms whatever the size, until
-        // the chip is full): without a memory cap a round decodes ~1 GiB instead of one device batch (exg_rd_gzip.cpp does
-        // the same for the rounds of one big gzip member)
-        if (!r->mem_cap && target_ >= (128ull << 20)) target_ = std::max<uint64_t>(target_, 1ull << 30);
-        read_ahead_ = !r->mem_cap && !getenv("EXG_ZSTD_NO_READAHEAD");
-        if (const char *e = getenv("EXG_STREAM_ROUND_OUT")) target_ = std::max<uint64_t>(128u << 10, strtoull(e, nullptr, 10));
-    }
-    int run(SegmentSink &sink, std::string *err) override;
-
-private:
+// what make_zstd_producer is given
+struct ZstdInput {
     int device_, fd_;
     uint64_t n_, c_begin_, c_end_, target_;
-    uint64_t mark_at_[2] = {~0ull, ~0ull};  // frame offsets whose decoded positions the reader wants to know (a shard's boundaries)
+    uint64_t mark_at_[2];  // frame offsets whose decoded positions the reader wants to know (a shard's boundaries; ~0: none)
     std::string path_;
     uint64_t reserve_;
-    bool read_ahead_ = false;  // the next round's compressed bytes travel while this round is decoded (a second window: not under a cap)
+    bool capped_;
 };
 
-#define ZS_HIP(expr)                                                                               \
-    do {                                                                                           \
-        hipError_t _e = (expr);                                                                    \
-        if (_e != hipSuccess) {                                                                    \
-            *err = std::string(#expr " failed: ") + hipGetErrorString(_e);                         \
-            return EXG_E_HIP;                                                                      \
-        }                                                                                          \
-    } while (0)
+// One decode of the stream, front to back.  It lives on the stack of SegmentProducer::run and not in the SegmentProducer: the
+// reader keeps that one until the file is closed, and what a decode holds — streams, windows, pinned blocks, threads — goes back
+// when the stream has ended, on the producer's thread (whose meter the pools charge).
+class ZstdProducer : ZstdInput {
+public:
+    static constexpr int kConsumerGone = 1;  // beside EXG_OK and the EXG_E_* codes: the consumer closed the stream — nothing more is wanted
+    ZstdProducer(const ZstdInput &in, SegmentSink &sink, std::string *err)
+        : ZstdInput(in), sink_(sink), err_(err), run_trace_{now_s(), sw_.trace}, st_(device_, true), read_ahead_(!capped_ && !sw_.no_readahead),
+          st_io_(device_, read_ahead_), d_comp_{{device_, st_}, {device_, st_}, {device_, st_}}, d_hist_(device_, st_),
+          hasher_(device_, &sink, tl_meter(), sw_), st_b_(device_) {
+        target_ = round_out_bytes(target_, 128u << 10, capped_, &round_out_forced_);
+    }
+    int run();  // EXG_OK, kConsumerGone or an error code + *err
 
-int ZstdProducer::run(SegmentSink &sink, std::string *err) {
-    const double t_run0 = now_s();
+private:
     struct RunTrace {
         double t0;
-        ~RunTrace() { if (getenv("EXG_TRACE")) fprintf(stderr, "[exg] zstd producer: gone %.1f ms after it began\n", (now_s() - t0) * 1e3); }
-    } run_trace{t_run0};
-    // Round 6: a consumer that pulls string columns gets rounds of 640 MiB instead of 1 GiB.  Behind the ramp the decode and the link
-    // run at about the same rate (a 1 GiB round every ~23 ms, its bytes + vectors 22 ms of link), so the drain ends when the link
-    // has caught up with everything the decoder had ready before it: smaller rounds start the link earlier and leave a smaller last
-    // segment (4 GB: 160 + 320 + 5 x 640 + 135 MiB).  A 4 GB frame into DataChunks, three boxes, A/B inside each: 1 GiB rounds 133-138
-    // ms, 768 MiB 126-133, 640 MiB 125-129, 512 MiB 141 (the decode itself slows down: COUNT(*) 99 ms against 91; 640 MiB: 93.5).
-    // COUNT(*) keeps its 1 GiB rounds
-    if (target_ == (1ull << 30) && sink.mirror_wanted() && !getenv("EXG_STREAM_ROUND_OUT")) target_ = 640ull << 20;
-    hipStream_t st = nullptr;
-    if (stream_pool()->take(device_, &st) != hipSuccess) {
-        *err = "cannot create a stream for the zstd decoder";
-        return EXG_E_HIP;
-    }
-    struct StreamBack {
-        int dev;
-        hipStream_t s;
-        ~StreamBack() { stream_pool()->give(dev, s); }  // (synchronises it)
-    } stream_back{device_, st};
-    zst::Index idx;
-    const double t_idx0 = now_s();
-    // The walk over the frame / block headers reads the file with two small preads per block.  (It used to read a mapping of
-    // the whole file: a page fault per 64 KiB — 80-100 ms per 2 GB on this thread, 20 ms with eight threads taking the faults
-    // first — and 49 ms to unmap it again at the end, a quarter of what a 4 GB frame took end to end.)
-    std::string damage;  // a malformed or truncated stream: the rows in front of the damage first, like a streaming decoder
+        bool on;
+        ~RunTrace() { if (on) fprintf(stderr, "[exg] zstd producer: gone %.1f ms after it began\n", (now_s() - t0) * 1e3); }
+    };
     // Round 5: a whole big file begins its first round on a PREFIX of the index (the blocks of one round and two more: ~6 ms of a
     // 4 GB frame's 23) while a helper walks the whole file; the whole index takes the prefix's place behind the first round's
     // entropy stages (finish_index), before anything asks for a block behind the prefix.  EXG_ZSTD_NO_INDEX_OVERLAP: never (A/B).
@@ -356,35 +339,7 @@ int ZstdProducer::run(SegmentSink &sink, std::string *err) {
         ~Walker() {
             if (th.joinable()) th.join();
         }
-    } walker;
-    // the round's compressed bytes: [the blocks whose tables are repeated (at most four) | the round's own, from a 16-byte boundary]
-    static constexpr uint64_t kSideSlot = (zst::kBlockMax + 64 + 15) & ~15ull, kSide = 4 * kSideSlot;
-    // (three windows of compressed bytes in turn: while round n is decoded out of one — and round n - 1 still executes out of
-    // the one before — a helper thread reads round n + 1's bytes into the third and sends them on a stream of its own: 9 ms of a
-    // round otherwise spent in front of the decode)
-    hipStream_t st_io = nullptr;
-    if (read_ahead_ && stream_pool()->take(device_, &st_io) != hipSuccess) st_io = nullptr, read_ahead_ = false;
-    struct StreamBack2 {
-        int dev;
-        hipStream_t s;
-        ~StreamBack2() { if (s) stream_pool()->give(dev, s); }
-    } stream_back2{device_, st_io};
-    PoolBuf d_comp_a(device_, st), d_comp_b(device_, st), d_comp_c(device_, st), d_hist(device_, st);
-    PoolBuf *d_comps[3] = {&d_comp_a, &d_comp_b, &d_comp_c};
-    struct Pin {
-        char *p = nullptr;
-        size_t cap = 0;
-        ~Pin() { if (p) global_pool()->give(p, cap); }
-        bool ensure(size_t n) {
-            if (n <= cap) return true;
-            if (p) global_pool()->give(p, cap);
-            size_t want = n;
-            p = global_pool()->take(&want);
-            cap = p ? want : 0;
-            return p != nullptr;
-        }
-    } pins[3];
-    size_t d_comp_caps[3] = {0, 0, 0}, d_hist_cap = 4096;
+    };
     struct Ahead {  // the window a helper thread is filling (or has filled) for the round that begins with block `b0`
         std::thread th;
         uint64_t b0 = ~0ull;
@@ -394,7 +349,7 @@ int ZstdProducer::run(SegmentSink &sink, std::string *err) {
         hipEvent_t ev = nullptr;
         hipStream_t io = nullptr;  // the stream the helper's H2D slices were enqueued on (pread_parallel only enqueues them)
         // Whatever way run() is left — the consumer closed early (a LIMIT query), a cancelled sink, an error — a window may
-        // still be travelling: its pinned block and its device window are locals declared in front of this one, i.e. released
+        // still be travelling: its pinned block and its device window are members declared in front of this one, i.e. released
         // to the process-wide pools AFTER this destructor.  The copies have to be over by then, or another reader of the same
         // device takes a block that a DMA is still reading from / writing to (advisor, round 4).
         ~Ahead() {
@@ -402,172 +357,7 @@ int ZstdProducer::run(SegmentSink &sink, std::string *err) {
             if (io) (void)hipStreamSynchronize(io);
             if (ev) (void)hipEventDestroy(ev);
         }
-    } ahead;
-    ahead.io = st_io;
-    if (read_ahead_ && hipEventCreateWithFlags(&ahead.ev, hipEventDisableTiming) != hipSuccess) read_ahead_ = false;
-    auto ensure_window = [&](int slot, uint64_t comp_len) -> bool {
-        if (kSide + comp_len + 64 > d_comp_caps[slot]) {
-            d_comp_caps[slot] = (size_t)(kSide + comp_len + comp_len / 4 + 64);
-            if (!d_comps[slot]->take(d_comp_caps[slot])) return false;
-        }
-        return pins[slot].ensure((size_t)(kSide + comp_len + 64));
     };
-    // file bytes [lo, lo + len) -> window `slot` on the helper thread (pread + H2D on st_io), for the round that begins with block b0
-    auto launch_ahead = [&](uint64_t b0_of, uint64_t lo, uint64_t len, int slot) {
-        ahead.b0 = b0_of;
-        ahead.lo = lo, ahead.hi = lo + len;
-        ahead.slot = slot;
-        ahead.ok = ahead.hip_failed = false;
-        char *h_dst = pins[slot].p + kSide, *d_dst = (char *)d_comps[slot]->p + kSide;
-        ahead.th = std::thread([this, &ahead, lo, len, h_dst, d_dst, st_io] {
-            (void)hipSetDevice(device_);
-            bool hf = false;
-            bool ok = !len || pread_parallel(device_, fd_, lo, (size_t)len, h_dst, d_dst, st_io, &hf);
-            if (ok && hipMemsetAsync(d_dst + len, 0, 64, st_io) != hipSuccess) ok = false, hf = true;
-            if (ok && hipEventRecord(ahead.ev, st_io) != hipSuccess) ok = false, hf = true;
-            ahead.hip_failed = hf;
-            ahead.ok = ok;
-        });
-    };
-    static constexpr uint64_t kFirstRound = ~1ull;  // launch_ahead's b0 while the first block is not known yet
-    {
-        const bool no_index_overlap = getenv("EXG_ZSTD_NO_INDEX_OVERLAP") != nullptr;  // (read per stream: the tests set them inside one process)
-        const uint64_t overlap_min = getenv("EXG_ZSTD_INDEX_OVERLAP_MIN") ? strtoull(getenv("EXG_ZSTD_INDEX_OVERLAP_MIN"), nullptr, 10) : (256ull << 20);  // (tests: 0)
-        const bool whole_file = c_begin_ == 0 && c_end_ >= n_ && mark_at_[0] == ~0ull && mark_at_[1] == ~0ull;
-        bool have = false, ok = false;
-        if (whole_file && read_ahead_ && !no_index_overlap && n_ >= overlap_min) {
-            walker.th = std::thread([&walker, this] { walker.ok = zst::build_index_fd(fd_, n_, walker.full); });
-            // ... and the first round's compressed bytes begin to travel before any block is known: the file's first 0.75 x a round's
-            // output (a round of a stream that compresses 1.33-fold or better lies inside; the round checks, and reads again if not)
-            // (a first round that will be a quarter — plan(): the consumer pulls strings, or the first frame carries a checksum, which
-            // its descriptor byte says — wants a quarter of that: the round waits for the whole guess to land)
-            uint8_t head[5] = {0, 0, 0, 0, 0};
-            const bool head_ok = pread(fd_, head, 5, 0) == 5;
-            const bool first_has_checksum = head_ok && head[0] == 0x28 && head[1] == 0xB5 && head[2] == 0x2F && head[3] == 0xFD && ((head[4] >> 2) & 1);
-            const uint64_t div_env = getenv("EXG_ZSTD_FIRST_ROUND_DIV") ? std::max<uint64_t>(1, strtoull(getenv("EXG_ZSTD_FIRST_ROUND_DIV"), nullptr, 10)) : 0;
-            const uint64_t div = div_env ? div_env : (first_has_checksum || sink.mirror_wanted()) ? 4 : 1;
-            const uint64_t first_out = std::min<uint64_t>(target_, std::max<uint64_t>(target_ / div, 16u << 20));
-            const uint64_t guess = std::min<uint64_t>(n_, first_out / 2 + first_out / 4);
-            if (ensure_window(0, guess)) launch_ahead(kFirstRound, 0, guess, 0);
-            bool stopped = false;
-            if (zst::build_index_prefix_fd(fd_, n_, first_out + 2 * (uint64_t)zst::kBlockMax, idx, &stopped) && stopped) {
-                walker.pending = true;
-                have = ok = true;
-            } else {  // (the stream is shorter than a round, or its prefix is damaged: the whole walk says what it is)
-                walker.th.join();
-                idx = std::move(walker.full);
-                have = true;
-                ok = walker.ok;
-            }
-        }
-        if (!have) ok = zst::build_index_fd(fd_, n_, idx);
-        if (!ok) {
-            damage = idx.error + " in '" + path_ + "'";
-            if (!zst::salvage_index(idx)) {
-                *err = damage;
-                return EXG_E_PARSE;
-            }
-        }
-    }
-    if (getenv("EXG_TRACE"))
-        fprintf(stderr, "[exg] zstd producer: index of %.1f MB (%zu blocks%s) %.1f ms\n", n_ / 1e6, idx.blocks.size(), walker.pending ? ": a prefix, the rest on a helper" : "",
-                (now_s() - t_idx0) * 1e3);
-    // the frames whose first byte lies in [c_begin, c_end) (a shard decodes its own frames and a halo of frames in front)
-    uint64_t b_first = 0, n_blocks = 0, b_mark[2] = {~0ull, ~0ull};
-    bool marked[2] = {false, false};
-    auto scan_frames = [&] {
-        b_first = idx.blocks.size(), n_blocks = 0;
-        for (const zst::Frame &F : idx.frames) {
-            if (F.src_off >= c_begin_ && F.src_off < c_end_) {
-                b_first = std::min<uint64_t>(b_first, F.first_block);
-                n_blocks = std::max<uint64_t>(n_blocks, (uint64_t)F.first_block + F.n_blocks);
-            }
-            for (int i = 0; i < 2; i++)
-                if (mark_at_[i] != ~0ull && F.src_off >= mark_at_[i] && b_mark[i] == ~0ull) b_mark[i] = F.first_block;
-        }
-        if (b_first > n_blocks) b_first = n_blocks;
-    };
-    scan_frames();
-    if (ahead.b0 == kFirstRound) ahead.b0 = b_first;
-    // the whole index in the prefix's place (block and frame numbers are the same: both walks begin at byte 0)
-    auto finish_index = [&](uint64_t blocks_used) -> int {
-        if (!walker.pending) return EXG_OK;
-        walker.pending = false;
-        walker.th.join();
-        idx = std::move(walker.full);
-        if (!walker.ok) {
-            damage = idx.error + " in '" + path_ + "'";
-            if (!zst::salvage_index(idx)) {
-                *err = damage;
-                return EXG_E_PARSE;
-            }
-        }
-        if (idx.blocks.size() < blocks_used) {  // (the file changed between the two walks)
-            *err = damage.empty() ? "the zstd stream changed while it was read: '" + path_ + "'" : damage;
-            return EXG_E_PARSE;
-        }
-        scan_frames();
-        if (getenv("EXG_TRACE")) fprintf(stderr, "[exg] zstd producer: whole index (%zu blocks) there %.1f ms after the start\n", idx.blocks.size(), (now_s() - t_idx0) * 1e3);
-        return EXG_OK;
-    };
-    auto marks = [&](uint64_t b_next, uint64_t pos) {  // b_next: the next block to be decoded, pos: where its bytes will lie
-        for (int i = 0; i < 2; i++)
-            if (!marked[i] && mark_at_[i] != ~0ull && (b_next >= b_mark[i] || b_next >= n_blocks)) sink.set_mark(i, pos), marked[i] = true;
-    };
-    uint64_t ramp_second = ~0ull;  // the block the second round begins with (plan)
-    uint64_t first_div_used = 1;   // what the first round's size was divided by (plan)
-    // where a round that begins with block b ends, and which file bytes it needs
-    auto plan = [&](uint64_t from, uint64_t *to, uint64_t *lo, uint64_t *hi) {
-        // The first round is a quarter of the size (never more than a round, never below 16 MiB of one) when rounds overlap and
-        // the first frame carries a Content_Checksum: the host's XXH64, which hashes slower than the device decodes, begins after
-        // ~25 ms instead of ~60 (223-262 against 247-284 ms on a 4 GB frame; nothing without a checksum: 121-127 against 126 ms).
-        static const uint64_t first_div_env = getenv("EXG_ZSTD_FIRST_ROUND_DIV") ? std::max<uint64_t>(1, strtoull(getenv("EXG_ZSTD_FIRST_ROUND_DIV"), nullptr, 10)) : 0;
-        // (... and when the consumer pulls string columns: until the first segment is out nothing crosses the link, and behind it the
-        // drain is the link's — a 4 GB frame into DataChunks 161-165 -> 153-155 ms)
-        const uint64_t first_div =
-            first_div_env ? first_div_env : ((!idx.frames.empty() && idx.frames[idx.blocks[from].frame].has_checksum) || sink.mirror_wanted() ? 4 : 1);
-        // (and the second round half: a whole round behind the quarter left the hasher idle for ~14 ms of a 4 GB frame's time)
-        const uint64_t div = !read_ahead_ ? 1 : from == b_first ? first_div : from == ramp_second && first_div > 1 ? first_div / 2 : 1;
-        if (from == b_first) first_div_used = div;
-        const uint64_t want_out = std::min<uint64_t>(target_, std::max<uint64_t>(target_ / std::max<uint64_t>(div, 1), 16u << 20));
-        uint64_t b1 = from, est = 0;
-        while (b1 < n_blocks && (b1 == from || est < want_out)) {
-            if (b1 > from && (b1 == b_mark[0] || b1 == b_mark[1])) break;
-            const zst::Block &B = idx.blocks[b1];
-            est += B.type == 2 ? zst::kBlockMax : B.src_size;  // raw / RLE: src_size is the regenerated size
-            b1++;
-            if (b1 - from >= 0x7FFFFF00u) break;
-        }
-        if (from == b_first) ramp_second = b1;
-        *to = b1;
-        *lo = idx.blocks[from].src_off & ~15ull;
-        const zst::Block &BL = idx.blocks[b1 - 1];
-        *hi = std::min<uint64_t>(n_, BL.src_off + (BL.type == 1 ? 1 : BL.src_size));
-    };
-    int cur = 0;
-    if (!d_hist.take(d_hist_cap)) {
-        *err = "out of device memory";
-        return EXG_E_HIP;
-    }
-    FrameHasher hasher(device_, &sink, tl_meter());
-    // A frame inside one round is hashed on the device up to this size, one wavefront per frame at ~0.55 GB/s: the round waits
-    // for the slowest of them.  1 MiB = 2 ms of a ~30 ms round; frames of 8 MiB cost 78 ms per 4 GB and frames of 64 MiB 610 ms
-    // (5.4 instead of 30.9 GB/s) when this was the decoder's 64 MiB.  Larger frames go to the hasher threads behind the decoder.
-    const uint64_t verify_max = getenv("EXG_ZSTD_VERIFY_MAX") ? zst::default_verify_max() : std::min<uint64_t>(zst::default_verify_max(), 1u << 20);
-    uint64_t d_pos = 0;             // decoded bytes produced so far
-    uint64_t b0 = b_first;          // next block
-    uint32_t rep[3] = {1, 4, 8};    // repeat offsets behind block b0 - 1 (of the frame that goes on)
-    uint64_t frame_done = 0;        // bytes of the frame that holds block b0 decoded so far (0: it begins with b0)
-    uint64_t hist = 0, pad = 0;     // d_hist holds [pad | hist bytes]: the end of that frame's output so far
-    bool pushed_last = false;
-    // Two rounds overlap (not under a memory cap — the second window is what read_ahead_ stands for): while round n's ~1 900
-    // dependent resolve launches run (launch latency: the chip is mostly idle), round n + 1's entropy stages, its scan and the
-    // execution of its chunks run on the other stream.  Only round n + 1's resolve needs round n's last bytes (the window): it is
-    // enqueued once round n is done, and round n's segment goes out then.  What the next round needs of a round — sizes, repeat offsets —
-    // is known when its entropy stages are (decode_round_begin); what needs its bytes is deferred (InFlight::complete).
-    hipStream_t st_b = nullptr;
-    const bool overlap = read_ahead_ && !getenv("EXG_ZSTD_NO_OVERLAP") && stream_pool()->take(device_, &st_b) == hipSuccess;
-    StreamBack2 stream_back3{device_, overlap ? st_b : nullptr};
     struct InFlight {
         zst::Round R;
         zst::RoundCtx *ctx = nullptr;  // between begin and wait
@@ -576,7 +366,6 @@ int ZstdProducer::run(SegmentSink &sink, std::string *err) {
         bool last = false;
         // the window the round leaves (0: none — its last frame ends)
         uint64_t nh = 0, npad = 0, window = 0;
-        bool active = false;
         // the ~1 900 resolve launches of a round take this long to ISSUE (~5 us each: 10 ms): a thread of their own issues them,
         // so that the round behind begins meanwhile (its entropy stages and execution then run beside these launches on the chip)
         std::thread launcher;
@@ -586,258 +375,539 @@ int ZstdProducer::run(SegmentSink &sink, std::string *err) {
             if (launcher.joinable()) launcher.join();
             if (ctx) zst::decode_round_abandon(ctx);
         }
-    } fl[2];
-    int n_round = 0;
-    InFlight *prev = nullptr;
-    // round `F` is done on the device: its window into d_hist, its segment to the hasher / the consumer
-    auto complete = [&](InFlight &F) -> int {
-        F.active = false;
-        if (F.launcher.joinable()) F.launcher.join();
-        if (F.launch_rc) {  // (the launcher has disposed of the context)
-            *err = F.launch_err + " in '" + path_ + "'";
-            return F.launch_rc;
+    };
+    static constexpr uint64_t kSideSlot = zst::kSideSlot, kSide = zst::kSide;
+    static constexpr uint64_t kFirstRound = ~1ull;  // launch_ahead's b0 while the first block is not known yet
+
+    // ---- compressed windows
+    bool ensure_window(int slot, uint64_t comp_len);
+    void launch_ahead(uint64_t b0_of, uint64_t lo, uint64_t len, int slot);
+    int claim(uint64_t b0, uint64_t c_lo, uint64_t c_hi, hipStream_t st_r, bool *have);
+    // ---- index
+    int begin_index();
+    int index_damaged();
+    void scan_frames();
+    int finish_index(uint64_t blocks_used);
+    void marks(uint64_t b_next, uint64_t pos);
+    // ---- plan
+    void plan(uint64_t from, uint64_t *to, uint64_t *lo, uint64_t *hi);
+    void start_ahead(uint64_t b1, uint64_t comp_len, bool guess);
+    // ---- a round
+    int read_round(InFlight &F, const std::vector<uint64_t> &extra_ids, uint64_t c_lo, uint64_t comp_len, bool have);
+    int begin_round(InFlight &F, uint64_t c_lo);
+    std::string size_error(const zst::Round &R) const;
+    int stage(InFlight &F, int (*fn)(zst::Round &, zst::RoundCtx *));
+    int enqueue_resolve(InFlight &F);
+    void carry_over(InFlight &F, uint64_t b1);
+    int complete(InFlight &F);
+    int flush_prev();
+    int fail_behind_prev(int rc, const std::string &msg);
+
+    SegmentSink &sink_;
+    std::string *err_;
+    const Switches sw_{};
+    // DESTRUCTION ORDER.  Whatever way run() is left — at the stream's end, early because the consumer closed it, or with an
+    // error — the members from run_trace_ to fl_ go in reverse order of declaration: the rounds in flight (launchers joined,
+    // contexts abandoned), the second stream back, the hasher stopped, the read-ahead thread joined and its stream synchronised,
+    // the pinned blocks, d_hist_ and the windows back to the pools, the read-ahead stream back, the walker joined, the index
+    // gone, the first stream back.  What MUST hold of it (the pools are process-wide: what goes back is another reader's at once):
+    //   * fl_ in front of st_b_, d_hist_ and d_comp_: a launcher thread enqueues a round's resolve launches on st_ / st_b_, and
+    //     they read d_hist_ and a window;
+    //   * st_b_ in front of d_hist_ and d_comp_: a PoolBuf waits for st_ alone before its block goes back — the rounds on
+    //     st_b_ are over because giving the stream back has synchronised it;
+    //   * ahead_ in front of pins_, d_comp_ and st_io_: its thread reads into a pinned block and enqueues copies out of it
+    //     into a window on st_io_; ~Ahead joins it and waits for the copies;
+    //   * d_comp_ and d_hist_ in front of st_: they wait for it.
+    // Incidental: where hasher_ stands (its thread has streams and pinned blocks of its own and talks to sink_, which outlives
+    // the producer), pins_ against d_hist_ / d_comp_, walker_ against idx_ (its thread fills walker_.full and nothing else),
+    // run_trace_ (a line of trace), and everything behind fl_ (plain values).
+    RunTrace run_trace_;  // (first: its line comes when everything else has gone)
+    StreamLease st_;      // the first stream: rounds 0, 2, ... (every round without overlap), the windows' and d_hist_'s pool blocks
+    // The walk over the frame / block headers reads the file with two small preads per block.  (It used to read a mapping of
+    // the whole file: a page fault per 64 KiB — 80-100 ms per 2 GB on this thread, 20 ms with eight threads taking the faults
+    // first — and 49 ms to unmap it again at the end, a quarter of what a 4 GB frame took end to end.)
+    zst::Index idx_;
+    std::string damage_;  // a malformed or truncated stream: the rows in front of the damage first, like a streaming decoder
+    Walker walker_;
+    bool read_ahead_;  // the next round's compressed bytes travel while this round is decoded (a second window: not under a cap)
+    // (three windows of compressed bytes in turn: while round n is decoded out of one — and round n - 1 still executes out of
+    // the one before — a helper thread reads round n + 1's bytes into the third and sends them on a stream of its own: 9 ms of a
+    // round otherwise spent in front of the decode)
+    StreamLease st_io_;
+    PoolBuf d_comp_[3], d_hist_;  // the windows: [kSide of side slots | the round's own bytes]; d_hist_: [pad_ | hist_ bytes]
+    PinBuf pins_[3];
+    Ahead ahead_;
+    FrameHasher hasher_;
+    StreamLease st_b_;  // the second stream: rounds 1, 3, ... when rounds overlap
+    InFlight fl_[2];
+
+    bool round_out_forced_ = false;
+    double t_idx0_ = 0;
+    size_t d_comp_caps_[3] = {0, 0, 0}, d_hist_cap_ = 4096;
+    int cur_ = 0;  // the window of the round being assembled
+    // the frames whose first byte lies in [c_begin, c_end) (a shard decodes its own frames and a halo of frames in front)
+    uint64_t b_first_ = 0, n_blocks_ = 0, b_mark_[2] = {~0ull, ~0ull};
+    bool marked_[2] = {false, false};
+    uint64_t ramp_second_ = ~0ull;  // the block the second round begins with (plan)
+    uint64_t first_div_used_ = 1;   // what the first round's size was divided by (plan)
+    uint64_t d_pos_ = 0;            // decoded bytes produced so far
+    uint64_t b0_ = 0;               // next block
+    uint32_t rep_[3] = {1, 4, 8};   // repeat offsets behind block b0 - 1 (of the frame that goes on)
+    uint64_t frame_done_ = 0;       // bytes of the frame that holds block b0 decoded so far (0: it begins with b0)
+    uint64_t hist_ = 0, pad_ = 0;   // d_hist holds [pad | hist bytes]: the end of that frame's output so far
+    bool pushed_last_ = false;
+    bool overlap_ = false;
+    int n_round_ = 0;
+    InFlight *prev_ = nullptr;  // the round in flight
+};
+
+bool ZstdProducer::ensure_window(int slot, uint64_t comp_len) {
+    if (kSide + comp_len + 64 > d_comp_caps_[slot]) {
+        d_comp_caps_[slot] = (size_t)(kSide + comp_len + comp_len / 4 + 64);
+        if (!d_comp_[slot].take(d_comp_caps_[slot])) return false;
+    }
+    return pins_[slot].ensure((size_t)(kSide + comp_len + 64));
+}
+
+// file bytes [lo, lo + len) -> window `slot` on the helper thread (pread + H2D on st_io), for the round that begins with block b0
+void ZstdProducer::launch_ahead(uint64_t b0_of, uint64_t lo, uint64_t len, int slot) {
+    Ahead &ahead = ahead_;
+    ahead.b0 = b0_of;
+    ahead.lo = lo, ahead.hi = lo + len;
+    ahead.slot = slot;
+    ahead.ok = ahead.hip_failed = false;
+    char *h_dst = pins_[slot].p + kSide, *d_dst = (char *)d_comp_[slot].p + kSide;
+    const hipStream_t st_io = st_io_;
+    ahead.th = std::thread([this, &ahead, lo, len, h_dst, d_dst, st_io] {
+        (void)hipSetDevice(device_);
+        bool hf = false;
+        bool ok = !len || pread_parallel(device_, fd_, lo, (size_t)len, h_dst, d_dst, st_io, &hf);
+        if (ok && hipMemsetAsync(d_dst + len, 0, 64, st_io) != hipSuccess) ok = false, hf = true;
+        if (ok && hipEventRecord(ahead.ev, st_io) != hipSuccess) ok = false, hf = true;
+        ahead.hip_failed = hf;
+        ahead.ok = ok;
+    });
+}
+
+// the window the helper thread has filled for the round [b0 ...) of file bytes [c_lo, c_hi): the round's stream waits for it (*have), or it
+// is let land and dropped
+int ZstdProducer::claim(uint64_t b0, uint64_t c_lo, uint64_t c_hi, hipStream_t st_r, bool *have) {
+    std::string *err = err_;
+    Ahead &ahead = ahead_;
+    *have = false;
+    if (!ahead.th.joinable()) return EXG_OK;
+    ahead.th.join();
+    if (ahead.b0 == b0 && ahead.ok && ahead.lo == c_lo && ahead.hi >= c_hi) {
+        cur_ = ahead.slot;
+        PRODUCER_HIP(hipStreamWaitEvent(st_r, ahead.ev, 0));
+        *have = true;
+    } else if (ahead.hip_failed) {
+        *err = "hipMemcpyAsync failed";
+        return EXG_E_HIP;
+    } else {
+        (void)hipStreamSynchronize(st_io_);  // (a window nobody wants: let it land before its buffers are used again)
+    }
+    ahead.b0 = ~0ull;
+    return EXG_OK;
+}
+
+// the index is damaged: what lies in front of the damage is decoded first (damage_ is reported behind its rows), if anything does
+int ZstdProducer::index_damaged() {
+    damage_ = idx_.error + in_file(path_);
+    if (zst::salvage_index(idx_)) return EXG_OK;
+    *err_ = damage_;
+    return EXG_E_PARSE;
+}
+
+int ZstdProducer::begin_index() {
+    t_idx0_ = now_s();
+    const bool whole_file = c_begin_ == 0 && c_end_ >= n_ && mark_at_[0] == ~0ull && mark_at_[1] == ~0ull;
+    bool have = false, ok = false;
+    if (whole_file && read_ahead_ && !sw_.no_index_overlap && n_ >= sw_.index_overlap_min) {
+        walker_.th = std::thread([this] { walker_.ok = zst::build_index_fd(fd_, n_, walker_.full); });
+        // ... and the first round's compressed bytes begin to travel before any block is known: the file's first 0.75 x a round's
+        // output (a round of a stream that compresses 1.33-fold or better lies inside; the round checks, and reads again if not)
+        // (a first round that will be a quarter — plan(): the consumer pulls strings, or the first frame carries a checksum, which
+        // its descriptor byte says — wants a quarter of that: the round waits for the whole guess to land)
+        uint8_t head[5] = {0, 0, 0, 0, 0};
+        const bool head_ok = pread(fd_, head, 5, 0) == 5;
+        const bool first_has_checksum = head_ok && head[0] == 0x28 && head[1] == 0xB5 && head[2] == 0x2F && head[3] == 0xFD && ((head[4] >> 2) & 1);
+        const uint64_t div = sw_.first_round_div ? sw_.first_round_div : (first_has_checksum || sink_.mirror_wanted()) ? 4 : 1;
+        const uint64_t first_out = std::min<uint64_t>(target_, std::max<uint64_t>(target_ / div, 16u << 20));
+        const uint64_t guess = std::min<uint64_t>(n_, first_out / 2 + first_out / 4);
+        if (ensure_window(0, guess)) launch_ahead(kFirstRound, 0, guess, 0);
+        bool stopped = false;
+        if (zst::build_index_prefix_fd(fd_, n_, first_out + 2 * (uint64_t)zst::kBlockMax, idx_, &stopped) && stopped) {
+            walker_.pending = true;
+            have = ok = true;
+        } else {  // (the stream is shorter than a round, or its prefix is damaged: the whole walk says what it is)
+            walker_.th.join();
+            idx_ = std::move(walker_.full);
+            have = true;
+            ok = walker_.ok;
         }
-        zst::RoundCtx *ctx = F.ctx;
-        F.ctx = nullptr;
-        int rc;
-        {
-            TraceRange range("exg: zstd round (wait)");
-            rc = zst::decode_round_wait(F.R, ctx);
+    }
+    if (!have) ok = zst::build_index_fd(fd_, n_, idx_);
+    if (!ok)
+        if (int rc = index_damaged()) return rc;
+    if (sw_.trace)
+        fprintf(stderr, "[exg] zstd producer: index of %.1f MB (%zu blocks%s) %.1f ms\n", n_ / 1e6, idx_.blocks.size(), walker_.pending ? ": a prefix, the rest on a helper" : "",
+                (now_s() - t_idx0_) * 1e3);
+    scan_frames();
+    if (ahead_.b0 == kFirstRound) ahead_.b0 = b_first_;
+    b0_ = b_first_;
+    return EXG_OK;
+}
+
+void ZstdProducer::scan_frames() {
+    b_first_ = idx_.blocks.size(), n_blocks_ = 0;
+    for (const zst::Frame &F : idx_.frames) {
+        if (F.src_off >= c_begin_ && F.src_off < c_end_) {
+            b_first_ = std::min<uint64_t>(b_first_, F.first_block);
+            n_blocks_ = std::max<uint64_t>(n_blocks_, (uint64_t)F.first_block + F.n_blocks);
         }
-        if (rc) {
-            *err = std::string(exg_last_error_message()) + " in '" + path_ + "'";
-            return rc;
+        for (int i = 0; i < 2; i++)
+            if (mark_at_[i] != ~0ull && F.src_off >= mark_at_[i] && b_mark_[i] == ~0ull) b_mark_[i] = F.first_block;
+    }
+    if (b_first_ > n_blocks_) b_first_ = n_blocks_;
+}
+
+// the whole index in the prefix's place (block and frame numbers are the same: both walks begin at byte 0)
+int ZstdProducer::finish_index(uint64_t blocks_used) {
+    if (!walker_.pending) return EXG_OK;
+    walker_.pending = false;
+    walker_.th.join();
+    idx_ = std::move(walker_.full);
+    if (!walker_.ok)
+        if (int rc = index_damaged()) return rc;
+    if (idx_.blocks.size() < blocks_used) {  // (the file changed between the two walks)
+        *err_ = damage_.empty() ? "the zstd stream changed while it was read: '" + path_ + "'" : damage_;
+        return EXG_E_PARSE;
+    }
+    scan_frames();
+    if (sw_.trace) fprintf(stderr, "[exg] zstd producer: whole index (%zu blocks) there %.1f ms after the start\n", idx_.blocks.size(), (now_s() - t_idx0_) * 1e3);
+    return EXG_OK;
+}
+
+void ZstdProducer::marks(uint64_t b_next, uint64_t pos) {  // b_next: the next block to be decoded, pos: where its bytes will lie
+    for (int i = 0; i < 2; i++)
+        if (!marked_[i] && mark_at_[i] != ~0ull && (b_next >= b_mark_[i] || b_next >= n_blocks_)) sink_.set_mark(i, pos), marked_[i] = true;
+}
+
+// where a round that begins with block b ends, and which file bytes it needs
+void ZstdProducer::plan(uint64_t from, uint64_t *to, uint64_t *lo, uint64_t *hi) {
+    // The first round is a quarter of the size (never more than a round, never below 16 MiB of one) when rounds overlap and
+    // the first frame carries a Content_Checksum: the host's XXH64, which hashes slower than the device decodes, begins after
+    // ~25 ms instead of ~60 (223-262 against 247-284 ms on a 4 GB frame; nothing without a checksum: 121-127 against 126 ms).
+    // (... and when the consumer pulls string columns: until the first segment is out nothing crosses the link, and behind it the
+    // drain is the link's — a 4 GB frame into DataChunks 161-165 -> 153-155 ms)
+    const uint64_t first_div = sw_.first_round_div
+                                   ? sw_.first_round_div
+                                   : ((!idx_.frames.empty() && idx_.frames[idx_.blocks[from].frame].has_checksum) || sink_.mirror_wanted() ? 4 : 1);
+    // (and the second round half: a whole round behind the quarter left the hasher idle for ~14 ms of a 4 GB frame's time)
+    const uint64_t div = !read_ahead_ ? 1 : from == b_first_ ? first_div : from == ramp_second_ && first_div > 1 ? first_div / 2 : 1;
+    if (from == b_first_) first_div_used_ = div;
+    const uint64_t want_out = std::min<uint64_t>(target_, std::max<uint64_t>(target_ / std::max<uint64_t>(div, 1), 16u << 20));
+    uint64_t b1 = from, est = 0;
+    while (b1 < n_blocks_ && (b1 == from || est < want_out)) {
+        if (b1 > from && (b1 == b_mark_[0] || b1 == b_mark_[1])) break;
+        const zst::Block &B = idx_.blocks[b1];
+        est += B.type == 2 ? zst::kBlockMax : B.src_size;  // raw / RLE: src_size is the regenerated size
+        b1++;
+        if (b1 - from >= 0x7FFFFF00u) break;
+    }
+    if (from == b_first_) ramp_second_ = b1;
+    *to = b1;
+    *lo = idx_.blocks[from].src_off & ~15ull;
+    const zst::Block &BL = idx_.blocks[b1 - 1];
+    *hi = std::min<uint64_t>(n_, BL.src_off + (BL.type == 1 ? 1 : BL.src_size));
+}
+
+// the round behind this one (it begins with block b1; this one has comp_len compressed bytes): its bytes begin to travel now, into
+// the next window (three in turn: the round in flight reads the one before this round's)
+void ZstdProducer::start_ahead(uint64_t b1, uint64_t comp_len, bool guess) {
+    if (!(read_ahead_ && b1 < n_blocks_)) return;
+    uint64_t nb1 = 0, nlo = 0, nhi = 0;
+    if (guess) {
+        // the index is still a prefix: the round behind this one begins with block b1 (in the prefix) and, with as many
+        // blocks, is about as long as this one (twice, behind a quarter) — 5 % more of the file travel; a window that turns out short is read again
+        nlo = idx_.blocks[b1].src_off & ~15ull;
+        // (behind a first round of a quarter comes one of a half)
+        const uint64_t like = first_div_used_ > 1 ? 2 * comp_len : comp_len;
+        nhi = std::min<uint64_t>(n_, nlo + like + like / 20 + (1u << 20));
+    } else {
+        plan(b1, &nb1, &nlo, &nhi);
+    }
+    const int other = (cur_ + 1) % 3;
+    if (ensure_window(other, nhi - nlo)) launch_ahead(b1, nlo, nhi - nlo, other);
+}
+
+// round F's compressed bytes on their way into window cur_: the blocks whose tables are repeated into the side slots (small
+// reads of this thread's), its own comp_len bytes from c_lo on unless the helper has brought them (have)
+int ZstdProducer::read_round(InFlight &F, const std::vector<uint64_t> &extra_ids, uint64_t c_lo, uint64_t comp_len, bool have) {
+    std::string *err = err_;
+    PoolBuf &d_comp = d_comp_[cur_];
+    PinBuf &pin = pins_[cur_];
+    const uint32_t nx = F.R.n_extra;
+    const hipStream_t st_r = F.st;
+    for (uint32_t i = 0; i < nx; i++) {
+        const zst::Block &E = idx_.blocks[extra_ids[i]];
+        const uint64_t sz = E.type == 2 ? E.src_size : 1;
+        if (!zst::pread_all(fd_, pin.p + i * kSideSlot, (size_t)std::min<uint64_t>(sz, kSideSlot), E.src_off)) {
+            *err = "short read of '" + path_ + "'";
+            return EXG_E_IO;
         }
-        zst::Round &R = F.R;
-        const uint64_t H = R.history;  // pad + hist
-        Segment seg;
-        seg.buf = R.d_buf;
-        seg.cap = R.alloc;
-        seg.org = (int64_t)F.d_pos - (int64_t)H - (int64_t)reserve_;
-        seg.lo = F.d_pos - F.hist;
-        seg.start = F.d_pos;
-        seg.hi = F.d_pos + R.produced;
-        seg.last = F.last;
-        const uint8_t *content = (const uint8_t *)R.d_buf + reserve_;  // buffer coordinate 0
-        FrameHasher::Job job;
-        for (const zst::RoundFrame &rf : R.frames) {
-            const zst::Frame &Fr = idx.frames[rf.frame_id];
-            if (Fr.has_checksum && !rf.verified) {
-                // its bytes come back in pieces and are hashed beside the next round's decode (FrameHasher), before the segment goes out
-                FrameHasher::Part part;
-                part.d_src = content + rf.out_off;
-                part.len = rf.out_size;
-                part.frame = rf.frame_id;
-                part.expect = Fr.checksum;
-                part.begins = rf.begins;
-                part.ends = rf.ends;
-                job.parts.push_back(part);
-            }
+    }
+    if (nx) PRODUCER_HIP(hipMemcpyAsync(d_comp.p, pin.p, nx * kSideSlot, hipMemcpyHostToDevice, st_r));
+    if (have || !comp_len) return EXG_OK;
+    return read_to_device(device_, fd_, c_lo, (size_t)comp_len, pin.p + kSide, (char *)d_comp.p + kSide, st_r, path_, err);
+}
+
+// an error of round n + 1 is reported behind round n's rows: round n goes out first
+int ZstdProducer::fail_behind_prev(int rc, const std::string &msg) {
+    if (int rp = flush_prev()) return rp;
+    *err_ = msg;
+    return rc;
+}
+
+// the round's entropy stages (decode_round_begin: sizes and repeat offsets are known behind them)
+int ZstdProducer::begin_round(InFlight &F, uint64_t c_lo) {
+    zst::Round &R = F.R;
+    R.rep_in[0] = rep_[0], R.rep_in[1] = rep_[1], R.rep_in[2] = rep_[2];
+    R.d_comp = d_comp_[cur_].p;
+    R.d_history = nullptr;  // (set when the round in front is done: d_hist may move)
+    // the first history byte is stream byte d_pos - hist: `pad` (unused) bytes in front of it put it on the 16-byte grid the
+    // decoder's stores and the scan's loads follow (buffer coordinate 0 is 16-byte aligned, and an address must be
+    // congruent to its stream offset: pad = (d_pos - hist) & 15, also when nothing is kept)
+    R.history = pad_ + hist_;
+    R.front_reserve = reserve_;
+    R.verify_max = sw_.verify_max;
+    R.first_block_id = b0_;
+    R.comp_base = c_lo - kSide;
+    F.d_pos = d_pos_;
+    F.hist = hist_;
+    int rc;
+    {
+        TraceRange range("exg: zstd round (entropy stages)");
+        rc = zst::decode_round_begin(R, F.st, &F.ctx);
+    }
+    return rc ? fail_behind_prev(rc, std::string(exg_last_error_message()) + in_file(path_)) : EXG_OK;
+}
+
+// a frame that ends in the round and states its size regenerates that size (with what earlier rounds decoded of it); "": all do
+std::string ZstdProducer::size_error(const zst::Round &R) const {
+    for (const zst::RoundFrame &rf : R.frames) {
+        const zst::Frame &Fr = idx_.frames[rf.frame_id];
+        const uint64_t before = rf.begins ? 0 : frame_done_;
+        if (rf.ends && Fr.content_size != ~0ull && Fr.content_size != before + rf.out_size)
+            return "Data corruption detected (zstd frame " + std::to_string(rf.frame_id) + " regenerates " + std::to_string(before + rf.out_size) +
+                   " bytes, its header says " + std::to_string(Fr.content_size) + ")" + in_file(path_);
+    }
+    return std::string();
+}
+
+// one of decode_round_*'s later stages: a stage that fails has disposed of the context
+int ZstdProducer::stage(InFlight &F, int (*fn)(zst::Round &, zst::RoundCtx *)) {
+    zst::RoundCtx *ctx = F.ctx;
+    F.ctx = nullptr;
+    const int rc = fn(F.R, ctx);
+    if (!rc) F.ctx = ctx;
+    return rc;
+}
+
+// the round's resolve launches (they need the round in front's last bytes: d_hist_ is final) — with overlap on a thread of their own
+int ZstdProducer::enqueue_resolve(InFlight &F) {
+    F.R.d_history = d_hist_.p;
+    F.launch_rc = 0;
+    if (overlap_) {
+        MemMeter *const meter = tl_meter();
+        F.launcher = std::thread([this, &F, meter] {
+            (void)hipSetDevice(device_);
+            MeterScope scope(meter);
+            TraceRange range("exg: zstd round (resolve enqueued)");
+            F.launch_rc = stage(F, zst::decode_round_enqueue_resolve);
+            if (F.launch_rc) F.launch_err = exg_last_error_message();
+        });
+        return EXG_OK;
+    }
+    TraceRange range("exg: zstd round (resolve enqueued)");
+    const int rc = stage(F, zst::decode_round_enqueue_resolve);
+    if (rc) *err_ = std::string(exg_last_error_message()) + in_file(path_);
+    return rc;
+}
+
+// what the next round needs of this one: the repeat offsets, how much of the frame that goes on is done, its window (F.nh bytes
+// behind F.npad: complete() copies them into d_hist_ once the round's bytes are there)
+void ZstdProducer::carry_over(InFlight &F, uint64_t b1) {
+    const zst::Round &R = F.R;
+    const zst::RoundFrame &lastf = R.frames.back();
+    const uint64_t last_before = lastf.begins ? 0 : frame_done_;
+    F.nh = F.npad = F.window = 0;
+    if (lastf.ends) {
+        frame_done_ = 0, hist_ = 0, pad_ = (d_pos_ + R.produced) & 15;
+        rep_[0] = 1, rep_[1] = 4, rep_[2] = 8;
+    } else {
+        frame_done_ = last_before + lastf.out_size;
+        rep_[0] = R.rep_out[0], rep_[1] = R.rep_out[1], rep_[2] = R.rep_out[2];
+        const uint64_t window = idx_.frames[lastf.frame_id].window;
+        const uint64_t nh = std::min<uint64_t>(std::max<uint64_t>(window, 1), frame_done_);
+        const uint64_t end_pos = d_pos_ + R.produced;  // stream offset behind this round
+        F.nh = nh, F.npad = (end_pos - nh) & 15, F.window = window;
+        hist_ = nh, pad_ = F.npad;
+    }
+    d_pos_ += R.produced;
+    b0_ = b1;
+    F.last = b0_ >= n_blocks_;
+}
+
+// round `F` is done on the device: its window into d_hist, its segment to the hasher / the consumer
+int ZstdProducer::complete(InFlight &F) {
+    std::string *err = err_;
+    if (F.launcher.joinable()) F.launcher.join();
+    if (F.launch_rc) {  // (the launcher has disposed of the context)
+        *err = F.launch_err + in_file(path_);
+        return F.launch_rc;
+    }
+    zst::RoundCtx *ctx = F.ctx;
+    F.ctx = nullptr;
+    int rc;
+    {
+        TraceRange range("exg: zstd round (wait)");
+        rc = zst::decode_round_wait(F.R, ctx);
+    }
+    if (rc) {
+        *err = std::string(exg_last_error_message()) + in_file(path_);
+        return rc;
+    }
+    zst::Round &R = F.R;
+    const uint64_t H = R.history;  // pad + hist
+    Segment seg;
+    seg.buf = R.d_buf;
+    seg.cap = R.alloc;
+    seg.org = (int64_t)F.d_pos - (int64_t)H - (int64_t)reserve_;
+    seg.lo = F.d_pos - F.hist;
+    seg.start = F.d_pos;
+    seg.hi = F.d_pos + R.produced;
+    seg.last = F.last;
+    const uint8_t *content = (const uint8_t *)R.d_buf + reserve_;  // buffer coordinate 0
+    FrameHasher::Job job;
+    for (const zst::RoundFrame &rf : R.frames) {
+        const zst::Frame &Fr = idx_.frames[rf.frame_id];
+        if (Fr.has_checksum && !rf.verified) {
+            // its bytes come back in pieces and are hashed beside the next round's decode (FrameHasher), before the segment goes out
+            FrameHasher::Part part;
+            part.d_src = content + rf.out_off;
+            part.len = rf.out_size;
+            part.frame = rf.frame_id;
+            part.expect = Fr.checksum;
+            part.begins = rf.begins;
+            part.ends = rf.ends;
+            job.parts.push_back(part);
         }
-        if (F.nh) {
-            if (F.npad + F.nh > d_hist_cap) {
-                // (the old window's bytes are in this round's buffer too: a new block loses nothing)
-                d_hist_cap = (size_t)(F.npad + std::max<uint64_t>(F.nh, std::min<uint64_t>(F.window, zst::kWindowMax)) + 64);
-                if (!d_hist.take(d_hist_cap)) {
-                    sink.give(seg.buf, seg.cap);
-                    *err = "out of device memory for the window of a zstd frame";
-                    return EXG_E_HIP;
-                }
-            }
-            // the last nh bytes of [history | produced] (nh <= history of this frame + what the round added to it)
-            const uint8_t *src = content + H + R.produced - F.nh;
-            hipError_t he = hipMemcpyAsync((char *)d_hist.p + F.npad, src, F.nh, hipMemcpyDeviceToDevice, F.st);
-            if (he == hipSuccess) he = hipStreamSynchronize(F.st);
-            if (he != hipSuccess) {
-                sink.give(seg.buf, seg.cap);
-                *err = std::string("keeping the window of a zstd frame failed: ") + hipGetErrorString(he);
+    }
+    if (F.nh) {
+        if (F.npad + F.nh > d_hist_cap_) {
+            // (the old window's bytes are in this round's buffer too: a new block loses nothing)
+            d_hist_cap_ = (size_t)(F.npad + std::max<uint64_t>(F.nh, std::min<uint64_t>(F.window, zst::kWindowMax)) + 64);
+            if (!d_hist_.take(d_hist_cap_)) {
+                sink_.give(seg.buf, seg.cap);
+                *err = "out of device memory for the window of a zstd frame";
                 return EXG_E_HIP;
             }
         }
-        pushed_last = seg.last;
-        job.seg = std::move(seg);
-        seg.buf = nullptr;
-        if (!hasher.submit(std::move(job))) {
-            if (hasher.gone()) return -1;  // the consumer closed the stream
-            *err = hasher.error() + " in '" + path_ + "'";
-            return EXG_E_PARSE;
+        // the last nh bytes of [history | produced] (nh <= history of this frame + what the round added to it)
+        const uint8_t *src = content + H + R.produced - F.nh;
+        hipError_t he = hipMemcpyAsync((char *)d_hist_.p + F.npad, src, F.nh, hipMemcpyDeviceToDevice, F.st);
+        if (he == hipSuccess) he = hipStreamSynchronize(F.st);
+        if (he != hipSuccess) {
+            sink_.give(seg.buf, seg.cap);
+            *err = std::string("keeping the window of a zstd frame failed: ") + hipGetErrorString(he);
+            return EXG_E_HIP;
         }
-        return EXG_OK;
-    };
-    // (an error of round n + 1 is reported behind round n's rows: round n goes out first)
-    auto flush_prev = [&]() -> int {
-        if (!prev) return EXG_OK;
-        InFlight *f = prev;
-        prev = nullptr;
-        return complete(*f);
-    };
-    while (b0 < n_blocks && !sink.cancelled()) {
-        marks(b0, d_pos);
-        InFlight &F = fl[n_round & 1];
-        hipStream_t st_r = overlap && (n_round & 1) ? st_b : st;
-        n_round++;
+    }
+    pushed_last_ = seg.last;
+    job.seg = std::move(seg);
+    if (!hasher_.submit(std::move(job))) {
+        if (hasher_.gone()) return kConsumerGone;
+        *err = hasher_.error() + in_file(path_);
+        return EXG_E_PARSE;
+    }
+    return EXG_OK;
+}
+
+int ZstdProducer::flush_prev() {
+    if (!prev_) return EXG_OK;
+    InFlight *f = prev_;
+    prev_ = nullptr;
+    return complete(*f);
+}
+
+int ZstdProducer::run() {
+    std::string *err = err_;
+    // Round 6: a consumer that pulls string columns gets rounds of 640 MiB instead of 1 GiB.  Behind the ramp the decode and the link
+    // run at about the same rate (a 1 GiB round every ~23 ms, its bytes + vectors 22 ms of link), so the drain ends when the link
+    // has caught up with everything the decoder had ready before it: smaller rounds start the link earlier and leave a smaller last
+    // segment (4 GB: 160 + 320 + 5 x 640 + 135 MiB).  A 4 GB frame into DataChunks, three boxes, A/B inside each: 1 GiB rounds 133-138
+    // ms, 768 MiB 126-133, 640 MiB 125-129, 512 MiB 141 (the decode itself slows down: COUNT(*) 99 ms against 91; 640 MiB: 93.5).
+    // COUNT(*) keeps its 1 GiB rounds
+    if (target_ == (1ull << 30) && sink_.mirror_wanted() && !round_out_forced_) target_ = 640ull << 20;
+    if (!st_) {
+        *err = "cannot create a stream for the zstd decoder";
+        return EXG_E_HIP;
+    }
+    if (read_ahead_ && !st_io_) read_ahead_ = false;
+    ahead_.io = st_io_;
+    if (read_ahead_ && hipEventCreateWithFlags(&ahead_.ev, hipEventDisableTiming) != hipSuccess) read_ahead_ = false;
+    if (int rc = begin_index()) return rc;
+    if (!d_hist_.take(d_hist_cap_)) {
+        *err = "out of device memory";
+        return EXG_E_HIP;
+    }
+    // Two rounds overlap (not under a memory cap — the second window is what read_ahead_ stands for): while round n's ~1 900
+    // dependent resolve launches run (launch latency: the chip is mostly idle), round n + 1's entropy stages, its scan and the
+    // execution of its chunks run on the other stream.  Only round n + 1's resolve needs round n's last bytes (the window): it is
+    // enqueued once round n is done, and round n's segment goes out then.  What the next round needs of a round — sizes, repeat offsets —
+    // is known when its entropy stages are (decode_round_begin); what needs its bytes is deferred (complete).
+    overlap_ = read_ahead_ && !sw_.no_overlap && st_b_.acquire();
+    while (b0_ < n_blocks_ && !sink_.cancelled()) {
+        marks(b0_, d_pos_);
+        InFlight &F = fl_[n_round_ & 1];
+        const hipStream_t st_r = overlap_ && (n_round_ & 1) ? st_b_ : st_;
+        F.st = st_r;
+        n_round_++;
         // ---- the round's blocks: about one segment of output (a block regenerates at most 128 KiB); a round ends at a mark
-        uint64_t b1 = b0, c_lo = 0, c_hi = 0;
-        plan(b0, &b1, &c_lo, &c_hi);
-        F.R = zst::Round();
-        zst::Round &R = F.R;
-        // blocks in front of the round whose tables its blocks repeat
+        uint64_t b1 = b0_, c_lo = 0, c_hi = 0;
+        plan(b0_, &b1, &c_lo, &c_hi);
+        const uint64_t comp_len = c_hi - c_lo;
+        // its block and frame lists, with the blocks in front of it whose tables its blocks repeat (while the helper may still be reading)
         std::vector<uint64_t> extra_ids;
-        auto local_of = [&](uint32_t g) -> uint32_t {
-            if (g == zst::kNone) return zst::kNone;
-            if (g >= b0) return (uint32_t)(g - b0) + (uint32_t)extra_ids.size();  // (patched below once the extras are known)
-            for (size_t i = 0; i < extra_ids.size(); i++)
-                if (extra_ids[i] == g) return (uint32_t)i;
-            extra_ids.push_back(g);
-            return (uint32_t)extra_ids.size() - 1;
-        };
-        for (uint64_t b = b0; b < b1; b++) {  // first pass: which sources
-            const zst::Block &B = idx.blocks[b];
-            if (B.type != 2) continue;
-            if (B.huf_src != zst::kNone && B.huf_src < b0) (void)local_of(B.huf_src);
-            for (int t = 0; t < 3; t++)
-                if (B.nseq && B.tbl_src[t] != zst::kNone && B.tbl_src[t] < b0) (void)local_of(B.tbl_src[t]);
-        }
-        const uint32_t nx = (uint32_t)extra_ids.size();
-        if (nx > 4) {
+        F.R = zst::Round();
+        if (!zst::assemble_round(idx_, b0_, b1, c_lo, hist_, F.R, &extra_ids)) {
             *err = "internal: a zstd round repeats the tables of more than four earlier blocks";
             return EXG_E_INVALID_ARG;
         }
-        const uint64_t comp_len = c_hi - c_lo;
         // this round's window: the one the helper thread has filled, or a read of its own
         bool have = false;
         const double t_join0 = now_s();
-        if (ahead.th.joinable()) {
-            ahead.th.join();
-            if (ahead.b0 == b0 && ahead.ok && ahead.lo == c_lo && ahead.hi >= c_hi) {
-                cur = ahead.slot;
-                ZS_HIP(hipStreamWaitEvent(st_r, ahead.ev, 0));
-                have = true;
-            } else if (ahead.hip_failed) {
-                *err = "hipMemcpyAsync failed";
-                return EXG_E_HIP;
-            } else {
-                (void)hipStreamSynchronize(st_io);  // (a window nobody wants: let it land before its buffers are used again)
-            }
-            ahead.b0 = ~0ull;
-        }
+        if (int rc = claim(b0_, c_lo, c_hi, st_r, &have)) return rc;
         if (!have) {
             // (a read of its own goes into the window the round in flight may be reading: that round first)
-            if (int rc = flush_prev()) return rc < 0 ? EXG_OK : rc;
-            if (!ensure_window(cur, comp_len)) {
+            if (int rc = flush_prev()) return rc;
+            if (!ensure_window(cur_, comp_len)) {
                 *err = "out of device / pinned memory for the compressed bytes of '" + path_ + "'";
                 return EXG_E_HIP;
             }
         }
-        PoolBuf &d_comp = *d_comps[cur];
-        auto &pin = pins[cur];
-        R.blocks.reserve(nx + (b1 - b0));
-        for (uint32_t i = 0; i < nx; i++) {
-            zst::Block E = idx.blocks[extra_ids[i]];
-            const uint64_t sz = E.type == 2 ? E.src_size : 1;
-            const size_t want = (size_t)std::min<uint64_t>(sz, kSideSlot);
-            size_t got = 0;
-            while (got < want) {
-                const ssize_t k = pread(fd_, pin.p + i * kSideSlot + got, want - got, (off_t)(E.src_off + got));
-                if (k <= 0) {
-                    if (k < 0 && errno == EINTR) continue;
-                    *err = "short read of '" + path_ + "'";
-                    return EXG_E_IO;
-                }
-                got += (size_t)k;
-            }
-            E.src_off = i * kSideSlot;
-            E.huf_src = E.tbl_src[0] = E.tbl_src[1] = E.tbl_src[2] = zst::kNone;  // (a source is only read, never decoded)
-            R.blocks.push_back(E);
-        }
-        if (nx) ZS_HIP(hipMemcpyAsync(d_comp.p, pin.p, nx * kSideSlot, hipMemcpyHostToDevice, st_r));
-        bool hip_failed = false;
-        if (!have && comp_len && !pread_parallel(device_, fd_, c_lo, (size_t)comp_len, pin.p + kSide, (char *)d_comp.p + kSide, st_r, &hip_failed)) {
-            *err = hip_failed ? "hipMemcpyAsync failed" : "short read of '" + path_ + "'";
-            return hip_failed ? EXG_E_HIP : EXG_E_IO;
-        }
-        // the round behind this one: its bytes begin to travel now, into the next window (three in turn: the round in flight reads
-        // the one before this round's)
-        auto start_ahead = [&](bool guess) {
-            if (!(read_ahead_ && b1 < n_blocks)) return;
-            uint64_t nb1 = 0, nlo = 0, nhi = 0;
-            if (guess) {
-                // the index is still a prefix: the round behind this one begins with block b1 (in the prefix) and, with as many
-                // blocks, is about as long as this one (twice, behind a quarter) — 5 % more of the file travel; a window that turns out short is read again
-                nlo = idx.blocks[b1].src_off & ~15ull;
-                // (behind a first round of a quarter comes one of a half)
-                const uint64_t like = first_div_used > 1 ? 2 * comp_len : comp_len;
-                nhi = std::min<uint64_t>(n_, nlo + like + like / 20 + (1u << 20));
-            } else {
-                plan(b1, &nb1, &nlo, &nhi);
-            }
-            const int other = (cur + 1) % 3;
-            if (ensure_window(other, nhi - nlo)) launch_ahead(b1, nlo, nhi - nlo, other);
-        };
+        if (int rc = read_round(F, extra_ids, c_lo, comp_len, have)) return rc;
         // (the first round of a file whose index is still a prefix: the round behind it is planned once the whole index is there,
         // behind this round's entropy stages — its bytes begin to travel now all the same, as a guess)
-        const bool ahead_deferred = walker.pending;
-        start_ahead(ahead_deferred);
-        if (!have) ZS_HIP(hipMemsetAsync((char *)d_comp.p + kSide + comp_len, 0, 64, st_r));
-        auto remap = [&](uint32_t g) -> uint32_t {
-            if (g == zst::kNone) return zst::kNone;
-            if (g >= b0) return (uint32_t)(g - b0) + nx;
-            for (uint32_t i = 0; i < nx; i++)
-                if (extra_ids[i] == g) return i;
-            return zst::kNone;
-        };
-        for (uint64_t b = b0; b < b1; b++) {
-            zst::Block B = idx.blocks[b];
-            B.src_off = kSide + (B.src_off - c_lo);
-            B.huf_src = remap(B.huf_src);
-            for (int t = 0; t < 3; t++) B.tbl_src[t] = remap(B.tbl_src[t]);
-            R.blocks.push_back(B);
-        }
-        R.n_extra = nx;
-        // the frames (or parts of frames) in the round
-        for (uint64_t b = b0; b < b1;) {
-            const uint32_t f = idx.blocks[b].frame;
-            const zst::Frame &Fr = idx.frames[f];
-            const uint64_t f_end = (uint64_t)Fr.first_block + Fr.n_blocks, e = std::min<uint64_t>(b1, f_end);
-            zst::RoundFrame rf;
-            rf.first_block = (uint32_t)(b - b0) + nx;
-            rf.n_blocks = (uint32_t)(e - b);
-            rf.frame_id = f;
-            rf.begins = b == Fr.first_block;
-            rf.ends = e == f_end;
-            rf.history = rf.begins ? 0 : hist;
-            rf.has_checksum = Fr.has_checksum;
-            rf.checksum = Fr.checksum;
-            R.frames.push_back(rf);
-            b = e;
-        }
-        R.rep_in[0] = rep[0], R.rep_in[1] = rep[1], R.rep_in[2] = rep[2];
-        R.d_comp = d_comp.p;
-        R.d_history = nullptr;  // (set when the round in front is done: d_hist may move)
-        // the first history byte is stream byte d_pos - hist: `pad` (unused) bytes in front of it put it on the 16-byte grid the
-        // decoder's stores and the scan's loads follow (buffer coordinate 0 is 16-byte aligned, and an address must be
-        // congruent to its stream offset: pad = (d_pos - hist) & 15, also when nothing is kept)
-        R.history = pad + hist;
-        R.front_reserve = reserve_;
-        R.verify_max = verify_max;
-        R.first_block_id = b0;
-        R.comp_base = c_lo - kSide;
-        F.st = st_r;
-        F.d_pos = d_pos;
-        F.hist = hist;
-        int rc;
+        const bool ahead_deferred = walker_.pending;
+        start_ahead(b1, comp_len, ahead_deferred);
+        PoolBuf &d_comp = d_comp_[cur_];
+        if (!have) PRODUCER_HIP(hipMemsetAsync((char *)d_comp.p + kSide + comp_len, 0, 64, st_r));
         const double t_dec0 = now_s();
-        {
-            TraceRange range("exg: zstd round (entropy stages)");
-            rc = zst::decode_round_begin(R, st_r, &F.ctx);
-        }
+        if (int rc = begin_round(F, c_lo)) return rc;
         const double t_dec1 = now_s();
-        if (rc) {
-            const std::string msg = std::string(exg_last_error_message()) + " in '" + path_ + "'";
-            if (int rp = flush_prev()) return rp < 0 ? EXG_OK : rp;
-            *err = msg;
-            return rc;
-        }
         if (ahead_deferred) {
             if (int ri = finish_index(b1)) {
                 zst::decode_round_abandon(F.ctx);
@@ -846,130 +916,66 @@ int ZstdProducer::run(SegmentSink &sink, std::string *err) {
             }
         }
         // ---- frames: sizes
-        std::string size_error;
-        for (const zst::RoundFrame &rf : R.frames) {
-            const zst::Frame &Fr = idx.frames[rf.frame_id];
-            const uint64_t before = rf.begins ? 0 : frame_done;
-            if (rf.ends && Fr.content_size != ~0ull && Fr.content_size != before + rf.out_size) {
-                size_error = "Data corruption detected (zstd frame " + std::to_string(rf.frame_id) + " regenerates " + std::to_string(before + rf.out_size) +
-                             " bytes, its header says " + std::to_string(Fr.content_size) + ") in '" + path_ + "'";
-                break;
-            }
-        }
+        const std::string bad_size = size_error(F.R);
         // this round's chunks execute beside the round in front's resolve launches (they need nothing of it)
-        if (size_error.empty()) {
+        if (bad_size.empty()) {
             TraceRange range("exg: zstd round (execution enqueued)");
-            zst::RoundCtx *ctx = F.ctx;
-            F.ctx = nullptr;
-            rc = zst::decode_round_enqueue_exec(R, ctx);
-            if (!rc) F.ctx = ctx;
-            if (rc) {
-                const std::string msg = std::string(exg_last_error_message()) + " in '" + path_ + "'";
-                if (int rp = flush_prev()) return rp < 0 ? EXG_OK : rp;
-                *err = msg;
-                return rc;
-            }
+            if (int rc = stage(F, zst::decode_round_enqueue_exec)) return fail_behind_prev(rc, std::string(exg_last_error_message()) + in_file(path_));
         }
         // the round in front: done by now or soon — its window is this round's history
-        if (int rp = flush_prev()) return rp < 0 ? EXG_OK : rp;
-        if (!size_error.empty()) {
-            *err = size_error;
+        if (int rc = flush_prev()) return rc;
+        if (!bad_size.empty()) {
+            *err = bad_size;
             return EXG_E_PARSE;
         }
-        R.d_history = d_hist.p;
-        F.launch_rc = 0;
-        if (overlap) {
-            MemMeter *const meter = tl_meter();
-            F.launcher = std::thread([this, &F, meter] {
-                (void)hipSetDevice(device_);
-                MeterScope scope(meter);
-                TraceRange range("exg: zstd round (resolve enqueued)");
-                zst::RoundCtx *ctx = F.ctx;
-                F.ctx = nullptr;
-                F.launch_rc = zst::decode_round_enqueue_resolve(F.R, ctx);
-                if (F.launch_rc) F.launch_err = exg_last_error_message();
-                else F.ctx = ctx;
-            });
-        } else {
-            TraceRange range("exg: zstd round (resolve enqueued)");
-            zst::RoundCtx *ctx = F.ctx;
-            F.ctx = nullptr;
-            rc = zst::decode_round_enqueue_resolve(R, ctx);
-            if (!rc) F.ctx = ctx;
-            if (rc) {
-                *err = std::string(exg_last_error_message()) + " in '" + path_ + "'";
-                return rc;
-            }
-        }
-        F.active = true;
-        // ---- what the next round needs of this one
-        const zst::RoundFrame &lastf = R.frames.back();
-        const uint64_t last_before = lastf.begins ? 0 : frame_done;
-        F.nh = F.npad = F.window = 0;
-        if (lastf.ends) {
-            frame_done = 0, hist = 0, pad = (d_pos + R.produced) & 15;
-            rep[0] = 1, rep[1] = 4, rep[2] = 8;
-        } else {
-            frame_done = last_before + lastf.out_size;
-            rep[0] = R.rep_out[0], rep[1] = R.rep_out[1], rep[2] = R.rep_out[2];
-            const uint64_t window = idx.frames[lastf.frame_id].window;
-            const uint64_t nh = std::min<uint64_t>(std::max<uint64_t>(window, 1), frame_done);
-            const uint64_t end_pos = d_pos + R.produced;  // stream offset behind this round
-            F.nh = nh, F.npad = (end_pos - nh) & 15, F.window = window;
-            hist = nh, pad = F.npad;
-        }
-        d_pos += R.produced;
-        b0 = b1;
-        F.last = b0 >= n_blocks;
-        if (getenv("EXG_TRACE"))
+        if (int rc = enqueue_resolve(F)) return rc;
+        carry_over(F, b1);
+        if (sw_.trace)
             fprintf(stderr, "[exg] zstd producer: round of %.1f MB compressed: window %.1f ms, entropy stages %.1f ms, round in front + enqueue %.1f ms\n",
                     comp_len / 1e6, (t_dec0 - t_join0) * 1e3, (t_dec1 - t_dec0) * 1e3, (now_s() - t_dec1) * 1e3);
-        prev = &F;
-        if (!overlap) {
-            if (int rp = flush_prev()) return rp < 0 ? EXG_OK : rp;
+        prev_ = &F;
+        if (!overlap_) {
+            if (int rc = flush_prev()) return rc;
         }
     }
-    if (int rp = flush_prev()) return rp < 0 ? EXG_OK : rp;
-    if (getenv("EXG_TRACE")) fprintf(stderr, "[exg] zstd producer: last segment out %.1f ms after it began\n", (now_s() - t_run0) * 1e3);
+    if (int rc = flush_prev()) return rc;
+    if (sw_.trace) fprintf(stderr, "[exg] zstd producer: last segment out %.1f ms after it began\n", (now_s() - run_trace_.t0) * 1e3);
     // The checksums still being folded: a mismatch is this thread's result, which the reader looks at once the last
     // segment's rows have been handed out (DecodedSource::finish) — where a streaming decoder reports it too.
-    if (!hasher.drain()) {
-        *err = hasher.error() + " in '" + path_ + "'";
+    if (!hasher_.drain()) {
+        *err = hasher_.error() + in_file(path_);
         return EXG_E_PARSE;
     }
-    if (!damage.empty() && c_end_ >= n_ && !sink.cancelled()) {  // (the shard that reads to the end of the file reports it)
-        *err = damage;
+    if (!damage_.empty() && c_end_ >= n_ && !sink_.cancelled()) {  // (the shard that reads to the end of the file reports it)
+        *err = damage_;
         return EXG_E_PARSE;
     }
-    marks(n_blocks, d_pos);
-    if (!pushed_last && !sink.cancelled()) {  // no block at all (an empty file, skippable frames only): the stream still ends
-        Segment seg;
-        seg.cap = (size_t)(reserve_ + 16 + 64);
-        seg.buf = sink.take(seg.cap);
-        if (!seg.buf) {
-            *err = "out of device memory";
-            return EXG_E_HIP;
-        }
-        seg.org = (int64_t)(d_pos & ~15ull) - (int64_t)reserve_;
-        seg.lo = seg.start = seg.hi = d_pos;
-        seg.last = true;
-        hipError_t he = hipMemsetAsync((char *)seg.buf + reserve_, 0, 16 + 64, st);
-        if (he == hipSuccess) he = hipStreamSynchronize(st);
-        if (he != hipSuccess) {
-            sink.give(seg.buf, seg.cap);
-            *err = std::string("hipMemsetAsync failed: ") + hipGetErrorString(he);
-            return EXG_E_HIP;
-        }
-        (void)sink.push(std::move(seg));
-    }
+    marks(n_blocks_, d_pos_);
+    // no block at all (an empty file, skippable frames only): the stream still ends
+    if (!pushed_last_ && !sink_.cancelled()) return push_empty_last(sink_, d_pos_, reserve_, st_, err);
     return EXG_OK;
 }
+
+class ZstdStream : public SegmentProducer {
+public:
+    explicit ZstdStream(const ZstdInput &in) : in_(in) {}
+    int run(SegmentSink &sink, std::string *err) override {
+        ZstdProducer p(in_, sink, err);
+        const int rc = p.run();
+        return rc == ZstdProducer::kConsumerGone ? EXG_OK : rc;
+    }
+
+private:
+    ZstdInput in_;
+};
 
 }  // namespace
 
 std::unique_ptr<SegmentProducer> make_zstd_producer(exg_reader *r, int fd, uint64_t n, uint64_t c_begin, uint64_t c_end, uint64_t target,
                                                     const std::string &path, uint64_t reserve, const uint64_t mark_at[2]) {
-    return std::unique_ptr<SegmentProducer>(new ZstdProducer(r, fd, n, c_begin, c_end, target, path, reserve, mark_at));
+    ZstdInput in{r->device, fd, n, c_begin, c_end, target, {~0ull, ~0ull}, path, (reserve + 15) & ~15ull, r->mem_cap != 0};
+    if (mark_at) in.mark_at_[0] = mark_at[0], in.mark_at_[1] = mark_at[1];
+    return std::unique_ptr<SegmentProducer>(new ZstdStream(in));
 }
 
 // Shard `shard_index` of `shard_count` of a zstd file: a FRAME belongs to the shard in whose 1/shard_count of the file's bytes
@@ -980,7 +986,7 @@ int plan_zstd_shard(exg_reader *r, int fd, uint64_t n, const std::string &path, 
                     uint64_t *c_end, uint64_t *own_lo, uint64_t *own_hi, bool *bytes_follow) {
     zst::Index idx;
     // (damage: the shards plan with what lies in front of it; the one that reads to the end of the file reports it behind its rows)
-    if (!zst::build_index_fd(fd, n, idx) && !zst::salvage_index(idx)) return fail(r, EXG_E_PARSE, idx.error + " in '" + path + "'");
+    if (!zst::build_index_fd(fd, n, idx) && !zst::salvage_index(idx)) return fail(r, EXG_E_PARSE, idx.error + in_file(path));
     const uint64_t lo = (uint64_t)((unsigned __int128)n * r->shard_index / r->shard_count);
     const uint64_t hi = r->shard_index + 1 == r->shard_count ? n : (uint64_t)((unsigned __int128)n * (r->shard_index + 1) / r->shard_count);
     const size_t nf = idx.frames.size();

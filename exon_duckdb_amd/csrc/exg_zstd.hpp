@@ -110,6 +110,8 @@ struct Index {
 
 // Host: walk the frames and blocks of data[0, n).  false + idx.error on a malformed stream.
 bool build_index(const uint8_t *data, uint64_t n, Index &idx);
+// pread of exactly `len` bytes (false: fewer came)
+bool pread_all(int fd, void *dst, size_t len, uint64_t off);
 // the same over file bytes [0, n) of fd, with small reads (nothing is mapped)
 bool build_index_fd(int fd, uint64_t n, Index &idx);
 // the index of the stream's first blocks (until their estimated output reaches stop_est): exg_zstd_index.cpp
@@ -153,6 +155,15 @@ struct Round {
     uint64_t produced = 0;
     uint32_t rep_out[3] = {1, 4, 8};
 };
+// where a round's compressed bytes lie in d_comp: [the blocks whose tables are repeated, a slot each (at most kRoundExtras) |
+// the round's own, file bytes from c_lo on]
+static constexpr uint32_t kRoundExtras = 4;
+static constexpr uint64_t kSideSlot = (kBlockMax + 64 + 15) & ~15ull, kSide = kRoundExtras * kSideSlot;
+// Host (exg_zstd_index.cpp: no HIP call, no file, no thread): blocks [b0, b1) of idx as a round — R.blocks ([the blocks in front
+// of the round whose Huffman tree / FSE tables its blocks repeat: *extra_ids, in side slot order | the round's own], sources
+// as places in THIS array), R.n_extra and R.frames (a frame that goes on has `hist` bytes in front of the round's).
+// false: more than kRoundExtras sources (the decoder's stages never leave that many in use).
+bool assemble_round(const Index &idx, uint64_t b0, uint64_t b1, uint64_t c_lo, uint64_t hist, Round &R, std::vector<uint64_t> *extra_ids);
 int decode_round(Round &R, void *stream);
 // the same in three phases (exg_zstd.hip): begin (entropy stages, scan, chunk plan) fills R.rep_out, R.frames[].out_off /
 // out_size and R.produced; enqueue (execution, resolve, checksums: launches only) needs R.d_history; wait hands R.d_buf over.

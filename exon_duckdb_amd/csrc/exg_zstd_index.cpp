@@ -283,8 +283,6 @@ bool build_index(const uint8_t *data, uint64_t n, Index &idx) {
     return build_index_from(src, n, idx);
 }
 
-namespace {
-// pread of exactly `len` bytes (false: fewer came)
 bool pread_all(int fd, void *dst, size_t len, uint64_t off) {
     size_t got = 0;
     while (got < len) {
@@ -298,6 +296,7 @@ bool pread_all(int fd, void *dst, size_t len, uint64_t off) {
     return true;
 }
 
+namespace {
 // The walk over a big file is a chain of ~0.5 us preads, two per block: 30 ms per 2 GB in front of the first round.  Only the
 // hops from block header to block header are a chain, though: a first pass makes them (one pread per block, which also
 // brings the literals header), eight threads then fetch every block's sequences header, and the walk proper —
@@ -442,6 +441,66 @@ bool salvage_index(Index &idx) {
     }
     idx.open_valid = false;
     return !idx.frames.empty();
+}
+
+bool assemble_round(const Index &idx, uint64_t b0, uint64_t b1, uint64_t c_lo, uint64_t hist, Round &R, std::vector<uint64_t> *extra_ids) {
+    std::vector<uint64_t> &extra = *extra_ids;
+    extra.clear();
+    // the place of index block g in R.blocks (a source in front of the round gets the next side slot when `add`)
+    auto place = [&](uint32_t g, bool add) -> uint32_t {
+        if (g == kNone) return kNone;
+        if (g >= b0) return (uint32_t)(g - b0) + (uint32_t)extra.size();
+        for (size_t i = 0; i < extra.size(); i++)
+            if (extra[i] == g) return (uint32_t)i;
+        if (!add) return kNone;
+        extra.push_back(g);
+        return (uint32_t)extra.size() - 1;
+    };
+    // blocks in front of the round whose tables its blocks repeat
+    for (uint64_t b = b0; b < b1; b++) {  // first pass: which sources
+        const Block &B = idx.blocks[b];
+        if (B.type != 2) continue;
+        if (B.huf_src != kNone && B.huf_src < b0) (void)place(B.huf_src, true);
+        for (int t = 0; t < 3; t++)
+            if (B.nseq && B.tbl_src[t] != kNone && B.tbl_src[t] < b0) (void)place(B.tbl_src[t], true);
+    }
+    const uint32_t nx = (uint32_t)extra.size();
+    if (nx > kRoundExtras) return false;
+    R.blocks.clear();
+    R.blocks.reserve(nx + (b1 - b0));
+    for (uint32_t i = 0; i < nx; i++) {
+        Block E = idx.blocks[extra[i]];
+        E.src_off = i * kSideSlot;
+        E.huf_src = E.tbl_src[0] = E.tbl_src[1] = E.tbl_src[2] = kNone;  // (a source is only read, never decoded)
+        R.blocks.push_back(E);
+    }
+    for (uint64_t b = b0; b < b1; b++) {
+        Block B = idx.blocks[b];
+        B.src_off = kSide + (B.src_off - c_lo);
+        B.huf_src = place(B.huf_src, false);
+        for (int t = 0; t < 3; t++) B.tbl_src[t] = place(B.tbl_src[t], false);
+        R.blocks.push_back(B);
+    }
+    R.n_extra = nx;
+    // the frames (or parts of frames) in the round
+    R.frames.clear();
+    for (uint64_t b = b0; b < b1;) {
+        const uint32_t f = idx.blocks[b].frame;
+        const Frame &Fr = idx.frames[f];
+        const uint64_t f_end = (uint64_t)Fr.first_block + Fr.n_blocks, e = std::min<uint64_t>(b1, f_end);
+        RoundFrame rf;
+        rf.first_block = (uint32_t)(b - b0) + nx;
+        rf.n_blocks = (uint32_t)(e - b);
+        rf.frame_id = f;
+        rf.begins = b == Fr.first_block;
+        rf.ends = e == f_end;
+        rf.history = rf.begins ? 0 : hist;
+        rf.has_checksum = Fr.has_checksum;
+        rf.checksum = Fr.checksum;
+        R.frames.push_back(rf);
+        b = e;
+    }
+    return true;
 }
 
 }  // namespace zst

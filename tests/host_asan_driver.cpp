@@ -144,6 +144,55 @@ int main(int argc, char **argv) {
                     }
                     close(fd);
                 }
+                // A ROUND as the zstd producer hands it to the device (assemble_round), for the unmutated stream cut at every pair of
+                // block boundaries: the round's own blocks behind the blocks in front of it whose tables they repeat (at most
+                // kRoundExtras, or the round is refused), every source a place in that array and the block it was in the index, the
+                // side blocks without sources of their own, the frames tiling the round's own blocks as the index has them
+                if (trial == 0 && whole) {
+                    using namespace exg::zst;
+                    const uint64_t nb = idx.blocks.size(), hist = 77;
+                    for (uint64_t b0 = 0; b0 < nb; b0++)
+                        for (uint64_t b1 = b0 + 1; b1 <= nb; b1++) {
+                            Round R;
+                            std::vector<uint64_t> extra;
+                            const uint64_t c_lo = idx.blocks[b0].src_off & ~15ull;
+                            if (!assemble_round(idx, b0, b1, c_lo, hist, R, &extra)) {
+                                if (extra.size() <= kRoundExtras) return 13;
+                                continue;
+                            }
+                            const uint32_t nx = R.n_extra;
+                            if (nx > kRoundExtras || nx != extra.size() || R.blocks.size() != nx + (b1 - b0)) return 13;
+                            for (uint32_t i = 0; i < nx; i++) {
+                                const Block &E = R.blocks[i];
+                                if (extra[i] >= b0 || E.src_off != i * kSideSlot || E.src_size != idx.blocks[extra[i]].src_size) return 13;
+                                if (E.huf_src != kNone || E.tbl_src[0] != kNone || E.tbl_src[1] != kNone || E.tbl_src[2] != kNone) return 13;
+                            }
+                            // a source in the round is the index's: in front of the round a side block, inside it the block itself
+                            auto same = [&](uint32_t local, uint32_t global, bool used) {
+                                if (local == kNone) return global == kNone || (global < b0 && !used);
+                                if (local >= R.blocks.size()) return false;
+                                return (local < nx ? extra[local] : b0 + (local - nx)) == global;
+                            };
+                            for (uint64_t b = b0; b < b1; b++) {
+                                const Block &B = R.blocks[nx + (b - b0)], &G = idx.blocks[b];
+                                if (B.src_off != kSide + (G.src_off - c_lo) || B.src_size != G.src_size || B.frame != G.frame) return 13;
+                                if (!same(B.huf_src, G.huf_src, G.type == 2)) return 13;
+                                for (int t = 0; t < 3; t++)
+                                    if (!same(B.tbl_src[t], G.tbl_src[t], G.type == 2 && G.nseq)) return 13;
+                            }
+                            uint64_t next = nx;
+                            for (const RoundFrame &rf : R.frames) {
+                                if (rf.first_block != next || !rf.n_blocks || rf.frame_id >= idx.frames.size()) return 13;
+                                const Frame &Fr = idx.frames[rf.frame_id];
+                                const uint64_t g0 = b0 + (rf.first_block - nx), g1 = g0 + rf.n_blocks, f1 = (uint64_t)Fr.first_block + Fr.n_blocks;
+                                if (g0 < Fr.first_block || g1 > f1) return 13;
+                                if (rf.begins != (g0 == Fr.first_block) || rf.ends != (g1 == f1) || (!rf.ends && g1 != b1)) return 13;
+                                if (rf.history != (rf.begins ? 0 : hist) || rf.has_checksum != Fr.has_checksum || rf.checksum != Fr.checksum) return 13;
+                                next += rf.n_blocks;
+                            }
+                            if (next != nx + (b1 - b0)) return 13;
+                        }
+                }
                 // a file that SHRANK behind its fstat (or an I/O error in the middle): the walk is told a size the file no longer has.
                 // It stops at the first read that does not come — no block behind the failure enters the index (a zero block header
                 // is a valid empty raw block: a walk that went on would push one block per three missing bytes) — and what was

@@ -185,11 +185,17 @@ def test_zstd_larger_than_the_cap(gpu, oracle, fastq_big, tmp_path, monkeypatch)
     assert st["decoded_segments"] >= 8
 
 
-@pytest.mark.parametrize("level,window_log", [(1, 0), (3, 18), (9, 20), (19, 21), (-3, 0)])
-def test_zstd_rounds_against_libzstd(gpu, oracle, tmp_path, monkeypatch, level, window_log):
+@pytest.mark.parametrize("level,window_log,prefix_index", [(1, 0, False), (3, 18, False), (9, 20, False), (19, 21, False), (-3, 0, False), (3, 18, True)],
+                         ids=["1-0", "3-18", "9-20", "19-21", "-3-0", "3-18-prefix-index"])
+def test_zstd_rounds_against_libzstd(gpu, oracle, tmp_path, monkeypatch, level, window_log, prefix_index):
     """frames and parts of frames in rounds of many sizes: multi-frame streams (some frames smaller than a round, some
-    spanning several), skippable frames in between, with and without checksums / content sizes — the rows of the plain file"""
+    spanning several), skippable frames in between, with and without checksums / content sizes — the rows of the plain file
+    (prefix_index: a whole file without a memory cap begins on a prefix of its index with a guessed first window, and the
+    whole index takes the prefix's place behind the first round — what only files of 256 MiB and more do by themselves)"""
     from zstd_util import compress, skippable
+    if prefix_index:
+        monkeypatch.delenv("EXG_DEVICE_MEM_CAP_MB", raising=False)   # (under a cap there is no read-ahead: the path is not taken)
+        monkeypatch.setenv("EXG_ZSTD_INDEX_OVERLAP_MIN", "0")
     data = bytes(oracle.synth_fastq(332 * 24000))                 # 8 MB
     want = _oracle_digest(oracle.fastq_parse(data, want_string_t=False), ["name", "description", "sequence", "quality_scores"])
     cuts = [0, 1000, 1000 + 332 * 300 + 7, 3_000_000, 3_000_001, 6_500_000, len(data)]

@@ -78,11 +78,13 @@ def fastq_seed_files(tmp_path_factory):
     return out
 
 
-@pytest.mark.parametrize("round_out", [128 << 10, 1 << 20])
-def test_fastq_seeds_through_the_reader(gpu, oracle, fastq_seed_files, monkeypatch, round_out):
+@pytest.mark.parametrize("round_out,prefix_index", [(128 << 10, False), (1 << 20, False), (1 << 20, True)], ids=["131072", "1048576", "1048576-prefix-index"])
+def test_fastq_seeds_through_the_reader(gpu, oracle, fastq_seed_files, monkeypatch, round_out, prefix_index):
     from exon_duckdb_amd.reader import ShardReader
     monkeypatch.delenv("EXG_DEVICE_MEM_CAP_MB", raising=False)
     monkeypatch.setenv("EXG_STREAM_ROUND_OUT", str(round_out))
+    if prefix_index:  # the first round on a prefix of the index and a guessed window (by itself: files of 256 MiB and more)
+        monkeypatch.setenv("EXG_ZSTD_INDEX_OVERLAP_MIN", "0")
     for zp, _, text in fastq_seed_files:
         want = _oracle_digest(oracle.fastq_parse(text, want_string_t=False), FQ_COLS)
         r = ShardReader(str(zp), "fastq")
@@ -91,6 +93,18 @@ def test_fastq_seeds_through_the_reader(gpu, oracle, fastq_seed_files, monkeypat
         r.close()
         assert got == want, zp.name
         assert st["decoded_segments"] >= (len(text) // round_out) // 2, st
+
+
+def test_an_error_found_when_a_round_completes_is_reported_as_the_decoders(gpu, tmp_path):
+    """a match that reaches in front of its frame is found when the round's execution is waited for: the reader says what the
+    decoder said (the producer once took that error's code for "the consumer closed the stream", and the stream ended
+    without its last segment)"""
+    from exon_duckdb_amd import ExgError
+    from exon_duckdb_amd.reader import ShardReader
+    p = tmp_path / "bad.fastq.zst"
+    p.write_bytes(zf.encode(zf.invalid()["bad_offset_past_start"][0]))
+    with pytest.raises(ExgError, match="Data corruption detected"):
+        ShardReader(str(p), "fastq").count()
 
 
 def test_fastq_seed_through_new_reader(gpu, fastq_seed_files):
