@@ -384,8 +384,13 @@ __global__ __launch_bounds__(256) void k_fastq_finalize_fused(FastqDev a, ScanWs
     *res = r;
 }
 
-int run_fastq_fused(const exg_fastq_scan_args *args, const FastqDev &dev, uint8_t *ws, const FastqWsLayout &l,
+int run_fastq_fused(const exg_fastq_scan_args *args, const FastqDev &dev_in, uint8_t *ws, const FastqWsLayout &l,
                     hipStream_t stream, bool full) {
+    FastqDev dev = dev_in;
+#ifdef EXG_DEV_PROBE
+    // development builds only (tools/dev_probe.py): the core's ablations (bits 8..11) and its wait histogram (bit 12)
+    if (const char *e = getenv("EXG_FASTQ_DEV_MODE")) dev.flags |= ((uint32_t)atoi(e) & 31u) << 8;
+#endif
     ScanWsHeader *hdr = reinterpret_cast<ScanWsHeader *>(ws);
     constexpr uint64_t kSuperBytes = (uint64_t)FastqFormat::kHalves * kTile;
     constexpr uint32_t kHalvesHost = FastqFormat::kHalves;

@@ -248,16 +248,18 @@ __device__ void scanner_wave(const uint8_t *__restrict__ d_in, uint64_t n_bytes,
 }
 
 // Workgroup side (wave 0): wait for the exclusive prefix of super-tile st (its count is published).
+// polls: how many polls were looked at (development builds: the wait record of tools/dev_probe.py)
 template <int kSuper>
 __device__ unsigned long long wait_prefix(const uint8_t *__restrict__ d_in, uint64_t n_bytes,
                                           unsigned int *__restrict__ tileA,
-                                          unsigned long long *__restrict__ tileP, uint32_t st, uint32_t lane) {
+                                          unsigned long long *__restrict__ tileP, uint32_t st, uint32_t lane, uint32_t &polls) {
     if (st == 0) return 0;
     const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
     __builtin_amdgcn_s_sleep(EXG_FIRST_POLL_SLEEP);
     for (;;) {
         unsigned long long x = lane == 0 ? ld_desc(&tileP[st]) : 0ull;
         x = (unsigned long long)__shfl((long long)x, 0, 64);
+        polls++;
         if (x & kFlag) return x & kVal;
         if (__builtin_amdgcn_s_memrealtime() - t0 > 200000) break;  // 2 ms: the scanner is not running
         __builtin_amdgcn_s_sleep(EXG_POLL_SLEEP);
@@ -427,23 +429,29 @@ __global__ __launch_bounds__(kThreads, kMode == kLean ? F::kMinWavesPerSimd : (k
     }
     const uint64_t super_off = (uint64_t)st * kSuper;
     const uint8_t *__restrict__ d_in = a.d_in;
-    const uint64_t n_pad = (a.n_bytes + 15) & ~15ull;
     const int64_t lim64 = (int64_t)a.n_bytes - (int64_t)super_off;
     const int lim_s = lim64 < kSuper ? (int)lim64 : kSuper;  // super-tile-relative end of input (> 0)
     const bool last_super = st + 1 == n_super;
 
-    // ---- loads: 8 strided 16 B chunks per thread, all in flight at once (+ window by wave 3) ------
+    // ---- loads: kHalves x 4 strided 16 B chunks per thread, all in flight at once (+ window by wave 3) ------
+    // ONE load sequence for every super-tile: the last one, which the input may end in, reads the chunks that lie past the end
+    // from the input's last chunk instead (in bounds; they are zeroed below).  With a sequence of its own for that super-tile
+    // ("off < n_pad ? load : 0") the two met in kHalves x 4 phis, and the register allocator resolved them with copies BETWEEN the
+    // loads of the common one: s_waitcnt vmcnt(1) + v_mov after every other load — two loads in flight per wave, not twelve
+    // (the ISA of the lean FASTQ scan; A/B in one box: 2.247 -> 2.171 ms per 10 GB).  The address is a uniform base + a 32-bit
+    // offset, which also takes the 64-bit vector adds out.
     uint4 v[kHalves * kRows];
-    if (lim_s == kSuper) {
-        const uint8_t *mine = d_in + super_off + (uint64_t)tid * 16;
-#pragma unroll
-        for (int j = 0; j < kHalves * kRows; j++) v[j] = ld_stream16(mine + j * (kThreads * 16));
-    } else {
+    if (lim_s > 0) {
+        const uint8_t *base = d_in + super_off;
+        const uint32_t last = (((uint32_t)lim_s + 15u) & ~15u) - 16u;
 #pragma unroll
         for (int j = 0; j < kHalves * kRows; j++) {
-            uint64_t off = super_off + (uint64_t)(j * kThreads + tid) * 16;
-            v[j] = off < n_pad ? ld_stream16(d_in + off) : make_uint4(0, 0, 0, 0);
+            const uint32_t rel = (uint32_t)(j * kThreads + tid) * 16;
+            v[j] = ld_stream16(base + (rel < last ? rel : last));
         }
+    } else {
+#pragma unroll
+        for (int j = 0; j < kHalves * kRows; j++) v[j] = make_uint4(0, 0, 0, 0);
     }
     uint4 wv = make_uint4(0, 0, 0, 0);
     const int64_t woff = (int64_t)super_off - kWin + (int64_t)lane * 16;  // wave 3 only
@@ -454,6 +462,7 @@ __global__ __launch_bounds__(kThreads, kMode == kLean ? F::kMinWavesPerSimd : (k
     uint32_t hi = 0, cnt = 0;
 #pragma unroll
     for (int j = 0; j < kHalves * kRows; j++) {
+        if (lim_s != kSuper && lim_s - (int)(j * kThreads + tid) * 16 <= 0) v[j] = make_uint4(0, 0, 0, 0);  // a chunk past the end
         uint32_t mj = match16(v[j], 0x0A0A0A0Au);
         hi |= v[j].x | v[j].y | v[j].z | v[j].w;
         if (lim_s != kSuper) {  // the input ends inside this super-tile: mask the bytes past the end
@@ -483,6 +492,9 @@ __global__ __launch_bounds__(kThreads, kMode == kLean ? F::kMinWavesPerSimd : (k
         if (tid == 0 && !analytic)
             __hip_atomic_store(&tileA[st], kFlagA | n_nl_super | (non_ascii ? kNonAsciiA : 0u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
+#ifdef EXG_DEV_PROBE
+    const unsigned long long t_pub = __builtin_amdgcn_s_memrealtime();
+#endif
     const unsigned long long halo_nl = rfl64(hdr->halo_nl);
     // Bytes >= 0x80 need UTF-8 validation of every field (the reference builds Arrow Utf8 columns).  That is rare and not the
     // lean scan's business: it marks the super-tile; the any-shape scan validates the fields of the records that end here
@@ -578,7 +590,25 @@ __global__ __launch_bounds__(kThreads, kMode == kLean ? F::kMinWavesPerSimd : (k
                 } else if (analytic) {
                     pre = F::analytic_prefix(super_off);
                 } else {
-                    pre = wait_prefix<kSuper>(d_in, a.n_bytes, tileA, tileP, st, lane);
+                    uint32_t polls = 0;
+#ifdef EXG_DEV_PROBE
+                    const unsigned long long t_in = __builtin_amdgcn_s_memrealtime();
+#endif
+                    pre = wait_prefix<kSuper>(d_in, a.n_bytes, tileA, tileP, st, lane, polls);
+#ifdef EXG_DEV_PROBE
+                    // flags bit 12 (tools/dev_probe.py --hist): this wait as a record of the workgroup's own — the FarRec of its
+                    // half 0, which the lean scan leaves alone —: 10 ns ticks wave 0 stood in wait_prefix, ticks from the
+                    // count's publish to the prefix, polls looked at.  (Counters in the header instead, five atomics per
+                    // workgroup on one line, stretched the launch from 2.3 to 12 ms and the waits with it.)
+                    if (kMode == kLean && ((a.flags >> 12) & 1u) && lane == 0) {
+                        const unsigned long long now = __builtin_amdgcn_s_memrealtime();
+                        FarRec f = {};
+                        f.pos[0] = (int32_t)(now - t_in);
+                        f.pos[1] = (int32_t)(now - t_pub);
+                        f.pos[2] = (int32_t)polls;
+                        far_rec_of<kB>(tile_qend, a.n_bytes)[(uint64_t)st * kHalves] = f;
+                    }
+#endif
                 }
                 if (lane == 0) s.prefix = pre;
             }
