@@ -25,8 +25,16 @@ EXG_PE_VCF_NO_HEADER = 11
 EXG_PE_FIELD_TOO_LONG = 12
 EXG_PE_VCF_INFO = 13
 EXG_PE_VCF_FORMAT = 14
+EXG_PE_BAM_BLOCK_SIZE = 15
+EXG_PE_BAM_TRUNCATED = 16
+EXG_PE_BAM_READ_NAME = 17
+EXG_PE_BAM_REFERENCE_ID = 18
+EXG_PE_BAM_FIELD_LENGTHS = 19
+EXG_PE_BAM_CIGAR_OP = 20
+EXG_PE_BAM_QUALITY = 21
 
-EXG_FMT_FASTA, EXG_FMT_FASTQ, EXG_FMT_VCF = 1, 2, 3
+EXG_FMT_FASTA, EXG_FMT_FASTQ, EXG_FMT_VCF, EXG_FMT_BAM = 1, 2, 3, 4
+EXG_BAM_COLUMNS = 10
 EXG_F_BOF, EXG_F_EOF, EXG_F_NO_STORE = 1, 2, 4
 EXG_RF_NON_ASCII, EXG_RF_HEAD_UNRESOLVED, EXG_RF_FALLBACK, EXG_RF_CAPACITY, EXG_RF_INDEX_OVERFLOW = 1, 2, 4, 8, 16
 EXG_RF_QUAL_RANGE = 32
@@ -117,6 +125,43 @@ class FastaScanArgs(C.Structure):
     ]
 
 
+class BamScanResult(C.Structure):
+    _fields_ = [
+        ("n_records", C.c_uint64),
+        ("consumed_bytes", C.c_uint64),
+        ("side_bytes", C.c_uint64),
+        ("error_record", C.c_uint64),
+        ("error_offset", C.c_uint64),
+        ("error_code", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("tiles", C.c_uint64),
+        ("tiles_rewalked", C.c_uint64),
+    ]
+
+
+class BamScanArgs(C.Structure):
+    _fields_ = [
+        ("d_input", C.c_void_p),
+        ("n_bytes", C.c_uint64),
+        ("flags", C.c_uint32),
+        ("n_ref", C.c_int32),
+        ("columns", C.c_uint64),
+        ("d_ref_names", C.c_void_p),
+        ("d_ref_offsets", C.c_void_p),
+        ("ref_names_base", C.c_uint64),
+        ("d_columns", C.c_void_p * 10),
+        ("d_validity", C.c_void_p * 10),
+        ("d_side", C.c_void_p),
+        ("side_capacity", C.c_uint64),
+        ("side_base", C.c_uint64),
+        ("capacity_records", C.c_uint64),
+        ("d_workspace", C.c_void_p),
+        ("workspace_bytes", C.c_uint64),
+        ("d_result", C.c_void_p),
+        ("stream", C.c_void_p),
+    ]
+
+
 class QualityListArgs(C.Structure):
     _fields_ = [
         ("d_strings", C.c_void_p),
@@ -158,6 +203,7 @@ SIGNATURES = {
     "exg_fastq_scan": (C.c_int, [C.POINTER(FastqScanArgs)]),
     "exg_vcf_scan": (C.c_int, [C.POINTER(VcfScanArgs)]),
     "exg_fasta_scan": (C.c_int, [C.POINTER(FastaScanArgs)]),
+    "exg_bam_scan": (C.c_int, [C.POINTER(BamScanArgs)]),
     "exg_gzip_index": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),
                                  C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
     "exg_inflate_members": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
@@ -175,7 +221,8 @@ class ReaderStats(C.Structure):
     _fields_ = [("device_bytes_now", C.c_uint64), ("device_bytes_peak", C.c_uint64), ("device_mem_cap", C.c_uint64),
                 ("device_batch_bytes", C.c_uint64), ("device_batches", C.c_uint64), ("decoded_segments", C.c_uint64),
                 ("scan_algo", C.c_uint64), ("input_bytes", C.c_uint64), ("input_compression", C.c_uint64),
-                ("nested_ns", C.c_uint64), ("host_vector_bytes", C.c_uint64), ("reserved", C.c_uint64 * 3)]
+                ("nested_ns", C.c_uint64), ("host_vector_bytes", C.c_uint64), ("bam_tiles", C.c_uint64),
+                ("bam_tiles_rewalked", C.c_uint64), ("reserved", C.c_uint64 * 1)]
 
 # libexon_tf_test.so (csrc/testing/): test / bench scaffolding — synthetic inputs generated in HBM, consumers that drain a
 # reader's chunks (counting, or folding every row into a digest), host-only introspection, the host-pipeline probe

@@ -5,6 +5,7 @@
 #include <string.h>
 
 #include "exg_arrow.hpp"
+#include "exg_bam.hpp"
 #include "exg_fastq.hpp"
 
 namespace exg {
@@ -63,11 +64,19 @@ extern "C" const char *exg_parse_error_string(uint32_t code) {
         case EXG_PE_FIELD_TOO_LONG: return "field longer than 4 GiB";
         case EXG_PE_VCF_INFO: return "invalid info field value";
         case EXG_PE_VCF_FORMAT: return "invalid genotype field value";
+        case EXG_PE_BAM_BLOCK_SIZE: return "block_size below 32";
+        case EXG_PE_BAM_TRUNCATED: return "record runs past the end of the stream";
+        case EXG_PE_BAM_READ_NAME: return "empty read name or read name without its NUL";
+        case EXG_PE_BAM_REFERENCE_ID: return "reference id outside the header's reference list";
+        case EXG_PE_BAM_FIELD_LENGTHS: return "field lengths exceed block_size";
+        case EXG_PE_BAM_CIGAR_OP: return "invalid CIGAR operation";
+        case EXG_PE_BAM_QUALITY: return "quality score above 93";
         default: return "unknown parse error";
     }
 }
 
 extern "C" uint64_t exg_scan_workspace_bytes(int format, uint64_t n_bytes) {
+    if (format == EXG_FMT_BAM) return exg::bam::workspace_bytes(n_bytes);
     return fastq_ws_layout(n_bytes, 0, format == EXG_FMT_FASTA ? 4 : 1).total_bytes;
 }
 

@@ -352,12 +352,13 @@ struct FilterEval {
                 int d;  // sign of column - literal; 2 = unordered (NaN)
                 if (cols.kind[c] == kColStr) {
                     d = cmp_str(c, r, op);
-                } else if (cols.kind[c] == kColI64 && op.lit == kLitInt) {
-                    const int64_t x = ((const int64_t *)cols.data[c])[r];
+                } else if ((cols.kind[c] == kColI64 || cols.kind[c] == kColI32) && op.lit == kLitInt) {
+                    const int64_t x = cols.kind[c] == kColI32 ? (int64_t)((const int32_t *)cols.data[c])[r] : ((const int64_t *)cols.data[c])[r];
                     d = x < op.i ? -1 : x > op.i ? 1 : 0;
                 } else {
-                    const double x = cols.kind[c] == kColI64 ? (double)((const int64_t *)cols.data[c])[r]
-                                                             : (double)((const float *)cols.data[c])[r];
+                    const double x = cols.kind[c] == kColI64   ? (double)((const int64_t *)cols.data[c])[r]
+                                     : cols.kind[c] == kColI32 ? (double)((const int32_t *)cols.data[c])[r]
+                                                               : (double)((const float *)cols.data[c])[r];
                     const double y = op.lit == kLitInt ? (double)op.i : op.f;
                     d = x < y ? -1 : x > y ? 1 : x == y ? 0 : 2;
                 }

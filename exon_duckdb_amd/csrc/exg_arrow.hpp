@@ -58,7 +58,7 @@ void quality_list(const StrCol &c, uint64_t n, const uint64_t *d_goff, ListEntry
                   uint64_t values_cap, hipStream_t stream);
 
 // ---- row selection (filters) ------------------------------------------------------------------------
-enum : uint8_t { kColStr = 0, kColI64 = 1, kColF32 = 2 };
+enum : uint8_t { kColStr = 0, kColI64 = 1, kColF32 = 2, kColI32 = 3 };  // (kColI32 compares as kColI64 does, on the widened value)
 enum : uint8_t { kOpCmp = 0, kOpIsNull = 1, kOpIsNotNull = 2, kOpAnd = 3, kOpOr = 4 };
 enum : uint8_t { kEq = 0, kNe = 1, kLt = 2, kLe = 3, kGt = 4, kGe = 5 };
 enum : uint8_t { kLitStr = 0, kLitInt = 1, kLitFloat = 2 };
@@ -70,7 +70,7 @@ struct FilterOp {
     double f;
 };
 static constexpr int kMaxFilterOps = 32;
-static constexpr int kMaxFilterCols = 9;
+static constexpr int kMaxFilterCols = 10;  // (read_bam_file_records has ten columns)
 struct FilterProgram {  // postfix
     uint32_t n_ops;
     FilterOp ops[kMaxFilterOps];

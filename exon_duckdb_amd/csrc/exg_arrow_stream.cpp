@@ -1520,6 +1520,8 @@ static int build_stream(const exg_open_args &oa, const char *filters, std::share
 extern "C" ReaderResult new_reader(ArrowArrayStream *stream_ptr, const char *uri, uintptr_t batch_size, const char *compression,
                                    const char *file_format, const char *filters) {
     if (!stream_ptr || !uri || !file_format) return result_error("new_reader: null argument");
+    if (strcasecmp(file_format, "bam") == 0)
+        return result_error("new_reader: BAM is served at the chunk boundary only (exg_open / read_bam_file_records); the Arrow boundary for BAM is not built");
     exg_open_args oa;
     memset(&oa, 0, sizeof oa);
     oa.path = uri;

@@ -18,7 +18,7 @@ namespace ea = exg::arrow;
 
 struct FilterColumn {
     std::string name;
-    char kind;  // 'u' Utf8 / VARCHAR, 'l' Int64, 'f' Float32, anything else: not filterable (nested)
+    char kind;  // 'u' Utf8 / VARCHAR, 'l' Int64, 'i' Int32, 'f' Float32, anything else: not filterable (nested)
 };
 
 struct FilterParser {
@@ -70,7 +70,7 @@ struct FilterParser {
             if (strcasecmp(cols[c].name.c_str(), name.c_str()) == 0) col = (int)c;
         if (col < 0) return err = "No field named " + name, false;
         const std::string fmt(1, cols[col].kind);
-        if (fmt != "u" && fmt != "l" && fmt != "f") return err = "filters on nested column " + name + " are not supported", false;
+        if (fmt != "u" && fmt != "l" && fmt != "i" && fmt != "f") return err = "filters on nested column " + name + " are not supported", false;
         ea::FilterOp op;
         memset(&op, 0, sizeof op);
         op.col = (uint8_t)col;

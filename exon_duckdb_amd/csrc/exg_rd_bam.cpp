@@ -1,0 +1,300 @@
+// exg_rd_bam.cpp — reader level of read_bam_file_records: a BAM file is BGZF members around a binary record stream.  The
+// members are inflated (and their CRCs verified) by the gzip producer into a bounded stream of decoded segments in HBM
+// (exg_rd_source.hpp); this file is everything behind the inflate:
+//   bam_open_file   the header, read from the front of the decoded stream through acquire() — as much of it as it takes: a
+//                   header may be larger than a segment — and parsed on the host (exg_bam_header.cpp); the reference names go
+//                   into a pinned table that every batch keeps alive (reference / mate_reference strings longer than 12
+//                   bytes point into it) and, with their offsets, into device memory
+//   bam_next_batch  one device batch = the records that lie completely inside what acquire() returned; the tail is carried
+//                   by asking for the next position; a batch without a complete record (one record larger than it) asks for
+//                   more.  Nothing of a BAM segment is useful on the host as it is — the sequence is packed, the qualities
+//                   lack their offset, the aux data is unwanted — so no host mirror is ever requested: the selected
+//                   columns' out-of-line strings are produced into a side buffer (exg_bam.hip) and only that, and the
+//                   vectors, cross PCIe.
+#include <string.h>
+
+#include <algorithm>
+
+#include "exg_bam.hpp"
+#include "exg_bam_header.hpp"
+#include "exg_filter.hpp"
+#include "exg_rd_bam.hpp"
+#include "exg_rd_source.hpp"
+
+namespace exg_rd {
+
+namespace {
+
+struct BamState {
+    int device = 0;
+    BamHeader header;
+    std::shared_ptr<PinnedBlock> names;  // the reference names on the host (pinned, pooled): kept alive by every batch
+    void *d_names = nullptr, *d_offsets = nullptr;
+    size_t d_names_bytes = 0, d_offsets_bytes = 0;
+    // the scan's buffers (the reader's dev_alloc: freed with the reader, or when a batch needs larger ones)
+    void *d_ws = nullptr, *d_side = nullptr, *d_cols[EXG_BAM_COLUMNS] = {}, *d_valid[EXG_BAM_COLUMNS] = {};
+    void *d_row_map = nullptr, *d_gather = nullptr, *d_filter_tmp = nullptr;
+    uint64_t in_cap = 0, side_cap = 0, cap_records = 0;
+    bool worst_case_rows = false;
+    uint64_t rows_before = 0;  // records of the current file in front of the current batch (a record error names its ordinal)
+    std::atomic<uint64_t> tiles{0}, tiles_rewalked{0};
+    void drop_tables() {
+        if (d_names) dev_pool()->give(device, d_names, d_names_bytes);
+        if (d_offsets) dev_pool()->give(device, d_offsets, d_offsets_bytes);
+        d_names = d_offsets = nullptr;
+    }
+    ~BamState() { drop_tables(); }
+};
+
+BamState *state_of(exg_reader *r) {
+    if (!r->bam_state) {
+        auto s = std::make_shared<BamState>();
+        s->device = r->device;
+        r->bam_state = s;
+    }
+    return (BamState *)r->bam_state.get();
+}
+
+const bool kIsInt[EXG_BAM_COLUMNS] = {false, true, false, true, true, false, false, false, false, false};
+const bool kNullable[EXG_BAM_COLUMNS] = {false, false, true, true, true, true, false, true, false, false};
+
+int ensure_buffers(exg_reader *r, BamState *s, uint64_t n, uint64_t side_bytes) {
+    if (s->d_ws && n <= s->in_cap && side_bytes <= s->side_cap) return EXG_OK;
+    if (s->d_ws) {
+        RD_HIP(r, hipStreamSynchronize(r->stream));
+        r->free_device();
+    }
+    // segments come at about the target size + what the scan carries over: provision once
+    s->in_cap = std::max<uint64_t>(n, r->device_batch_bytes + r->device_batch_bytes / 4 + (r->src ? r->src->reserve() : 0) + 4096);
+    // rows: a 150 bp read is ~350 bytes, one per 64 bytes is dense; the smallest record there can be is 37 bytes — a batch
+    // that holds more rows than provisioned is found out before a column is written and provisioned for the worst case
+    s->cap_records = s->worst_case_rows ? s->in_cap / exg::bam::kMinRecordBytes + 2 : s->in_cap / 64 + 4096;
+    // side buffer: name + CIGAR text + sequence + qualities of a 150 bp read are about its own bytes (the sequence doubles,
+    // the aux fields are dropped); a batch that needs more says so before anything is written
+    s->side_cap = std::max<uint64_t>(side_bytes, s->in_cap + s->in_cap / 4);
+    int rc;
+    if ((rc = r->dev_alloc(&s->d_ws, exg_scan_workspace_bytes(EXG_FMT_BAM, s->in_cap)))) return rc;
+    if ((rc = r->dev_alloc(&s->d_side, s->side_cap + 64))) return rc;
+    const uint64_t produce = r->want_cols | r->filter_cols;
+    for (int c = 0; c < EXG_BAM_COLUMNS; c++) {
+        if (!((produce >> c) & 1)) continue;
+        if ((rc = r->dev_alloc(&s->d_cols[c], s->cap_records * (kIsInt[c] ? 4 : 16)))) return rc;
+        if (kNullable[c] && (rc = r->dev_alloc(&s->d_valid[c], (s->cap_records + 63) / 64 * 8))) return rc;
+    }
+    if (r->has_filter) {
+        if ((rc = r->dev_alloc(&s->d_row_map, s->cap_records * 4 + 64))) return rc;
+        if ((rc = r->dev_alloc(&s->d_gather, std::max<uint64_t>(s->cap_records * 16, sizeof(ea::FilterCols))))) return rc;
+        if ((rc = r->dev_alloc(&s->d_filter_tmp, (s->cap_records + 1 + ea::scan_tmp_entries(s->cap_records)) * 8))) return rc;
+    }
+    if (!r->d_res && !(r->d_res = dev_pool()->take(r->device, 4096))) return fail(r, EXG_E_HIP, "out of device memory");
+    return EXG_OK;
+}
+
+}  // namespace
+
+int bam_open_file(exg_reader *r) {
+    BamState *s = state_of(r);
+    const std::string &path = r->files[r->file_idx - 1];
+    s->rows_before = 0;
+    RD_HIP(r, hipStreamSynchronize(r->stream));  // (a batch of the file before may still read the tables)
+    s->drop_tables();
+    PinBuf host;
+    for (uint64_t want = 64u << 10;;) {
+        const uint8_t *d_at = nullptr;
+        uint64_t avail = 0;
+        bool eof = false;
+        std::string msg;
+        int rc = r->src->acquire(0, want, &d_at, &avail, &eof, &msg);
+        if (rc) return fail(r, rc, msg + (msg.find(path) == std::string::npos ? in_file(path) : ""));
+        const uint64_t len = std::min<uint64_t>(want, avail);
+        if (!host.ensure((size_t)len + 64)) return fail(r, EXG_E_HIP, "out of pinned host memory for the BAM header");
+        if (len) RD_HIP(r, hipMemcpyAsync(host.p, d_at, len, hipMemcpyDeviceToHost, r->stream));
+        RD_HIP(r, hipStreamSynchronize(r->stream));
+        uint64_t need = 0;
+        std::string why;
+        const int prc = bam_parse_header((const uint8_t *)host.p, len, eof && len == avail, &s->header, &need, &why);
+        if (prc == kBamHeaderBad) return fail(r, EXG_E_PARSE, why + in_file(path));
+        if (prc == kBamHeaderOk) break;
+        want = std::max<uint64_t>(need, want * 2);
+    }
+    // the reference names: a pinned table of the reader's (the batches keep it alive), and a copy on the device
+    const BamHeader &h = s->header;
+    auto blk = std::make_shared<PinnedBlock>();
+    size_t cap = h.names.size() + 64;
+    blk->p = global_pool()->take(&cap);
+    if (!blk->p) return fail(r, EXG_E_HIP, "out of pinned host memory for the BAM reference names");
+    blk->cap = cap, blk->pooled = true, blk->n = h.names.size();
+    memcpy(blk->p, h.names.data(), h.names.size());
+    s->names = blk;
+    s->d_names_bytes = h.names.size() + 64, s->d_offsets_bytes = h.offsets.size() * 8;
+    if (!(s->d_names = dev_pool()->take(r->device, s->d_names_bytes)) || !(s->d_offsets = dev_pool()->take(r->device, s->d_offsets_bytes)))
+        return fail(r, EXG_E_HIP, "out of device memory for the BAM reference names");
+    if (!h.names.empty()) RD_HIP(r, hipMemcpyAsync(s->d_names, blk->p, h.names.size(), hipMemcpyHostToDevice, r->stream));
+    RD_HIP(r, hipMemcpyAsync(s->d_offsets, h.offsets.data(), h.offsets.size() * 8, hipMemcpyHostToDevice, r->stream));
+    RD_HIP(r, hipStreamSynchronize(r->stream));
+    r->file_pos = r->data_base = h.end;
+    return EXG_OK;
+}
+
+void bam_stats(exg_reader *r, uint64_t *tiles, uint64_t *rewalked) {
+    *tiles = *rewalked = 0;
+    if (!r->bam_state) return;
+    BamState *s = (BamState *)r->bam_state.get();
+    *tiles = s->tiles.load(), *rewalked = s->tiles_rewalked.load();
+}
+
+int bam_next_batch(exg_reader *r, bool count_only, uint64_t *n_records_out) {
+    BamState *s = state_of(r);
+    const std::string &path = r->files[r->file_idx - 1];
+    const bool no_store = count_only && !r->has_filter;  // a predicate needs its columns even for COUNT(*)
+    uint64_t want = r->device_batch_bytes;
+    for (;;) {
+        // "the rest of the segment that holds file_pos"; a batch that held no complete record asks for more than a batch
+        const uint64_t ask = want > r->device_batch_bytes ? want : std::min<uint64_t>(want, 1u << 20);
+        const uint8_t *d_at = nullptr;
+        uint64_t n = 0;
+        bool eof = false;
+        std::string msg;
+        int rc = r->src->acquire(r->file_pos, ask, &d_at, &n, &eof, &msg);
+        if (rc) return fail(r, rc, msg + (msg.find(path) == std::string::npos ? in_file(path) : ""));
+        r->n_segments = r->src->segments_consumed() + 1;
+        if (n == 0 && eof) {
+            r->file_done = true;
+            return EXG_OK;
+        }
+        if ((rc = ensure_buffers(r, s, n, 0))) return rc;
+        TraceRange scan_range("exg: scan bam batch");
+        exg_bam_scan_args a;
+        memset(&a, 0, sizeof a);
+        a.d_input = d_at;
+        a.n_bytes = n;
+        a.flags = (eof ? EXG_F_EOF : 0u) | (no_store ? EXG_F_NO_STORE : 0u);
+        a.n_ref = s->header.n_ref;
+        // every record is validated whatever is selected; only the selected columns (and the predicate's) are produced
+        a.columns = (r->want_cols | r->filter_cols) & ((1ull << EXG_BAM_COLUMNS) - 1);
+        if (!a.columns) a.columns = 1ull << 63;
+        a.d_ref_names = (const uint8_t *)s->d_names;
+        a.d_ref_offsets = (const uint64_t *)s->d_offsets;
+        a.ref_names_base = (uint64_t)(uintptr_t)s->names->p;
+        a.d_workspace = s->d_ws;
+        a.workspace_bytes = exg_scan_workspace_bytes(EXG_FMT_BAM, s->in_cap);
+        a.d_result = (exg_bam_scan_result *)r->d_res;
+        a.stream = r->stream;
+        exg_bam_scan_result res;
+        if ((rc = exg::bam::discover(&a, &res))) return fail(r, rc, exg_last_error_message());
+        r->n_batches++;
+        s->tiles += res.tiles, s->tiles_rewalked += res.tiles_rewalked;
+        if (res.n_records == 0 && !res.error_code && !eof) {
+            want = std::max<uint64_t>(want, n) * 2;  // one record larger than the batch: widen it
+            continue;
+        }
+        if (!no_store && res.n_records > s->cap_records) {
+            if (s->worst_case_rows) return fail(r, EXG_E_CAPACITY, "more BAM records than bytes allow: internal error");
+            s->worst_case_rows = true;  // denser rows than provisioned: worst-case vectors, same batch again
+            s->in_cap = 0;
+            continue;
+        }
+        if (!no_store && res.side_bytes > s->side_cap) {
+            if ((rc = ensure_buffers(r, s, n, res.side_bytes))) return rc;
+            continue;  // (the workspace moved: same batch again)
+        }
+        uint64_t k = res.n_records;
+        if (res.error_code) {
+            r->pending_error = res.error_code;
+            r->pending_error_offset = r->file_pos + res.error_offset;
+            r->pending_error_text = "invalid BAM record " + std::to_string(s->rows_before + res.error_record) + ": " +
+                                    exg_parse_error_string(res.error_code) + " at byte " + std::to_string(r->file_pos + res.error_offset) +
+                                    " of the decoded stream of " + path;
+        }
+        s->rows_before += res.n_records;
+        if (k && !no_store) {
+            auto b = std::make_shared<Batch>();
+            b->host.reserve(r->host_hint);
+            b->file = s->names;
+            uint8_t *h_side = nullptr;
+            if (res.side_bytes && !(h_side = (uint8_t *)b->host.alloc(res.side_bytes + 64))) return fail(r, EXG_E_HIP, "out of pinned host memory");
+            for (int c = 0; c < EXG_BAM_COLUMNS; c++) a.d_columns[c] = s->d_cols[c], a.d_validity[c] = (uint64_t *)s->d_valid[c];
+            a.d_side = (uint8_t *)s->d_side;
+            a.side_capacity = s->side_cap;
+            a.side_base = (uint64_t)(uintptr_t)h_side;
+            a.capacity_records = s->cap_records;
+            if ((rc = exg::bam::emit(&a, &res))) return fail(r, rc, exg_last_error_message());
+            const uint32_t *row_map = nullptr;
+            if (r->has_filter) {
+                // rows where the predicate is TRUE -> row map; the columns are gathered through it on their way out (the side
+                // buffer travels whole: the strings of the rows that stay behind are in it too)
+                ea::FilterCols fc;
+                memset(&fc, 0, sizeof fc);
+                for (int c = 0; c < EXG_BAM_COLUMNS; c++) {
+                    fc.kind[c] = kIsInt[c] ? ea::kColI32 : ea::kColStr;
+                    fc.data[c] = s->d_cols[c];
+                    fc.validity[c] = (const uint64_t *)s->d_valid[c];
+                    const bool ref = c == 2 || c == 7;
+                    fc.d_base[c] = ref ? (const uint8_t *)s->d_names : (const uint8_t *)s->d_side;
+                    fc.payload_base[c] = ref ? a.ref_names_base : a.side_base;
+                }
+                uint64_t *d_goff = (uint64_t *)s->d_filter_tmp, *d_tmp = d_goff + s->cap_records + 1;
+                ea::FilterCols *d_fc = (ea::FilterCols *)s->d_gather;  // (the scratch column is free until the gathers)
+                RD_HIP(r, hipMemcpyAsync(d_fc, &fc, sizeof fc, hipMemcpyHostToDevice, r->stream));
+                ea::filter_rows((const ea::FilterProgram *)r->d_filter_prog, d_fc, (const uint8_t *)r->d_filter_consts, k, d_goff, d_tmp,
+                                (uint32_t *)s->d_row_map, r->stream);
+                uint64_t n_sel = 0;
+                RD_HIP(r, hipMemcpyAsync(&n_sel, d_goff + k, 8, hipMemcpyDeviceToHost, r->stream));
+                RD_HIP(r, hipStreamSynchronize(r->stream));
+                k = n_sel;
+                row_map = (const uint32_t *)s->d_row_map;
+            }
+            if (k && !count_only) {
+                TraceRange d2h_range("exg: columns -> host");
+                b->n_rows = k;
+                b->n_cols = EXG_BAM_COLUMNS;
+                bool any_side = false;
+                for (int c = 0; c < EXG_BAM_COLUMNS; c++) {
+                    b->elem[c] = 0, b->cols[c] = nullptr;
+                    if (!r->want(c)) continue;
+                    const uint32_t es = kIsInt[c] ? 4 : 16;
+                    b->elem[c] = es;
+                    if (!(b->cols[c] = b->host.alloc(k * es))) return fail(r, EXG_E_HIP, "out of pinned host memory");
+                    const void *src = s->d_cols[c];
+                    if (row_map) {
+                        if (es == 16) ea::gather_u128(src, row_map, k, s->d_gather, r->stream);
+                        else ea::gather_u32((const uint32_t *)src, row_map, k, (uint32_t *)s->d_gather, r->stream);
+                        src = s->d_gather;
+                    }
+                    RD_HIP(r, hipMemcpyAsync(b->cols[c], src, k * es, hipMemcpyDeviceToHost, r->stream));
+                    r->host_vector_bytes += k * es;
+                    if (kNullable[c]) {
+                        const size_t vw = (size_t)((k + 63) / 64) * 8;
+                        if (!(b->validity[c] = b->host.alloc(vw))) return fail(r, EXG_E_HIP, "out of pinned host memory");
+                        const void *v = s->d_valid[c];
+                        if (row_map) {
+                            ea::gather_bits((const uint64_t *)v, row_map, k, (uint64_t *)s->d_gather, r->stream);
+                            v = s->d_gather;
+                        }
+                        RD_HIP(r, hipMemcpyAsync(b->validity[c], v, vw, hipMemcpyDeviceToHost, r->stream));
+                        r->host_vector_bytes += vw;
+                    }
+                    any_side |= c == 0 || c == 6 || c == 8 || c == 9;
+                }
+                if (any_side && res.side_bytes) {
+                    RD_HIP(r, hipMemcpyAsync(h_side, s->d_side, res.side_bytes, hipMemcpyDeviceToHost, r->stream));
+                    r->host_vector_bytes += res.side_bytes;  // (the strings' payload is made on the device: it is part of the vectors)
+                }
+                RD_HIP(r, hipStreamSynchronize(r->stream));
+                r->host_hint = b->host.total + b->host.total / 8 + (1u << 20);
+                b->seq = r->batch_seq++;
+                r->batch = b;
+            }
+        }
+        *n_records_out = k;
+        if (res.error_code) {
+            r->file_done = true;
+        } else {
+            r->file_pos += res.consumed_bytes;
+            if (eof) r->file_done = true;  // (a tail behind the last record at the end of the stream is an error above)
+        }
+        return EXG_OK;
+    }
+}
+
+}  // namespace exg_rd

@@ -23,6 +23,7 @@
 #include "exg_fastq_ws.hpp"
 #include "exg_filter.hpp"
 #include "exg_map_guard.hpp"
+#include "exg_rd_bam.hpp"
 #include "exg_rd_source.hpp"
 
 namespace exg_rd {
@@ -175,6 +176,7 @@ static int plan_bgzf_shard(exg_reader *r, const std::string &path, uint64_t n, u
 // sent every byte back twice, 92 ms for 1.96 GB).
 enum PayloadRoute { kPayloadNone, kPayloadCompact, kPayloadMirror };
 static PayloadRoute payload_route(const exg_reader *r) {
+    if (r->format == EXG_FMT_BAM) return kPayloadNone;  // (a BAM segment is never mirrored: its strings are produced into a side buffer)
     if (r->format == EXG_FMT_FASTA) {
         static const bool fasta_whole = getenv("EXG_FASTA_WHOLE_TEXT") != nullptr;  // (A/B: the decoded text behind the scan)
         return (r->want_cols & 3ull) && !fasta_whole ? kPayloadCompact : kPayloadNone;
@@ -435,6 +437,7 @@ int open_next_file(exg_reader *r) {
     r->range_hi = r->src ? ~0ull : blk->n;  // (a decoded stream ends where its source says so)
     r->shard_first = false;
     r->data_base = r->file_pos;  // 0, or the end of the VCF header
+    if (r->format == EXG_FMT_BAM) return bam_open_file(r);  // (the header, from the front of the decoded stream; one shard)
     // Which scan first: from the first MiB behind the header, which is mapped anyway (a decoded stream has no bytes on the host: its
     // first batches' results decide, as before).  The batches' result flags correct the choice either way.
     if (!r->src && blk->p && blk->n > r->file_pos && !getenv("EXG_NO_ALGO_HINT"))
@@ -507,6 +510,7 @@ int advance_batch(exg_reader *r, bool *end) {
             // rows before the failing record have been handed out; now surface the error
             std::string msg = std::string(exg_parse_error_string(r->pending_error)) + " at byte " + std::to_string(r->pending_error_offset) + " of " +
                               r->files[r->file_idx - 1];
+            if (!r->pending_error_text.empty()) msg.swap(r->pending_error_text), r->pending_error_text.clear();
             r->pending_error = 0;
             r->batch.reset();
             return fail(r, EXG_E_PARSE, msg);
@@ -601,6 +605,7 @@ int next_batch(exg_reader *r, bool count_only, uint64_t *n_records_out) {
     r->batch_row = 0;
     if (int trc = truncated_while_read(r)) return trc;
     if (r->file_done) return EXG_OK;  // (opening the file found nothing of this shard's in it)
+    if (r->format == EXG_FMT_BAM) return bam_next_batch(r, count_only, n_records_out);
     uint64_t want = r->device_batch_bytes;
     double t_batch = now_s();
     for (;;) {

@@ -55,7 +55,7 @@ using namespace exg_rd;
 // can a file of this format / compression be read as byte-range shards?  (text; BGZF — FEXTRA with a 'BC' subfield in the
 // first member — by members; zstd with several frames by frames)
 static bool file_is_shardable(const std::string &f, const std::string &fmt_lower, Compression comp) {
-    (void)fmt_lower;
+    if (fmt_lower == "bam") return false;  // (one file is one shard: sharding BAM by BGZF members is a follow-up)
     if (comp == kNone) return true;
     if (comp == kZstd) {
         // by frames: worth it when the file has several (pzstd, the seekable format; the zstd CLI writes one) — the walk over
@@ -206,6 +206,7 @@ extern "C" ReplacementScanResult replacement_scan(const char *uri) {
     if (ext == "fasta" || ext == "fa" || ext == "fna") res.file_type = "FASTA";
     if (ext == "fastq" || ext == "fq") res.file_type = "FASTQ";
     if (ext == "vcf") res.file_type = "VCF";
+    if (ext == "bam") res.file_type = "BAM";
     return res;
 }
 

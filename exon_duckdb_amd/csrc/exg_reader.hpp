@@ -320,9 +320,9 @@ struct Batch {  // host vectors of one device batch, shared by its chunks
     std::shared_ptr<PinnedBlock> file;
     HostArena host;
     int n_cols = 0;
-    void *cols[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    uint32_t elem[9] = {16, 16, 16, 16, 16, 16, 16, 16, 16};  // bytes per row
-    void *validity[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // NULL => all valid
+    void *cols[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    uint32_t elem[10] = {16, 16, 16, 16, 16, 16, 16, 16, 16, 16};  // bytes per row
+    void *validity[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // NULL => all valid
     void *payload = nullptr;  // FASTA: compacted sequences
     uint64_t n_rows = 0;
     uint64_t seq = 0;          // which device batch of its reader this is (exg_chunk.batch_no)
@@ -494,12 +494,15 @@ struct exg_reader {
     uint64_t batch_seq = 0;  // device batches handed out so far (all files)
     uint32_t pending_error = 0;  // parse error to raise once the rows before it have been handed out
     uint64_t pending_error_offset = 0;
+    std::string pending_error_text;  // read_bam_file_records: the whole message (it names the record's ordinal)
 
     // Arrow mode (new_reader): the columns stay on the device and `arrow_emit` turns them into Arrow buffers
     int (*arrow_emit)(exg_reader *, const exg_rd::ScanCtx &) = nullptr;
     std::shared_ptr<void> arrow_state;
     // chunk mode, VCF: the INFO / FORMAT keys of the header, the schema trees, the emitter's device arena
     std::shared_ptr<void> nested_state;
+    // read_bam_file_records: the header's reference names (host + device) and the scan's buffers (exg_rd_bam.cpp)
+    std::shared_ptr<void> bam_state;
 
     void free_device();
     exg_reader();  // (out of line: `src` is a pointer to a type this header only declares)

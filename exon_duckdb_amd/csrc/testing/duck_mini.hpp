@@ -128,7 +128,7 @@ struct Value {
             }
             return out + "'";
         }
-        if (type == LogicalTypeId::BIGINT) return std::to_string(i);
+        if (type == LogicalTypeId::BIGINT || type == LogicalTypeId::INTEGER) return std::to_string(i);
         char buf[64];
         snprintf(buf, sizeof buf, "%.9g", f);
         std::string t = buf;

@@ -241,7 +241,7 @@ static std::unique_ptr<TableFilter> build_filter(const exon_tf_filter_node *node
             Value v;
             v.type = (LogicalTypeId)nd.const_type;
             v.str = nd.constant ? nd.constant : "";
-            if (v.type == LogicalTypeId::BIGINT) v.i = strtoll(v.str.c_str(), nullptr, 10);
+            if (v.type == LogicalTypeId::BIGINT || v.type == LogicalTypeId::INTEGER) v.i = strtoll(v.str.c_str(), nullptr, 10);
             if (v.type == LogicalTypeId::FLOAT) v.f = strtod(v.str.c_str(), nullptr);
             return std::make_unique<ConstantFilter>((ExpressionType)nd.cmp, v);
         }

@@ -251,3 +251,85 @@ class FastaScan:
         cols = [c[:n].cpu().numpy().view(np.uint8).reshape(n, 16) for c in self.cols]
         words = self.validity[: (n + 63) // 64].cpu().numpy().view(np.uint64)
         return cols, words, self.payload[:payload_bytes].cpu().numpy()
+
+
+class BamScan:
+    """exg_bam_scan on decoded BAM records resident in HBM (d_input[0] is a record start): buffers for all ten columns, the
+    side buffer and the reference table; rows() decodes what came back into the tuples tests compare (bytes / int / None)."""
+    SIDE_BASE, REF_BASE = 1 << 44, 1 << 45
+    INT_COLS, NULLABLE = (1, 3, 4), (2, 3, 4, 5, 7)
+
+    def __init__(self, n_bytes, refs=(), capacity_records=None, side_capacity=None, device="cuda"):
+        torch = _torch()
+        self.lib = load_library()
+        self.n_bytes = n_bytes
+        self.capacity = int(capacity_records if capacity_records is not None else n_bytes // 36 + 2)
+        cap = max(self.capacity, 1)
+        self.cols = [torch.empty((cap,), dtype=torch.int32, device=device) if c in self.INT_COLS else
+                     torch.empty((cap, 2), dtype=torch.int64, device=device) for c in range(abi.EXG_BAM_COLUMNS)]
+        self.validity = {c: torch.empty(((cap + 63) // 64,), dtype=torch.int64, device=device) for c in self.NULLABLE}
+        self.side_capacity = int(side_capacity if side_capacity is not None else 3 * n_bytes + 64)
+        self.side = torch.empty(max(self.side_capacity, 1), dtype=torch.uint8, device=device)
+        self.ref_names = b"".join(name for name, _ in refs)
+        offs = [0]
+        for name, _ in refs:
+            offs.append(offs[-1] + len(name))
+        self.n_ref = len(refs)
+        self.d_ref_names = upload(self.ref_names)
+        self.d_ref_offsets = torch.tensor(offs, dtype=torch.int64, device=device)
+        self.ws_bytes = int(self.lib.exg_scan_workspace_bytes(abi.EXG_FMT_BAM, n_bytes))
+        self.ws = torch.empty((self.ws_bytes + 255) // 8, dtype=torch.int64, device=device)
+        self.result = torch.zeros(8, dtype=torch.int64, device=device)
+        self.args = abi.BamScanArgs()
+
+    def launch(self, d_input, n_bytes=None, flags=abi.EXG_F_EOF, columns=0):
+        a = self.args
+        a.d_input = d_input.data_ptr() if hasattr(d_input, "data_ptr") else d_input
+        a.n_bytes = self.n_bytes if n_bytes is None else n_bytes
+        a.flags, a.n_ref, a.columns = flags, self.n_ref, columns
+        a.d_ref_names, a.d_ref_offsets, a.ref_names_base = self.d_ref_names.data_ptr(), self.d_ref_offsets.data_ptr(), self.REF_BASE
+        for c in range(abi.EXG_BAM_COLUMNS):
+            a.d_columns[c] = self.cols[c].data_ptr()
+            a.d_validity[c] = self.validity[c].data_ptr() if c in self.validity else None
+        a.d_side, a.side_capacity, a.side_base = self.side.data_ptr(), self.side_capacity, self.SIDE_BASE
+        a.capacity_records = self.capacity
+        a.d_workspace, a.workspace_bytes = self.ws.data_ptr(), self.ws_bytes
+        a.d_result = self.result.data_ptr()
+        a.stream = stream_ptr().value
+        check(self.lib.exg_bam_scan(C.byref(a)))
+
+    def fetch(self):
+        r = abi.BamScanResult()
+        check(self.lib.exg_fetch_result(C.c_void_p(self.result.data_ptr()), stream_ptr(), C.cast(C.byref(r), C.POINTER(abi.ScanResult))))
+        return r
+
+    def rows(self, n, side_bytes):
+        """the first n rows as tuples of the ten columns"""
+        side = self.side[:side_bytes].cpu().numpy().tobytes()
+        out = []
+        for c in range(abi.EXG_BAM_COLUMNS):
+            valid = None
+            if c in self.validity:
+                words = self.validity[c][: (n + 63) // 64].cpu().numpy().view(np.uint64)
+                valid = np.unpackbits(words.view(np.uint8), bitorder="little")[:n]
+            if c in self.INT_COLS:
+                vals = self.cols[c][:n].cpu().numpy().tolist()
+            else:
+                raw = self.cols[c][:n].cpu().numpy().view(np.uint8).reshape(n, 16)
+                lens = raw[:, :4].copy().view(np.uint32).reshape(n)
+                ptrs = raw[:, 8:16].copy().view(np.uint64).reshape(n)
+                vals = []
+                for i in range(n):
+                    ln = int(lens[i])
+                    if ln <= 12:
+                        vals.append(raw[i, 4:4 + ln].tobytes())
+                        continue
+                    p = int(ptrs[i])
+                    if p >= self.REF_BASE:
+                        vals.append(self.ref_names[p - self.REF_BASE:p - self.REF_BASE + ln])
+                    else:
+                        s = side[p - self.SIDE_BASE:p - self.SIDE_BASE + ln]
+                        assert len(s) == ln and s[:4] == raw[i, 4:8].tobytes(), "string_t outside the side buffer, or a wrong prefix"
+                        vals.append(s)
+            out.append([v if valid is None or valid[i] else None for i, v in enumerate(vals)])
+        return list(zip(*out))

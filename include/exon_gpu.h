@@ -78,6 +78,13 @@ extern "C" {
 #define EXG_PE_FIELD_TOO_LONG 12      /* a field exceeds 2^32-1 bytes (string_t length is u32) */
 #define EXG_PE_VCF_INFO 13            /* an INFO value does not parse as the type its ##INFO line declares */
 #define EXG_PE_VCF_FORMAT 14          /* a sample value does not parse as the type its ##FORMAT line declares */
+#define EXG_PE_BAM_BLOCK_SIZE 15      /* BAM: block_size < 32 (the fixed fields alone are 32 bytes) */
+#define EXG_PE_BAM_TRUNCATED 16       /* BAM: a record runs past the end of the stream */
+#define EXG_PE_BAM_READ_NAME 17       /* BAM: l_read_name = 0, or the name is not NUL-terminated */
+#define EXG_PE_BAM_REFERENCE_ID 18    /* BAM: refID / next_refID is not in [-1, n_ref) */
+#define EXG_PE_BAM_FIELD_LENGTHS 19   /* BAM: the declared field lengths do not fit in block_size */
+#define EXG_PE_BAM_CIGAR_OP 20        /* BAM: a CIGAR operation code above 8 */
+#define EXG_PE_BAM_QUALITY 21         /* BAM: a quality byte above 93 (and the qualities are not all 0xFF = absent) */
 
 /* ---- duckdb::string_t, bit-for-bit (v0.8.1 duckdb/common/types/string_type.hpp)
  * length <= 12: bytes inlined, zero padded.  Otherwise 4-byte prefix + pointer.
@@ -100,6 +107,7 @@ typedef union exg_string_t {
 #define EXG_FMT_FASTA 1
 #define EXG_FMT_FASTQ 2
 #define EXG_FMT_VCF 3
+#define EXG_FMT_BAM 4 /* reader level + exg_bam_scan; the chunk boundary only (new_reader refuses it) */
 
 /* ---- scan flags ------------------------------------------------------------ */
 #define EXG_F_BOF 1u /* a line starts at d_input[0] (start of file, or a record-aligned batch) */
@@ -217,6 +225,60 @@ typedef struct exg_fasta_scan_args {
     void *stream;
 } exg_fasta_scan_args;
 
+/* BAM (SAM v1 §4.2): the DECODED bytes of a BAM file behind its header — block_size-prefixed binary records without a
+ * delimiter — in HBM, d_input[0] being a record start.  Ten columns (the reference's read_bam_file_records, order pinned by
+ * test_bam_record_scan.test:5-17; types as exon 0.2.x is recalled to declare them — INTEGRATION.md):
+ *   0 name VARCHAR, 1 flag INTEGER, 2 reference VARCHAR?, 3 start INTEGER?, 4 end INTEGER?, 5 mapping_quality VARCHAR?,
+ *   6 cigar VARCHAR, 7 mate_reference VARCHAR, 8 sequence VARCHAR, 9 quality_score VARCHAR
+ * Three of them do not exist as text in the file and are PRODUCED into a side buffer (d_side): the sequence (4-bit packed),
+ * the qualities (raw bytes, +33) and the CIGAR (uint32 operations, rendered as <len><op>); the name is copied there too.
+ * A string_t of more than 12 bytes points at side_base + its offset in d_side; reference / mate_reference point into the
+ * table of reference names (ref_names_base + d_ref_offsets[refID]).  The CIGAR is rendered as stored: the CG:B,I
+ * convention for more than 65535 operations is not resolved.  Trailing aux fields are skipped unread.
+ *
+ * Records are found by speculation over fixed tiles (a plausible record header with a plausible successor) and a stitch
+ * that accepts a tile only when the chain from d_input[0] lands exactly on its speculated entry; every other tile the chain
+ * enters is walked again from the true entry (tiles_rewalked).  The rows are exactly the serial chain's, whatever the
+ * bytes look like.
+ *
+ * Without EXG_F_EOF the tail behind the last complete record is left to the next batch (consumed_bytes); with it, a tail is
+ * EXG_PE_BAM_TRUNCATED.  EXG_F_NO_STORE: records are found and validated, nothing else is written.  The rows in front of the
+ * first failing record are produced (n_records = its ordinal).  Synchronises the stream (twice: the row count and the
+ * side-buffer size come back to the host between the passes). */
+typedef struct exg_bam_scan_result { /* 64 bytes, written by the device */
+    uint64_t n_records;      /* rows produced: the complete records of the buffer, or those in front of the first error */
+    uint64_t consumed_bytes; /* offset just past the last complete record (where the next batch begins) */
+    uint64_t side_bytes;     /* bytes of d_side the rows need (> side_capacity with EXG_RF_CAPACITY: nothing was written) */
+    uint64_t error_record;   /* ordinal (within this buffer) of the first failing record */
+    uint64_t error_offset;   /* its byte offset in d_input */
+    uint32_t error_code;     /* EXG_PE_BAM_* */
+    uint32_t flags;          /* EXG_RF_CAPACITY: more records than capacity_records, or side_bytes > side_capacity */
+    uint64_t tiles;          /* tiles of 32 KiB the buffer was cut into */
+    uint64_t tiles_rewalked; /* tiles whose speculated entry was not the chain's: walked again from the true entry */
+} exg_bam_scan_result;
+
+#define EXG_BAM_COLUMNS 10
+typedef struct exg_bam_scan_args {
+    const void *d_input; /* device, any alignment */
+    uint64_t n_bytes;
+    uint32_t flags;      /* EXG_F_EOF | EXG_F_NO_STORE */
+    int32_t n_ref;       /* references in the file's header */
+    uint64_t columns;    /* bit c: produce column c (0 = all); every record is validated whatever is selected */
+    const uint8_t *d_ref_names;    /* device: the reference names, closed up (no NULs) */
+    const uint64_t *d_ref_offsets; /* device: n_ref + 1 offsets into d_ref_names */
+    uint64_t ref_names_base;       /* string_t.ptr of a reference name = ref_names_base + its offset */
+    void *d_columns[EXG_BAM_COLUMNS];      /* device: exg_string_t[capacity_records] (VARCHAR) / int32_t[] (INTEGER); NULL = not produced */
+    uint64_t *d_validity[EXG_BAM_COLUMNS]; /* device: ceil(capacity / 64) words for columns 2, 3, 4, 5, 7 (when produced) */
+    uint8_t *d_side;        /* device, side_capacity bytes */
+    uint64_t side_capacity;
+    uint64_t side_base;     /* string_t.ptr = side_base + offset in d_side */
+    uint64_t capacity_records;
+    void *d_workspace;      /* device, exg_scan_workspace_bytes(EXG_FMT_BAM, n_bytes), 256-byte aligned */
+    uint64_t workspace_bytes;
+    exg_bam_scan_result *d_result; /* device, 64 bytes */
+    void *stream;
+} exg_bam_scan_args;
+
 /* ---- library / device ------------------------------------------------------ */
 int exg_abi_version(void);
 /* Number of visible HIP devices, or EXG_E_NO_DEVICE. Does not initialise a context. */
@@ -231,6 +293,8 @@ uint64_t exg_scan_workspace_bytes(int format, uint64_t n_bytes);
 int exg_fastq_scan(const exg_fastq_scan_args *args);
 int exg_vcf_scan(const exg_vcf_scan_args *args);
 int exg_fasta_scan(const exg_fasta_scan_args *args);
+/* Synchronises args->stream (see exg_bam_scan_args).  The 64-byte result comes back with exg_fetch_result, like the others'. */
+int exg_bam_scan(const exg_bam_scan_args *args);
 /* Synchronising copy of the 64-byte result to the host. */
 int exg_fetch_result(const exg_scan_result *d_result, void *stream, exg_scan_result *out);
 /* '\n' count of d_input[begin,end) into *d_count (device u64); used for the shard phase exchange. */
@@ -383,7 +447,9 @@ typedef struct exg_reader exg_reader;
 
 typedef struct exg_open_args {
     const char *path;        /* local file or directory (the reference lists directories: test_fasta_scan.test:55-59) */
-    const char *file_format; /* "fasta" | "fastq" | "vcf" (the reference's file_type strings, exon_extension.cpp:50,51,55) */
+    const char *file_format; /* "fasta" | "fastq" | "vcf" | "bam" (the reference's file_type strings, exon_extension.cpp:47-58).  A BAM
+                              * file is always read as gzip members (BGZF), whatever `compression` says, and as ONE shard
+                              * (shard_count > 1: EXG_E_UNSUPPORTED); "sam" is refused */
     const char *compression; /* NULL = infer from extension like arrow_reader.rs:60-75; "gzip","zstd","uncompressed",... */
     uint64_t batch_rows;     /* rows per chunk; 0 => EXG_VECTOR_SIZE */
     int device;              /* HIP device ordinal */
@@ -510,7 +576,9 @@ typedef struct exg_reader_stats {
                                   * point where their vectors start for the host (exg_vcf_nested.hpp) */
     uint64_t host_vector_bytes;  /* ABI 9: bytes of column vectors (flat and nested, validity included) sent to the host so far —
                                   * what a scan INTO DataChunks pays on the D2H link next to a decoded input's own bytes */
-    uint64_t reserved[3];
+    uint64_t bam_tiles;          /* read_bam_file_records: tiles of all device batches so far (exg_bam_scan_result.tiles) ... */
+    uint64_t bam_tiles_rewalked; /* ... and those that were walked a second time (words that were reserved: the layout is ABI 9's) */
+    uint64_t reserved[1];
 } exg_reader_stats;
 int exg_reader_stats_of(exg_reader *r, exg_reader_stats *out);
 /* Device buffers, pinned host blocks and HIP streams of closed readers are recycled process-wide (size classes, at most
@@ -521,7 +589,7 @@ void exg_close(exg_reader *r);
 /* ---- (3) reference-FFI compatible ------------------------------------------------------ */
 /* exon/include/rust.hpp:11-13 */
 typedef struct ReplacementScanResult {
-    const char *file_type; /* "FASTA" | "FASTQ" | "VCF" (static storage) or NULL */
+    const char *file_type; /* "FASTA" | "FASTQ" | "VCF" | "BAM" (static storage) or NULL */
 } ReplacementScanResult;
 /* exon/include/rust.hpp:48, rust/src/arrow_reader.rs:173-197: last extension, skipping one
  * compression extension (gz, gzip, zst, zstd, bz2, bzip2, xz). */
@@ -580,7 +648,7 @@ typedef struct ReaderResult {
  * the `filters` predicate and the Arrow buffers themselves (offsets, values, validity) are produced
  * on the device; the host only copies them back and wires the ArrowArray structs.
  *   compression: NULL = by extension (:60-75), else DataFusion's FileCompressionType names (:77-91)
- *   file_format: "fasta" | "fastq" | "vcf"
+ *   file_format: "fasta" | "fastq" | "vcf" ("bam" is refused: BAM is served at the chunk boundary, exg_open, only)
  *   filters:     NULL / "" or the predicate text FilterToString renders (module.cpp:158-214):
  *                <column> (= | != | <> | < | <= | > | >=) <literal>, <column> IS [NOT] NULL, AND, OR
  *                with SQL precedence; it is applied as `SELECT * FROM exon_table WHERE <filters>` (:125-141). */
