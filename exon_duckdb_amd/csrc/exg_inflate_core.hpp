@@ -16,7 +16,9 @@ struct InflateMember {
 
 struct InflateStatus {
     unsigned int code;             // 0 ok; 1 bad block type / stored len; 2 bad code lengths; 3 bad symbol or distance;
-                                   // 4 output overflow; 5 input exhausted; 6 not text (InflateJob::text_probe)
+                                   // 4 output overflow; 5 input exhausted; 6 not text (InflateJob::text_probe).
+                                   // 5 takes precedence: a decode that consumed a bit behind comp_size reports 5 whatever it
+                                   // made of those bits (any other code means all the bits read were the stream's own)
     unsigned int pad;
     unsigned long long produced;   // bytes written
     unsigned long long consumed;   // compressed bytes consumed (from comp_off, byte aligned after the final block)
@@ -224,7 +226,8 @@ __device__ __forceinline__ uint32_t getbits(L &s, BitIn &br, uint32_t n, uint32_
 }
 
 // Build one decode table from code lengths lens[0..n): LUT (primary `bits`), sorted symbols, counts.
-// Returns false when the lengths are over-subscribed or incomplete (except the single-code cases zlib allows).
+// Returns false when the lengths are over-subscribed or incomplete.  single_ok: one code of length 1 may stand alone (zlib
+// allows it for the literal/length and the distance code, RFC 1951 3.2.7; never for the code-length code).
 // kFill: what the slots of codes longer than the table (and of unused codes) hold
 struct EncPlain {  // (symbol << 4) | length
     static constexpr uint16_t kFill = 0;
@@ -264,7 +267,7 @@ __device__ __forceinline__ void dist_base_extra(uint32_t sym, uint32_t *base, ui
 
 template <class Lut, class Enc, class Sorted>
 __device__ inline bool build_table(const uint8_t *lens, uint32_t n, Lut *lut, uint32_t bits, Sorted *sorted, uint16_t *count,
-                            uint32_t lane, Enc enc) {
+                            uint32_t lane, Enc enc, bool single_ok = true) {
     for (uint32_t e = lane; e < (1u << bits); e += 64) lut[e] = Enc::kFill;
     // all the lengths (n <= 320) are read before anything is written: `sorted` may lie over `lens`
     uint32_t lv[5];
@@ -304,7 +307,7 @@ __device__ inline bool build_table(const uint8_t *lens, uint32_t n, Lut *lut, ui
         if (lane == (uint32_t)L) count[L] = (uint16_t)(L ? cnt[L] : 0);
     if (bad) return false;
     // incomplete codes are only legal with a single code of length 1 (zlib / puff behaviour)
-    if (left > 0 && !(off == 1 && cnt[1] == 1) && off != 0) return false;
+    if (left > 0 && !(single_ok && off == 1 && cnt[1] == 1) && off != 0) return false;
     // per symbol: canonical code = first[len] + rank among equal lengths, in symbol order
     uint32_t run[16];
 #pragma unroll
@@ -572,7 +575,7 @@ __device__ __forceinline__ void inflate_job(InflateLdsT<SYM, RING> &s, const uin
                 }
                 // the code-length code reuses the distance table storage (7-bit codes, 19 symbols)
                 uint16_t *cl_lut = s.dist_lut;  // borrowed until the real tables are built
-                if (!build_table(s.lens, 19, cl_lut, 7, s.dist_sorted, s.dist_count, lane, EncPlain())) {
+                if (!build_table(s.lens, 19, cl_lut, 7, s.dist_sorted, s.dist_count, lane, EncPlain(), false)) {
                     err = 2;
                     break;
                 }
@@ -621,6 +624,10 @@ __device__ __forceinline__ void inflate_job(InflateLdsT<SYM, RING> &s, const uin
                         s.lens[i] = lv[k];
                     else if (i < nlit + ndist)
                         s.lens[288 + (i - nlit)] = lv[k];
+                }
+                if (sgpr(s.lens[256]) == 0) {  // no code for end-of-block: the block could never end
+                    err = 2;
+                    break;
                 }
             }
             if (!build_table(s.lens + 288, ndist, s.dist_lut, kDistBits, s.dist_sorted, s.dist_count, lane, EncDist()) ||
@@ -735,6 +742,21 @@ __device__ __forceinline__ void inflate_job(InflateLdsT<SYM, RING> &s, const uin
                         advance_pad = pad_s;
                     }
 #endif
+                    // The step's windows reach the end of the input (a member's last step or two): a token that needs bits from
+                    // behind it ends the step there, so that nothing decoded from the padding is placed, counted against the
+                    // output's bound or taken for an error of the stream
+                    // (32-bit and scalar: the byte the step starts in is what the check at the loop's head compared already)
+                    const uint32_t step_byte = (uint32_t)(br.bitpos >> 3);
+                    const bool near_end = step_byte + (64u * NW + 48u) / 8u + 1u > br.limit;
+                    // (only the production shape, EMIT >= 2, does this; the EMIT 0 / 1 A/B partners still place what the padding
+                    // decodes to and count it against out_cap: on input cut short only the override at the job's end, code 5,
+                    // makes them agree)
+                    int32_t bits_left = 0;
+                    if (near_end) {
+                        bits_left = (int32_t)((br.limit - step_byte) * 8u) - (int32_t)((uint32_t)br.bitpos & 7u);  // -79 .. 311: limit - step_byte is -9 .. 38 here
+#pragma unroll
+                        for (int k = 0; k < NW; k++) stop_mask[k] |= __ballot((int32_t)(64u * k + lane + tl[k]) > bits_left);
+                    }
                     // The real chain from offset 0, window after window.  The walk is the scalar unit's main load (~15 tokens
                     // per window), so its loop is written out: the position is kept as cur - 64 (mod 2^32; bit set and lane
                     // select use the low six bits), so that the add's carry is the exit test — three scalar instructions and
@@ -1009,9 +1031,16 @@ __device__ __forceinline__ void inflate_job(InflateLdsT<SYM, RING> &s, const uin
                                 e_s = __builtin_amdgcn_readlane(e[k], sl);
                                 de_s = __builtin_amdgcn_readlane(de[k], sl);
                             }
+                        // (its bits, from its entries as tl[] above: scalar work, and only a step at the input's end asks)
+                        const uint32_t tl_s = !(e_s & 0x8000u) ? (e_s & 15u)
+                                                               : (e_s & 15u) + ((e_s >> 4) & 7u) + (de_s & 15u) +
+                                                                     __builtin_elementwise_sub_sat((de_s >> 5) & 15u, 1u);
                         if (e_s & 0x8000u ? dist_is_long(de_s) : lit_is_long(e_s)) {
                             advance = stop_pos;  // a code longer than the tables: decoded by every lane uniformly below
                             slow_token = true;
+                        } else if (near_end && (int32_t)(stop_pos + tl_s) > bits_left) {
+                            err = 5;  // the token is cut off by the end of the input
+                            break;
                         } else if (!(e_s & 0x8000u) && (e_s & 0x3000u) == 0x1000u) {
                             advance = stop_pos + (e_s & 15u);
                             eob = true;
@@ -1232,6 +1261,9 @@ __device__ __forceinline__ void inflate_job(InflateLdsT<SYM, RING> &s, const uin
                 }
             }
         }
+        // whatever a decode made of bits behind the end of its input (zero padding, a neighbour's bytes), it ran out of input:
+        // a final block cut short must not pass for a whole one, nor padding for a bad symbol
+        if (((br.bitpos + 7) >> 3) > br.limit) err = 5;
         // tail: the bytes after the last full segment
         if (!err && d_out) {
             for (uint32_t i = flushed + lane; i < pos; i += 64) d_out[mb.out_off + i] = s.win[i & kRingMask];

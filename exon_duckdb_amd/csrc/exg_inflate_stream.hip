@@ -226,11 +226,17 @@ __global__ __launch_bounds__(256) void k_win_apply(const uint16_t *__restrict__ 
 
 // ---- 5. resolve ------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_resolve(const ChunkOut *__restrict__ chunks, const uint8_t *__restrict__ windows,
-                                                 uint8_t *__restrict__ d_out, uint32_t n_chunks, uint32_t *bad, uint32_t have_window0) {
+                                                 uint8_t *__restrict__ d_out, uint32_t n_chunks, uint32_t *bad, uint32_t have_window0,
+                                                 unsigned long long front_reserve) {
     // blockIdx.y = chunk; 16 symbols per thread -> one 16-byte store when the destination is aligned
     const uint32_t c = blockIdx.y;
     const ChunkOut ch = chunks[c];
     const uint8_t *w = windows + (size_t)c * 32768;
+    // Without a window in front of the call only the bytes the chunks before this one produced precede it: window byte i is
+    // real from 32768 - that many on.  A marker below points in front of the stream's first byte (any marker of the first
+    // chunk; in a later chunk when little was produced so far, e.g. behind a run of empty stored blocks)
+    const unsigned long long in_front = ch.out_off - front_reserve;
+    const uint32_t first_real = have_window0 || in_front >= 32768 ? 0u : 32768u - (uint32_t)in_front;
     for (unsigned long long g = (unsigned long long)blockIdx.x * 256 + threadIdx.x; g * 16 < ch.n; g += (unsigned long long)gridDim.x * 256) {
         const unsigned long long i0 = g * 16;
         uint8_t b[16];
@@ -239,7 +245,7 @@ __global__ __launch_bounds__(256) void k_resolve(const ChunkOut *__restrict__ ch
         for (uint32_t k = 0; k < 16; k++) {
             uint16_t sy = k < cnt ? ch.sym[i0 + k] : (uint16_t)0;
             b[k] = sy & 0x8000u ? w[sy & 0x7FFFu] : (uint8_t)sy;
-            if ((sy & 0x8000u) && c == 0 && !have_window0) atomicOr(bad, 1u);  // nothing precedes a member's first chunk
+            if ((sy & 0x8000u) && (sy & 0x7FFFu) < first_real) atomicOr(bad, 1u);  // a distance before the start of the output
         }
         uint8_t *dst = d_out + ch.out_off + i0;
         if (cnt == 16 && (((uintptr_t)dst) & 15) == 0) {
@@ -690,7 +696,7 @@ static int inflate_stream_impl(const void *d_comp_v, uint64_t comp_off, uint64_t
     }
     if (n)
         hipLaunchKernelGGL(k_resolve, dim3(256, n), dim3(256), 0, stream, (const ChunkOut *)d_co.p, (const uint8_t *)d_win.p,
-                           (uint8_t *)d_out, n, (uint32_t *)d_bad.p, ra.have_window ? 1u : 0u);
+                           (uint8_t *)d_out, n, (uint32_t *)d_bad.p, ra.have_window ? 1u : 0u, (unsigned long long)reserve);
     if (ra.d_window)  // what the next round of this member has in front of it
         hipLaunchKernelGGL(k_win_tail, dim3(32), dim3(256), 0, stream, (const uint8_t *)d_out + reserve, (unsigned long long)total,
                            ra.have_window ? (const uint8_t *)d_win.p : (const uint8_t *)nullptr, (uint8_t *)ra.d_window);
