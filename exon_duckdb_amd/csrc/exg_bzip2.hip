@@ -480,7 +480,11 @@ __global__ void k_chain(const uint8_t *comp, uint64_t n, const unsigned long lon
             }
             if (b + 4 > n) {
                 if (!final_window) break;
-                status = first ? kErrNotBzip2 : kOk;  // (bytes behind a stream that are no stream are ignored, like bz2.decompress)
+                // bytes behind a stream that are no stream are ignored, like bz2.decompress; the first bytes of a stream
+                // header ("B", "BZ", "BZh") are a stream cut short, as bz2.decompress and the bzip2 program read them
+                bool head = true;
+                for (uint64_t i = b; i < n; i++) head = head && comp[i] == (i == b ? 'B' : i == b + 1 ? 'Z' : 'h');
+                status = first ? kErrNotBzip2 : head ? kErrTruncated : kOk;
                 done = 1;
                 break;
             }
@@ -542,7 +546,7 @@ __global__ void k_chain(const uint8_t *comp, uint64_t n, const unsigned long lon
     res->n_blocks = m;
     res->n_events = ne;
     res->status = status;
-    res->err_block = err_block;
+    res->err_block = status ? m : err_block;  // (a refusal is of the block behind the m chained ones, whoever found it)
     res->bit_end = p;
     res->at_header = at_header;
     res->level = level;

@@ -7,6 +7,7 @@
 // is read again by the next round from its block's first bit.  A round holds, per block, its BWT column and LF vector
 // (5 bytes per byte of BWT input) beside its output: under EXG_DEVICE_MEM_CAP_MB the rounds shrink to one block.
 #include <errno.h>
+#include <stdlib.h>
 #include <string.h>
 #include <unistd.h>
 
@@ -24,7 +25,9 @@ namespace {
 class Bzip2Producer : public SegmentProducer {
 public:
     Bzip2Producer(exg_reader *r, int fd, uint64_t n, uint64_t target, const std::string &path, uint64_t reserve)
-        : device_(r->device), fd_(fd), n_(n), cap_(r->mem_cap), target_(round_out_bytes(target, 128u << 10, r->mem_cap != 0)), path_(path), reserve_((reserve + 15) & ~15ull) {}
+        : device_(r->device), fd_(fd), n_(n), cap_(r->mem_cap), target_(round_out_bytes(target, 128u << 10, r->mem_cap != 0)), path_(path), reserve_((reserve + 15) & ~15ull) {
+        if (const char *e = getenv("EXG_BZIP2_WINDOW_BYTES")) window_bytes_ = std::max<uint64_t>(16, strtoull(e, nullptr, 10));
+    }
     int run(SegmentSink &sink, std::string *err) override;
 
 private:
@@ -32,6 +35,7 @@ private:
     uint64_t n_, cap_, target_;
     std::string path_;
     uint64_t reserve_;
+    uint64_t window_bytes_ = 0;  // 0: sized from the blocks seen so far
 };
 
 int Bzip2Producer::run(SegmentSink &sink, std::string *err) {
@@ -64,7 +68,8 @@ int Bzip2Producer::run(SegmentSink &sink, std::string *err) {
         uint64_t max_blocks = std::max<uint64_t>(1, target_ / slot);
         if (cap_) max_blocks = std::max<uint64_t>(1, std::min<uint64_t>(max_blocks, (cap_ / 3) / (slot * 53 / 10)));
         uint64_t want = est_block ? max_blocks * est_block + est_block / 2 + (64u << 10) : (cap_ ? (1u << 20) : std::max<uint64_t>(4u << 20, target_ / 3));
-        want = std::max<uint64_t>(want, 256u << 10) * grow;
+        if (window_bytes_) want = window_bytes_ * grow;  // (EXG_BZIP2_WINDOW_BYTES, tests: windows smaller than a block)
+        else want = std::max<uint64_t>(want, 256u << 10) * grow;
         const uint64_t len = std::min<uint64_t>(want, n_ - std::min(n_, lo));
         const size_t wcap = (size_t)len + 128;
         if (!d_win.p || d_win.sz < wcap) {
