@@ -96,8 +96,11 @@ __device__ __forceinline__ uint32_t wave_incl_sum(uint32_t v) {
 }
 
 // inclusive wave64 prefix sum on the VALU (DPP row shifts + row broadcasts: no LDS traffic, unlike __shfl_up).
-// Not a free win: in the fused FASTQ kernel, which is VALU-bound with an idle LDS pipeline, it measured 4 % SLOWER
-// than the ds_bpermute form above (A/B on one box); it pays where the LDS pipeline is the busy one (FASTA tiles).
+// Judge it by the register report of the kernel it goes into, not by the instruction count.  An early form of the fused FASTQ
+// kernel (serialised loads, more spills) measured 4 % SLOWER with it than with the ds_bpermute form above.  Today's lean scan
+// takes its per-half rank scan from here: 80 -> 77 VGPRs, 40 -> 28 spilled SGPRs, 18 ds_bpermute fewer, and 1.5 % faster in an
+// A/B on one box (2.1823 -> 2.1499 ms per 10 GB, 3.7 x the spread; profiles/fastq_input_end_ab.md).  It also pays where the
+// LDS pipeline is the busy one (FASTA tiles).
 __device__ __forceinline__ uint32_t wave_incl_sum_dpp(uint32_t v) {
     v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false);  // row_shr:1
     v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false);  // row_shr:2

@@ -435,7 +435,7 @@ __global__ __launch_bounds__(kThreads, kMode == kLean ? F::kMinWavesPerSimd : (k
 
     // ---- loads: kHalves x 4 strided 16 B chunks per thread, all in flight at once (+ window by wave 3) ------
     // ONE load sequence for every super-tile: the last one, which the input may end in, reads the chunks that lie past the end
-    // from the input's last chunk instead (in bounds; they are zeroed below).  With a sequence of its own for that super-tile
+    // from the input's last chunk instead (in bounds; their newline bits are cleared behind the classification).  With a sequence of its own for that super-tile
     // ("off < n_pad ? load : 0") the two met in kHalves x 4 phis, and the register allocator resolved them with copies BETWEEN the
     // loads of the common one: s_waitcnt vmcnt(1) + v_mov after every other load — two loads in flight per wave, not twelve
     // (the ISA of the lean FASTQ scan; A/B in one box: 2.247 -> 2.171 ms per 10 GB).  The address is a uniform base + a 32-bit
@@ -459,19 +459,37 @@ __global__ __launch_bounds__(kThreads, kMode == kLean ? F::kMinWavesPerSimd : (k
 
     // ---- classify ONCE, in registers: 16-bit '\n' mask per chunk -> LDS bitmap; count for the publish ----
     // (the kernel is instruction-issue bound: classifying again when a half is staged cost 20 % more VALU)
+    // The loop knows nothing of the end of the input: ONE workgroup of a launch holds it, and every workgroup paid for it per chunk
+    // (the ISA of the lean FASTQ scan: four v_cndmask that zeroed a chunk past the end, the condition re-made in vector registers
+    // and a branch around the byte mask, twelve times per wave).  A chunk past the end is a copy of the input's last chunk (the
+    // clamped loads above) and stays one: `hi` gains only bytes it already holds, and whoever reads s.bytes beyond lim_e masks by
+    // position or length (the 32-byte space search, the 12-byte inline read of make_string_lds, LdsSrc::tabs64 / tab_bits).  Its
+    // newline and tab bits are taken out behind the loop, by that one workgroup.
     uint32_t hi = 0, cnt = 0;
 #pragma unroll
     for (int j = 0; j < kHalves * kRows; j++) {
-        if (lim_s != kSuper && lim_s - (int)(j * kThreads + tid) * 16 <= 0) v[j] = make_uint4(0, 0, 0, 0);  // a chunk past the end
-        uint32_t mj = match16(v[j], 0x0A0A0A0Au);
+        const uint32_t mj = match16(v[j], 0x0A0A0A0Au);
         hi |= v[j].x | v[j].y | v[j].z | v[j].w;
-        if (lim_s != kSuper) {  // the input ends inside this super-tile: mask the bytes past the end
-            int rem = lim_s - (int)(j * kThreads + tid) * 16;
-            if (rem < 16) mj &= rem <= 0 ? 0u : ((1u << rem) - 1u);
-        }
         s.bitmap[j / kRows][(j % kRows) * kThreads + tid] = (uint16_t)mj;
         if constexpr (FusedLds::kHasTabs) s.tabmap[j / kRows][(j % kRows) * kThreads + tid] = (uint16_t)match16(v[j], 0x09090909u);
         cnt += __popc(mj);
+    }
+    if (lim_s != kSuper) {
+        // the input ends inside this super-tile: every thread takes the bytes past the end out of its own map entries (written
+        // above by the same thread: no barrier) and counts again.  Rolled: cold code, kept short.
+        cnt = 0;
+#pragma unroll 1
+        for (int j = 0; j < kHalves * kRows; j++) {
+            const int rem = lim_s - (int)(j * kThreads + tid) * 16;
+            uint16_t *bm = &s.bitmap[j / kRows][(j % kRows) * kThreads + tid];
+            uint32_t mj = *bm;
+            if (rem < 16) mj &= rem <= 0 ? 0u : ((1u << rem) - 1u);
+            *bm = (uint16_t)mj;
+            if constexpr (FusedLds::kHasTabs) {
+                if (rem <= 0) s.tabmap[j / kRows][(j % kRows) * kThreads + tid] = 0;
+            }
+            cnt += __popc(mj);
+        }
     }
     hi &= 0x80808080u;
     for (int o = 32; o > 0; o >>= 1) cnt += __shfl_down(cnt, o, 64);
@@ -568,7 +586,7 @@ __global__ __launch_bounds__(kThreads, kMode == kLean ? F::kMinWavesPerSimd : (k
             // read of the bitmap, so newline ranks follow from one 32-bit wave scan.
             unsigned long long mask = *reinterpret_cast<const unsigned long long *>(&s.bitmap[h][tid * 4]);
             uint32_t c = (uint32_t)__popcll(mask);
-            uint32_t inc = wave_incl_sum(c);
+            uint32_t inc = wave_incl_sum_dpp(c);  // (on the VALU: three registers and twelve spilled scalars fewer than by ds_bpermute)
             if (lane == 63) s.wtot[wave] = inc;
             __syncthreads();
             uint32_t r = inc - c + (wave > 0 ? s.wtot[0] : 0) + (wave > 1 ? s.wtot[1] : 0) + (wave > 2 ? s.wtot[2] : 0);
