@@ -35,7 +35,7 @@ def new_reader(uri, file_format, batch_size=abi.EXG_VECTOR_SIZE, compression=Non
 
     l = _lib()
     stream = (C.c_uint64 * 8)()  # struct ArrowArrayStream (5 pointers), filled by the callee
-    enc = lambda s: None if s is None else s.encode()  # noqa: E731
+    enc = lambda s: s if s is None or isinstance(s, bytes) else s.encode()  # noqa: E731  (bytes: a `filters` text as it stands)
     res = l.new_reader(C.addressof(stream), enc(uri), batch_size, enc(compression), enc(file_format), enc(filters))
     if res.error:
         msg = C.string_at(res.error).decode("utf-8", "replace")

@@ -4,6 +4,7 @@
 // FASTQArrayBuilder / FASTAArrayBuilder / VCFArrayBuilder and from DataFusion's FilterExec
 // (rust/src/arrow_reader.rs:125-153), restated as HBM-resident scans and copies.
 #include "exg_arrow.hpp"
+#include "exg_filter_eval.hpp"
 #include "exg_scan.hpp"
 
 namespace exg {
@@ -293,90 +294,32 @@ void narrow_offsets(const uint64_t *d_goff, uint64_t n, int32_t *d_off32, hipStr
 }
 
 // ---- filters -----------------------------------------------------------------------------------------------------
-// SQL three-valued logic over a postfix program; the operand stack is two bit fields (value, is-null).
+// SQL three-valued logic over a postfix program; the operand stack is two bit fields (value, is-null).  The predicate itself
+// is exg_filter_eval.hpp (host and device); here is the fetching.
 struct FilterEval {
     const FilterProgram &prog;  // device memory
     const FilterCols &cols;
     const uint8_t *consts;
 
-    __device__ bool is_null(uint32_t c, uint64_t r) const {
-        const uint64_t *v = cols.validity[c];
-        return v && !((v[r >> 6] >> (r & 63)) & 1);
-    }
-    __device__ int cmp_str(uint32_t c, uint64_t r, const FilterOp &op) const {
-        ColGet g{StrCol{(const exg_string_t *)cols.data[c], cols.d_base[c], cols.payload_base[c]}, nullptr};
-        uint32_t len;
-        const uint8_t *p = g.ptr(r, &len);
-        const uint8_t *q = consts + op.str_off;
-
-        const uint32_t m = len < op.str_len ? len : op.str_len;
-        for (uint32_t i = 0; i < m; i++) {
-            int d = (int)p[i] - (int)q[i];
-            if (d) return d < 0 ? -1 : 1;
+    // what exg_filter_eval.hpp's filter_eval_row fetches of row r: the columns, their validity words
+    struct Row {
+        const FilterCols &cols;
+        uint64_t r;
+        __device__ uint32_t kind(uint32_t c) const { return cols.kind[c]; }
+        __device__ bool is_null(uint32_t c) const {
+            const uint64_t *v = cols.validity[c];
+            return v && !((v[r >> 6] >> (r & 63)) & 1);
         }
-        return len < op.str_len ? -1 : len > op.str_len ? 1 : 0;
-    }
-    __device__ uint64_t operator()(uint64_t r) const {
-        uint32_t vals = 0, nulls = 0;
-        int sp = 0;
-        for (uint32_t k = 0; k < prog.n_ops; k++) {
-            const FilterOp &op = prog.ops[k];
-            if (op.op == kOpAnd || op.op == kOpOr) {
-                sp -= 2;
-                const bool av = (vals >> sp) & 1, an = (nulls >> sp) & 1;
-                const bool bv = (vals >> (sp + 1)) & 1, bn = (nulls >> (sp + 1)) & 1;
-                bool rv, rn;
-                if (op.op == kOpAnd) {
-                    const bool any_false = (!an && !av) || (!bn && !bv);
-                    rn = !any_false && (an || bn);
-                    rv = !any_false && !rn;
-                } else {
-                    const bool any_true = (!an && av) || (!bn && bv);
-                    rn = !any_true && (an || bn);
-                    rv = any_true;
-                }
-                vals = (vals & ~(3u << sp)) | ((uint32_t)rv << sp);
-                nulls = (nulls & ~(3u << sp)) | ((uint32_t)rn << sp);
-                sp++;
-                continue;
-            }
-            const uint32_t c = op.col;
-            bool v = false, nul = false;
-            if (op.op == kOpIsNull)
-                v = is_null(c, r);
-            else if (op.op == kOpIsNotNull)
-                v = !is_null(c, r);
-            else if (is_null(c, r))
-                nul = true;
-            else {
-                int d;  // sign of column - literal; 2 = unordered (NaN)
-                if (cols.kind[c] == kColStr) {
-                    d = cmp_str(c, r, op);
-                } else if ((cols.kind[c] == kColI64 || cols.kind[c] == kColI32) && op.lit == kLitInt) {
-                    const int64_t x = cols.kind[c] == kColI32 ? (int64_t)((const int32_t *)cols.data[c])[r] : ((const int64_t *)cols.data[c])[r];
-                    d = x < op.i ? -1 : x > op.i ? 1 : 0;
-                } else {
-                    const double x = cols.kind[c] == kColI64   ? (double)((const int64_t *)cols.data[c])[r]
-                                     : cols.kind[c] == kColI32 ? (double)((const int32_t *)cols.data[c])[r]
-                                                               : (double)((const float *)cols.data[c])[r];
-                    const double y = op.lit == kLitInt ? (double)op.i : op.f;
-                    d = x < y ? -1 : x > y ? 1 : x == y ? 0 : 2;
-                }
-                switch (op.cmp) {
-                    case kEq: v = d == 0; break;
-                    case kNe: v = d != 0; break;
-                    case kLt: v = d < 0; break;
-                    case kLe: v = d <= 0; break;
-                    case kGt: v = d > 0 && d != 2; break;
-                    default: v = d >= 0 && d != 2; break;
-                }
-            }
-            vals = (vals & ~(1u << sp)) | ((uint32_t)v << sp);
-            nulls = (nulls & ~(1u << sp)) | ((uint32_t)nul << sp);
-            sp++;
+        __device__ const uint8_t *str(uint32_t c, uint32_t *len) const {
+            ColGet g{StrCol{(const exg_string_t *)cols.data[c], cols.d_base[c], cols.payload_base[c]}, nullptr};
+            return g.ptr(r, len);
         }
-        return (sp == 1 && (vals & 1) && !(nulls & 1)) ? 1 : 0;
-    }
+        __device__ int64_t i64(uint32_t c) const {
+            return cols.kind[c] == kColI32 ? (int64_t)((const int32_t *)cols.data[c])[r] : ((const int64_t *)cols.data[c])[r];
+        }
+        __device__ float f32(uint32_t c) const { return ((const float *)cols.data[c])[r]; }
+    };
+    __device__ uint64_t operator()(uint64_t r) const { return filter_eval_row(prog, consts, Row{cols, r}) ? 1 : 0; }
 };
 
 __global__ __launch_bounds__(256) void k_row_map(const uint64_t *__restrict__ goff, uint64_t n, uint32_t *row_map) {

@@ -1494,7 +1494,13 @@ static int build_stream(const exg_open_args &oa, const char *filters, std::share
         std::vector<exg_rd::FilterColumn> fcols;
         for (auto &f : st->schema) fcols.push_back({f.name, f.format == "u" ? 'u' : f.format == "l" ? 'l' : f.format == "f" ? 'f' : 'x'});
         exg_rd::FilterParser fp(text, fcols);
-        if (!fp.parse()) {
+        bool parsed = false;
+        try {
+            parsed = fp.parse();
+        } catch (const std::exception &e) {
+            fp.err = e.what();
+        }
+        if (!parsed) {
             *err = "could not execute sql: " + fp.err;
             return EXG_E_INVALID_ARG;
         }

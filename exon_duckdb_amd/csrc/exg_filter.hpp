@@ -4,10 +4,12 @@
 // program exg_arrow.hip evaluates on the device.
 #pragma once
 #include <ctype.h>
+#include <errno.h>
 #include <stdlib.h>
 #include <string.h>
 #include <strings.h>
 
+#include <cmath>
 #include <string>
 #include <vector>
 
@@ -60,6 +62,7 @@ struct FilterParser {
         if (i < s.size() && s[i] == '"') {
             i++;
             while (i < s.size() && s[i] != '"') name.push_back(s[i++]);
+            if (i >= s.size()) return err = "unterminated quoted identifier", false;
             i++;
         } else {
             while (i < s.size() && (isalnum((unsigned char)s[i]) || s[i] == '_')) name.push_back(s[i++]);
@@ -124,12 +127,28 @@ struct FilterParser {
             std::string num = s.substr(i, j - i);
             i = j;
             if (fmt == "u") return err = "cannot compare " + name + " with a number", false;
-            if (is_float) {
+            // the whole token must be one number (the end pointer says so): "-", "1.2.3", "5e" and "-e" are not
+            char *end = nullptr;
+            if (fmt == "f") {
+                // a FLOAT column compares in float32, against the literal rounded to float32 (DuckDB casts the constant to the
+                // column's type, and does not evaluate a pushed filter again): op.f carries that float, whatever the literal's
+                // form — 99999999999999999999 is no int64, and a fine float
+                const float y = strtof(num.c_str(), &end);
+                if (end != num.c_str() + num.size()) return err = "malformed number '" + num + "'", false;
+                if (std::isinf(y)) return err = "number out of FLOAT range '" + num + "'", false;
                 op.lit = ea::kLitFloat;
-                op.f = strtod(num.c_str(), nullptr);
+                op.f = (double)y;
+            } else if (is_float) {
+                op.lit = ea::kLitFloat;
+                op.f = strtod(num.c_str(), &end);
+                if (end != num.c_str() + num.size()) return err = "malformed number '" + num + "'", false;
+                if (std::isinf(op.f)) return err = "number out of range '" + num + "'", false;
             } else {
                 op.lit = ea::kLitInt;
-                op.i = strtoll(num.c_str(), nullptr, 10);
+                errno = 0;
+                op.i = strtoll(num.c_str(), &end, 10);
+                if (end != num.c_str() + num.size()) return err = "malformed number '" + num + "'", false;
+                if (errno == ERANGE) return err = "integer literal out of range '" + num + "'", false;
                 op.f = (double)op.i;
             }
         }

@@ -119,7 +119,13 @@ extern "C" int exg_open(const exg_open_args *args, exg_reader **out) {
             fcols.push_back({sch.names[c], sch.types[c] == EXG_TYPE_BIGINT ? 'l' : sch.types[c] == EXG_TYPE_INTEGER ? 'i' : sch.types[c] == EXG_TYPE_FLOAT ? 'f' : sch.types[c] == EXG_TYPE_VARCHAR ? 'u' : 'x'});
         const std::string text = args->filters;
         FilterParser fp(text, fcols);
-        if (!fp.parse()) {
+        bool parsed = false;
+        try {  // (exg_open is extern "C": nothing may leave it)
+            parsed = fp.parse();
+        } catch (const std::exception &e) {
+            fp.err = e.what();
+        }
+        if (!parsed) {
             exg::set_error("could not execute sql: %s", fp.err.c_str());
             return EXG_E_INVALID_ARG;
         }

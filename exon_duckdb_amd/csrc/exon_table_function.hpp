@@ -22,7 +22,10 @@
 //     shard and summed by DuckDB's aggregate;
 //   * get_batch_index orders the chunks (shard-major, then the shard's device batches), so an order-preserving plan sees
 //     the file order; a device batch (~256 MiB of input) is one DuckDB batch, and the index stays far below DuckDB's
-//     per-pipeline increment (10^13) for any shard count the planner allows.
+//     per-pipeline increment (10^13) for any shard count the planner allows;
+//   * FilterToString keeps the tree: every conjunction it renders, and every per-column entry of the TableFilterSet, goes
+//     into parentheses.  The reference joins them bare (module.cpp:158-214), so `start<5 OR start>=9` on one column beside
+//     `flag=99` on another is read back as `start<5 OR (start>=9 AND flag=99)` — rows DuckDB never sees again to reject.
 //
 // What D provides: the types FunctionData, GlobalTableFunctionState, LocalTableFunctionState, LogicalType, DataChunk,
 // TableFilter, ConstantFilter, ConjunctionFilter, TableFilterSet, TableFilterType, idx_t, the constants
@@ -147,7 +150,8 @@ struct ExonTableFunction {
         return out;
     }
 
-    // module.cpp:158-199: the predicate text the engine parses again (`filters` of exg_open / new_reader)
+    // module.cpp:158-199: the predicate text the engine parses again (`filters` of exg_open / new_reader); parenthesised, unlike
+    // the reference's, so that the text means the tree
     static std::string FilterToString(const typename D::TableFilter &filter, const std::string &column_name) {
         using T = typename D::TableFilterType;
         switch (filter.filter_type) {
@@ -160,7 +164,7 @@ struct ExonTableFunction {
                 auto &cj = static_cast<const typename D::ConjunctionFilter &>(filter);
                 std::vector<std::string> parts;
                 for (auto &c : cj.child_filters) parts.push_back(FilterToString(*c, column_name));
-                return Join(parts, filter.filter_type == T::CONJUNCTION_AND ? " AND " : " OR ");
+                return "(" + Join(parts, filter.filter_type == T::CONJUNCTION_AND ? " AND " : " OR ") + ")";
             }
             case T::IS_NOT_NULL: return column_name + " IS NOT NULL";
             case T::IS_NULL: return column_name + " IS NULL";
@@ -172,7 +176,7 @@ struct ExonTableFunction {
     static std::string FilterToString(const typename D::TableFilterSet &set, const std::vector<idx_t> &column_ids,
                                       const std::vector<std::string> &column_names) {
         std::vector<std::string> parts;
-        for (auto &f : set.filters) parts.push_back(FilterToString(*f.second, column_names.at(column_ids.at(f.first))));
+        for (auto &f : set.filters) parts.push_back("(" + FilterToString(*f.second, column_names.at(column_ids.at(f.first))) + ")");
         return Join(parts, " AND ");
     }
 

@@ -597,7 +597,13 @@ extern "C" int exon_tf_filter_explain(const char *file_format, const char *filte
     exg_rd::FilterParser fp(text, cols);
     std::string res;
     int rc = 0;
-    if (!fp.parse()) {
+    bool parsed = false;
+    try {
+        parsed = fp.parse();
+    } catch (const std::exception &e) {
+        fp.err = e.what();
+    }
+    if (!parsed) {
         res = fp.err;
         rc = -1;
     } else {

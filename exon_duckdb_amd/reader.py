@@ -21,8 +21,9 @@ class ShardReader:
         self._l.exg_reader_error.restype = C.c_char_p
         self._l.exg_reader_error.argtypes = [C.c_void_p]
         self._l.exg_close.argtypes = [C.c_void_p]
+        enc = lambda s: s if s is None or isinstance(s, bytes) else s.encode()  # noqa: E731  (bytes: a `filters` text as it stands)
         a = abi.OpenArgs(path.encode(), file_format.encode(), compression.encode() if compression else None, batch_rows, device,
-                         device_batch_bytes, filters.encode() if filters else None, shard_index, shard_count,
+                         device_batch_bytes, enc(filters or None), shard_index, shard_count,
                          sum(1 << int(c) for c in columns) if columns is not None else 0, abi.EXG_OPEN_CHUNKS if expect_chunks else 0)
         self.columns = None if columns is None else sorted(int(c) for c in columns)
         self._r = C.c_void_p()

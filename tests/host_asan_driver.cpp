@@ -256,10 +256,15 @@ int main(int argc, char **argv) {
     // the filter grammar on well-formed and mangled predicates
     const std::vector<exg_rd::FilterColumn> cols = {{"chrom", 'u'}, {"pos", 'l'}, {"id", 'x'}, {"qual", 'f'}};
     const char *seeds[] = {"chrom='7' AND pos>=3000 AND pos<9000", "qual IS NULL OR qual>900.5", "\"chrom\"!='a''b' AND (pos<>1 OR qual<=1e3)",
-                           "id='x'", "pos=", "((((chrom='1'", "qual>'abc'", "chrom IS NOT NULL AND chrom IS NULL OR pos>1 OR pos>2 OR pos>3"};
-    for (const char *sd : seeds)
+                           "id='x'", "pos=", "((((chrom='1'", "qual>'abc'", "chrom IS NOT NULL AND chrom IS NULL OR pos>1 OR pos>2 OR pos>3",
+                           // the last seven have to be refused as they stand: an unterminated quoted identifier that names a
+                           // column (the index ran past the end), malformed and out-of-range numbers (each was accepted as
+                           // some other number)
+                           "\"pos", "\"", "pos = -", "pos=1.2.3", "pos=5e", "qual=-e", "pos=99999999999999999999"};
+    const size_t n_seeds = sizeof seeds / sizeof *seeds, first_refused = n_seeds - 7;
+    for (size_t sd = 0; sd < n_seeds; sd++)
         for (int trial = 0; trial < 300; trial++) {
-            std::string t = sd;
+            std::string t = seeds[sd];
             if (trial) {
                 for (int k = 0; k < 1 + (int)(rng() % 3); k++) {
                     const size_t at = rng() % (t.size() + 1);
@@ -271,7 +276,8 @@ int main(int argc, char **argv) {
                 }
             }
             exg_rd::FilterParser fp(t, cols);
-            (void)fp.parse();
+            const bool ok = fp.parse();
+            if (!trial && ok && sd >= first_refused) return 6;  // (those seeds themselves, unmutated: refused)
             runs++;
         }
     // a long conjunction must be refused, not overflow the program
