@@ -89,6 +89,17 @@ struct FilterCols {
 // d_goff_tmp has n + 1 entries; program and column table live in device memory
 void filter_rows(const FilterProgram *d_prog, const FilterCols *d_cols, const uint8_t *d_consts, uint64_t n,
                  uint64_t *d_goff_tmp, uint64_t *d_tmp, uint32_t *d_row_map, hipStream_t stream);
+// The predicate step of a batch, host side: the column table `fc` goes to d_fc, the rows where the predicate is TRUE become
+// d_row_map (scratch as for filter_rows) and their number comes back in *n_out.  Synchronises `stream` once, at that read-back
+// (fc, a stack object of the caller's, is alive until then).
+inline hipError_t select_rows(const FilterCols &fc, const FilterProgram *d_prog, const uint8_t *d_consts, uint64_t n, uint64_t *d_goff_tmp,
+                              uint64_t *d_tmp, uint32_t *d_row_map, FilterCols *d_fc, hipStream_t stream, uint64_t *n_out) {
+    hipError_t e = hipMemcpyAsync(d_fc, &fc, sizeof fc, hipMemcpyHostToDevice, stream);
+    if (e != hipSuccess) return e;
+    filter_rows(d_prog, d_fc, d_consts, n, d_goff_tmp, d_tmp, d_row_map, stream);
+    if ((e = hipMemcpyAsync(n_out, d_goff_tmp + n, 8, hipMemcpyDeviceToHost, stream)) != hipSuccess) return e;
+    return hipStreamSynchronize(stream);
+}
 
 // ---- gathers through the row map ------------------------------------------------------------------------
 void gather_bits(const uint64_t *d_in, const uint32_t *d_row_map, uint64_t n_out, uint64_t *d_out, hipStream_t stream);

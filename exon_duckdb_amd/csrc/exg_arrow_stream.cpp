@@ -785,13 +785,9 @@ int arrow_emit(exg_reader *r, const ScanCtx &ctx) {
         if (em.rc) return em.rc;
         ea::FilterCols *d_fc = (ea::FilterCols *)em.dalloc(sizeof fc);
         if (em.rc) return em.rc;
-        EM_HIP(hipMemcpyAsync(d_fc, &fc, sizeof fc, hipMemcpyHostToDevice, r->stream));
-        EM_HIP(hipStreamSynchronize(r->stream));  // fc is a stack object
-        ea::filter_rows((const ea::FilterProgram *)st->d_prog, d_fc, (const uint8_t *)st->d_consts, em.n, d_goff, d_tmp, d_map,
-                        r->stream);
-        em.n = em.fetch_u64(d_goff + ctx.n_records);
+        EM_HIP(ea::select_rows(fc, (const ea::FilterProgram *)st->d_prog, (const uint8_t *)st->d_consts, ctx.n_records, d_goff, d_tmp, d_map, d_fc,
+                               r->stream, &em.n));
         em.d_row_map = d_map;
-        if (em.rc) return em.rc;
     }
     const uint64_t n = em.n;
     if (n == 0) {

@@ -143,6 +143,65 @@ void bam_stats(exg_reader *r, uint64_t *tiles, uint64_t *rewalked) {
     *tiles = s->tiles.load(), *rewalked = s->tiles_rewalked.load();
 }
 
+namespace {
+
+// what discover() found, against what is provisioned (nothing has been written yet)
+enum BamVerdict { kBamAccept, kBamWiden, kBamWorstCaseRows, kBamFailRows, kBamGrowSide };
+BamVerdict bam_judge(const exg_bam_scan_result &res, const BamState *s, bool eof, bool no_store) {
+    if (res.n_records == 0 && !res.error_code && !eof) return kBamWiden;  // one record larger than the batch
+    if (!no_store && res.n_records > s->cap_records) return s->worst_case_rows ? kBamFailRows : kBamWorstCaseRows;
+    if (!no_store && res.side_bytes > s->side_cap) return kBamGrowSide;
+    return kBamAccept;
+}
+
+// rows where the predicate is TRUE -> row map; the columns are gathered through it on their way out (the side
+// buffer travels whole: the strings of the rows that stay behind are in it too)
+int bam_select_rows(exg_reader *r, BamState *s, const exg_bam_scan_args &a, uint64_t *k, const uint32_t **row_map) {
+    ea::FilterCols fc;
+    memset(&fc, 0, sizeof fc);
+    for (int c = 0; c < EXG_BAM_COLUMNS; c++) {
+        fc.kind[c] = kIsInt[c] ? ea::kColI32 : ea::kColStr;
+        fc.data[c] = s->d_cols[c];
+        fc.validity[c] = (const uint64_t *)s->d_valid[c];
+        const bool ref = c == 2 || c == 7;
+        fc.d_base[c] = ref ? (const uint8_t *)s->d_names : (const uint8_t *)s->d_side;
+        fc.payload_base[c] = ref ? a.ref_names_base : a.side_base;
+    }
+    uint64_t *d_goff = (uint64_t *)s->d_filter_tmp, *d_tmp = d_goff + s->cap_records + 1;
+    ea::FilterCols *d_fc = (ea::FilterCols *)s->d_gather;  // (the scratch column is free until the gathers)
+    RD_HIP(r, ea::select_rows(fc, (const ea::FilterProgram *)r->d_filter_prog, (const uint8_t *)r->d_filter_consts, *k, d_goff, d_tmp,
+                              (uint32_t *)s->d_row_map, d_fc, r->stream, k));
+    *row_map = (const uint32_t *)s->d_row_map;
+    return EXG_OK;
+}
+
+int bam_columns_to_host(exg_reader *r, BamState *s, const std::shared_ptr<Batch> &b, const exg_bam_scan_result &res, uint8_t *h_side, uint64_t k,
+                        const uint32_t *row_map) {
+    TraceRange d2h_range("exg: columns -> host");
+    b->n_rows = k;
+    b->n_cols = EXG_BAM_COLUMNS;
+    bool any_side = false;
+    for (int c = 0; c < EXG_BAM_COLUMNS; c++) {
+        b->elem[c] = 0, b->cols[c] = nullptr;
+        if (!r->want(c)) continue;
+        b->elem[c] = kIsInt[c] ? 4 : 16;
+        if (int rc = column_to_host(r, b.get(), c, s->d_cols[c], b->elem[c], kNullable[c] ? s->d_valid[c] : nullptr, k, row_map, s->d_gather, r->stream))
+            return rc;
+        any_side |= c == 0 || c == 6 || c == 8 || c == 9;
+    }
+    if (any_side && res.side_bytes) {
+        RD_HIP(r, hipMemcpyAsync(h_side, s->d_side, res.side_bytes, hipMemcpyDeviceToHost, r->stream));
+        r->host_vector_bytes += res.side_bytes;  // (the strings' payload is made on the device: it is part of the vectors)
+    }
+    RD_HIP(r, hipStreamSynchronize(r->stream));
+    r->host_hint = b->host.total + b->host.total / 8 + (1u << 20);
+    b->seq = r->batch_seq++;
+    r->batch = b;
+    return EXG_OK;
+}
+
+}  // namespace
+
 int bam_next_batch(exg_reader *r, bool count_only, uint64_t *n_records_out) {
     BamState *s = state_of(r);
     const std::string &path = r->files[r->file_idx - 1];
@@ -184,19 +243,17 @@ int bam_next_batch(exg_reader *r, bool count_only, uint64_t *n_records_out) {
         if ((rc = exg::bam::discover(&a, &res))) return fail(r, rc, exg_last_error_message());
         r->n_batches++;
         s->tiles += res.tiles, s->tiles_rewalked += res.tiles_rewalked;
-        if (res.n_records == 0 && !res.error_code && !eof) {
-            want = std::max<uint64_t>(want, n) * 2;  // one record larger than the batch: widen it
-            continue;
-        }
-        if (!no_store && res.n_records > s->cap_records) {
-            if (s->worst_case_rows) return fail(r, EXG_E_CAPACITY, "more BAM records than bytes allow: internal error");
-            s->worst_case_rows = true;  // denser rows than provisioned: worst-case vectors, same batch again
-            s->in_cap = 0;
-            continue;
-        }
-        if (!no_store && res.side_bytes > s->side_cap) {
-            if ((rc = ensure_buffers(r, s, n, res.side_bytes))) return rc;
-            continue;  // (the workspace moved: same batch again)
+        switch (bam_judge(res, s, eof, no_store)) {  // (the only place that scans the batch again)
+            case kBamAccept: break;
+            case kBamWiden: want = std::max<uint64_t>(want, n) * 2; continue;
+            case kBamFailRows: return fail(r, EXG_E_CAPACITY, "more BAM records than bytes allow: internal error");
+            case kBamWorstCaseRows:  // denser rows than provisioned: worst-case vectors, same batch again
+                s->worst_case_rows = true;
+                s->in_cap = 0;
+                continue;
+            case kBamGrowSide:
+                if ((rc = ensure_buffers(r, s, n, res.side_bytes))) return rc;
+                continue;  // (the workspace moved: same batch again)
         }
         uint64_t k = res.n_records;
         if (res.error_code) {
@@ -220,71 +277,8 @@ int bam_next_batch(exg_reader *r, bool count_only, uint64_t *n_records_out) {
             a.capacity_records = s->cap_records;
             if ((rc = exg::bam::emit(&a, &res))) return fail(r, rc, exg_last_error_message());
             const uint32_t *row_map = nullptr;
-            if (r->has_filter) {
-                // rows where the predicate is TRUE -> row map; the columns are gathered through it on their way out (the side
-                // buffer travels whole: the strings of the rows that stay behind are in it too)
-                ea::FilterCols fc;
-                memset(&fc, 0, sizeof fc);
-                for (int c = 0; c < EXG_BAM_COLUMNS; c++) {
-                    fc.kind[c] = kIsInt[c] ? ea::kColI32 : ea::kColStr;
-                    fc.data[c] = s->d_cols[c];
-                    fc.validity[c] = (const uint64_t *)s->d_valid[c];
-                    const bool ref = c == 2 || c == 7;
-                    fc.d_base[c] = ref ? (const uint8_t *)s->d_names : (const uint8_t *)s->d_side;
-                    fc.payload_base[c] = ref ? a.ref_names_base : a.side_base;
-                }
-                uint64_t *d_goff = (uint64_t *)s->d_filter_tmp, *d_tmp = d_goff + s->cap_records + 1;
-                ea::FilterCols *d_fc = (ea::FilterCols *)s->d_gather;  // (the scratch column is free until the gathers)
-                RD_HIP(r, hipMemcpyAsync(d_fc, &fc, sizeof fc, hipMemcpyHostToDevice, r->stream));
-                ea::filter_rows((const ea::FilterProgram *)r->d_filter_prog, d_fc, (const uint8_t *)r->d_filter_consts, k, d_goff, d_tmp,
-                                (uint32_t *)s->d_row_map, r->stream);
-                uint64_t n_sel = 0;
-                RD_HIP(r, hipMemcpyAsync(&n_sel, d_goff + k, 8, hipMemcpyDeviceToHost, r->stream));
-                RD_HIP(r, hipStreamSynchronize(r->stream));
-                k = n_sel;
-                row_map = (const uint32_t *)s->d_row_map;
-            }
-            if (k && !count_only) {
-                TraceRange d2h_range("exg: columns -> host");
-                b->n_rows = k;
-                b->n_cols = EXG_BAM_COLUMNS;
-                bool any_side = false;
-                for (int c = 0; c < EXG_BAM_COLUMNS; c++) {
-                    b->elem[c] = 0, b->cols[c] = nullptr;
-                    if (!r->want(c)) continue;
-                    const uint32_t es = kIsInt[c] ? 4 : 16;
-                    b->elem[c] = es;
-                    if (!(b->cols[c] = b->host.alloc(k * es))) return fail(r, EXG_E_HIP, "out of pinned host memory");
-                    const void *src = s->d_cols[c];
-                    if (row_map) {
-                        if (es == 16) ea::gather_u128(src, row_map, k, s->d_gather, r->stream);
-                        else ea::gather_u32((const uint32_t *)src, row_map, k, (uint32_t *)s->d_gather, r->stream);
-                        src = s->d_gather;
-                    }
-                    RD_HIP(r, hipMemcpyAsync(b->cols[c], src, k * es, hipMemcpyDeviceToHost, r->stream));
-                    r->host_vector_bytes += k * es;
-                    if (kNullable[c]) {
-                        const size_t vw = (size_t)((k + 63) / 64) * 8;
-                        if (!(b->validity[c] = b->host.alloc(vw))) return fail(r, EXG_E_HIP, "out of pinned host memory");
-                        const void *v = s->d_valid[c];
-                        if (row_map) {
-                            ea::gather_bits((const uint64_t *)v, row_map, k, (uint64_t *)s->d_gather, r->stream);
-                            v = s->d_gather;
-                        }
-                        RD_HIP(r, hipMemcpyAsync(b->validity[c], v, vw, hipMemcpyDeviceToHost, r->stream));
-                        r->host_vector_bytes += vw;
-                    }
-                    any_side |= c == 0 || c == 6 || c == 8 || c == 9;
-                }
-                if (any_side && res.side_bytes) {
-                    RD_HIP(r, hipMemcpyAsync(h_side, s->d_side, res.side_bytes, hipMemcpyDeviceToHost, r->stream));
-                    r->host_vector_bytes += res.side_bytes;  // (the strings' payload is made on the device: it is part of the vectors)
-                }
-                RD_HIP(r, hipStreamSynchronize(r->stream));
-                r->host_hint = b->host.total + b->host.total / 8 + (1u << 20);
-                b->seq = r->batch_seq++;
-                r->batch = b;
-            }
+            if (r->has_filter && (rc = bam_select_rows(r, s, a, &k, &row_map))) return rc;
+            if (k && !count_only && (rc = bam_columns_to_host(r, s, b, res, h_side, k, row_map))) return rc;
         }
         *n_records_out = k;
         if (res.error_code) {

@@ -16,7 +16,6 @@
 #include <unistd.h>
 
 #include <algorithm>
-#include <functional>
 #include <memory>
 #include <thread>
 
@@ -25,8 +24,29 @@
 #include "exg_map_guard.hpp"
 #include "exg_rd_bam.hpp"
 #include "exg_rd_source.hpp"
+#include "exg_rd_stages.hpp"
 
 namespace exg_rd {
+
+// The A/B switches of this file, read once per process.  (EXG_NO_VCF_INDEX and EXG_VCF_ONE_STREAM are not here: they are read per
+// batch, where they are used — the tests switch them inside one process.)
+namespace {
+struct Switches {
+    const bool fasta_whole_text = getenv("EXG_FASTA_WHOLE_TEXT") != nullptr;      // a decoded FASTA: the decoded text behind the scan, no side buffer
+    const bool no_payload_compact = getenv("EXG_NO_PAYLOAD_COMPACT") != nullptr;  // a projection of a decoded input: no side buffer
+    const bool no_host_mirror = getenv("EXG_NO_HOST_MIRROR") != nullptr;          // (and tests) a decoded input: the copy behind the scan
+    const bool no_ramp = getenv("EXG_NO_RAMP") != nullptr;                        // a text file's first batch is a full one
+    const bool no_fasta_prefetch = getenv("EXG_NO_FASTA_PREFETCH") != nullptr;    // FASTA: one input slot, no upload beside the way back
+    const bool no_prefetch = getenv("EXG_NO_PREFETCH") != nullptr;                // no upload ahead of the scan
+    const bool fastq_one_stream = getenv("EXG_FASTQ_ONE_STREAM") != nullptr;      // a text FASTQ's vectors on the scan's stream
+    const bool vcf_eager_landing = getenv("EXG_VCF_EAGER_LANDING") != nullptr;    // read_vcf waits for its vectors inside next_batch
+    const bool fasta_d2h_engine = getenv("EXG_FASTA_D2H_ENGINE") != nullptr;      // FASTA: the joined sequences by a copy engine
+};
+const Switches &switches() {
+    static const Switches s;
+    return s;
+}
+}  // namespace
 
 // ---- compressed inputs: the file becomes a stream of decoded segments (exg_rd_source.hpp) --------------------------------
 
@@ -178,16 +198,13 @@ enum PayloadRoute { kPayloadNone, kPayloadCompact, kPayloadMirror };
 static PayloadRoute payload_route(const exg_reader *r) {
     if (r->format == EXG_FMT_BAM) return kPayloadNone;  // (a BAM segment is never mirrored: its strings are produced into a side buffer)
     if (r->format == EXG_FMT_FASTA) {
-        static const bool fasta_whole = getenv("EXG_FASTA_WHOLE_TEXT") != nullptr;  // (A/B: the decoded text behind the scan)
-        return (r->want_cols & 3ull) && !fasta_whole ? kPayloadCompact : kPayloadNone;
+        return (r->want_cols & 3ull) && !switches().fasta_whole_text ? kPayloadCompact : kPayloadNone;
     }
     const uint64_t strs = r->format == EXG_FMT_VCF ? 0x1DDull : 0xFull, nested = r->format == EXG_FMT_VCF ? 0x1D4ull : 0ull;
     const uint64_t sel = r->want_cols & strs;
     if (!sel) return kPayloadNone;
-    static const bool no_compact = getenv("EXG_NO_PAYLOAD_COMPACT") != nullptr;
-    if (!no_compact && sel != strs && !(sel & nested)) return kPayloadCompact;
-    static const bool no_mirror = getenv("EXG_NO_HOST_MIRROR") != nullptr;  // (A/B and tests: the copy behind the scan)
-    return no_mirror ? kPayloadNone : kPayloadMirror;
+    if (!switches().no_payload_compact && sel != strs && !(sel & nested)) return kPayloadCompact;
+    return switches().no_host_mirror ? kPayloadNone : kPayloadMirror;
 }
 
 static int open_source(exg_reader *r, std::shared_ptr<PinnedBlock> &blk, const std::string &path, uint64_t n) {
@@ -353,6 +370,62 @@ static int count_newlines_in_front(exg_reader *r, uint64_t *out) {
     return frc ? fail(r, frc, e) : EXG_OK;
 }
 
+// Where this reader's bytes of the file just opened begin and end (file_pos, range_hi), and whether its first batch takes a halo
+static int place_shard(exg_reader *r, const PinnedBlock &blk) {
+    if (r->fa_shard) {
+        // a shard of a compressed FASTA: the run of whole records from the first '>' line that begins in its own bytes to the
+        // first that begins behind them (found while scanning: next_batch), like a text shard's run
+        r->shard_first = false;
+        if (r->preset_pos == 0 && r->data0_is_line_start) {
+            r->file_pos = 0;
+        } else {
+            uint64_t at = ~0ull;
+            int rc = source_find_record(r, r->preset_pos, &at);
+            if (rc) return rc;
+            if (at == ~0ull) r->file_done = true;  // no record begins in this shard's bytes (or behind them)
+            else r->file_pos = at;
+        }
+    } else if (r->range_preset) {  // BGZF / zstd shard: the members / frames were chosen in open_source
+        // its stream begins with the file (header and all) or somewhere behind the header
+        r->data_base = r->data0_is_line_start ? r->data_base : 0;
+        r->file_pos = std::max<uint64_t>(r->preset_pos, r->data_base);
+        r->shard_first = r->file_pos > r->data_base;
+    } else if (r->shard_count > 1 && r->format == EXG_FMT_FASTA) {
+        // FASTA: a record belongs to the shard in whose bytes its '>' line BEGINS, and a shard is the run of whole
+        // records from its first such line to the next shard's — scanned like a file of its own (a record is never
+        // cut, however long its sequence: the run simply reaches as far as it has to)
+        const char *d = (const char *)blk.p;
+        const uint64_t N = blk.n;
+        auto first_record_at_or_after = [&](uint64_t pos) -> uint64_t {
+            if (pos == 0) return 0;
+            for (uint64_t q = pos - 1; q + 1 < N;) {  // a line start is the byte behind a newline
+                const void *hit = memchr(d + q, '\n', (size_t)(N - q));
+                if (!hit) return N;
+                q = (uint64_t)((const char *)hit - d) + 1;
+                if (q < N && d[q] == '>') return q;
+            }
+            return N;
+        };
+        const uint64_t lo = (uint64_t)((unsigned __int128)N * r->shard_index / r->shard_count);
+        const uint64_t hi = r->shard_index + 1 == r->shard_count ? N : (uint64_t)((unsigned __int128)N * (r->shard_index + 1) / r->shard_count);
+        r->file_pos = first_record_at_or_after(lo);
+        r->range_hi = hi == N ? N : first_record_at_or_after(hi);
+        if (r->range_hi < r->file_pos) r->range_hi = r->file_pos;
+        r->range_eof = true;  // the run is a FASTA file of its own
+    } else if (r->shard_count > 1) {
+        const uint64_t base = r->file_pos, span = blk.n - base;
+        const uint64_t lo = base + (uint64_t)((unsigned __int128)span * r->shard_index / r->shard_count);
+        const uint64_t hi = r->shard_index + 1 == r->shard_count
+                                ? blk.n
+                                : base + (uint64_t)((unsigned __int128)span * (r->shard_index + 1) / r->shard_count);
+        r->file_pos = lo;
+        r->range_hi = hi;
+        r->shard_first = lo > base;
+        r->range_eof = hi == blk.n;
+    }
+    return EXG_OK;
+}
+
 int open_next_file(exg_reader *r) {
     if (int jrc = r->finish_source()) return jrc;
     r->src.reset();  // (its thread reads the previous file's descriptor)
@@ -442,60 +515,8 @@ int open_next_file(exg_reader *r) {
     // first batches' results decide, as before).  The batches' result flags correct the choice either way.
     if (!r->src && blk->p && blk->n > r->file_pos && !getenv("EXG_NO_ALGO_HINT"))
         r->fused_algo = (uint32_t)exg_scan_algo_hint(r->format, (const uint8_t *)blk->p + r->file_pos, blk->n - r->file_pos);
-    static const bool no_ramp = getenv("EXG_NO_RAMP") != nullptr;
-    r->ramp_bytes = (!r->src && r->format != EXG_FMT_FASTA && !no_ramp && r->device_batch_bytes > kRampFirstBytes) ? kRampFirstBytes : 0;
-    if (r->fa_shard) {
-        // a shard of a compressed FASTA: the run of whole records from the first '>' line that begins in its own bytes to the
-        // first that begins behind them (found while scanning: next_batch), like a text shard's run
-        r->shard_first = false;
-        if (r->preset_pos == 0 && r->data0_is_line_start) {
-            r->file_pos = 0;
-        } else {
-            uint64_t at = ~0ull;
-            int rc = source_find_record(r, r->preset_pos, &at);
-            if (rc) return rc;
-            if (at == ~0ull) r->file_done = true;  // no record begins in this shard's bytes (or behind them)
-            else r->file_pos = at;
-        }
-    } else if (r->range_preset) {  // BGZF / zstd shard: the members / frames were chosen in open_source
-        // its stream begins with the file (header and all) or somewhere behind the header
-        r->data_base = r->data0_is_line_start ? r->data_base : 0;
-        r->file_pos = std::max<uint64_t>(r->preset_pos, r->data_base);
-        r->shard_first = r->file_pos > r->data_base;
-    } else if (r->shard_count > 1 && r->format == EXG_FMT_FASTA) {
-        // FASTA: a record belongs to the shard in whose bytes its '>' line BEGINS, and a shard is the run of whole
-        // records from its first such line to the next shard's — scanned like a file of its own (a record is never
-        // cut, however long its sequence: the run simply reaches as far as it has to)
-        const char *d = (const char *)blk->p;
-        const uint64_t N = blk->n;
-        auto first_record_at_or_after = [&](uint64_t pos) -> uint64_t {
-            if (pos == 0) return 0;
-            for (uint64_t q = pos - 1; q + 1 < N;) {  // a line start is the byte behind a newline
-                const void *hit = memchr(d + q, '\n', (size_t)(N - q));
-                if (!hit) return N;
-                q = (uint64_t)((const char *)hit - d) + 1;
-                if (q < N && d[q] == '>') return q;
-            }
-            return N;
-        };
-        const uint64_t lo = (uint64_t)((unsigned __int128)N * r->shard_index / r->shard_count);
-        const uint64_t hi = r->shard_index + 1 == r->shard_count ? N : (uint64_t)((unsigned __int128)N * (r->shard_index + 1) / r->shard_count);
-        r->file_pos = first_record_at_or_after(lo);
-        r->range_hi = hi == N ? N : first_record_at_or_after(hi);
-        if (r->range_hi < r->file_pos) r->range_hi = r->file_pos;
-        r->range_eof = true;  // the run is a FASTA file of its own
-    } else if (r->shard_count > 1) {
-        const uint64_t base = r->file_pos, span = blk->n - base;
-        const uint64_t lo = base + (uint64_t)((unsigned __int128)span * r->shard_index / r->shard_count);
-        const uint64_t hi = r->shard_index + 1 == r->shard_count
-                                ? blk->n
-                                : base + (uint64_t)((unsigned __int128)span * (r->shard_index + 1) / r->shard_count);
-        r->file_pos = lo;
-        r->range_hi = hi;
-        r->shard_first = lo > base;
-        r->range_eof = hi == blk->n;
-    }
-    return EXG_OK;
+    r->ramp_bytes = (!r->src && r->format != EXG_FMT_FASTA && !switches().no_ramp && r->device_batch_bytes > kRampFirstBytes) ? kRampFirstBytes : 0;
+    return r->fa_shard || r->range_preset || r->shard_count > 1 ? place_shard(r, *blk) : EXG_OK;
 }
 
 int n_string_cols(int format) { return format == EXG_FMT_FASTQ ? 4 : format == EXG_FMT_FASTA ? 3 : 9; }
@@ -563,8 +584,7 @@ int ensure_device(exg_reader *r, uint64_t need_bytes) {
     // two upload slots (a FASTA under a memory cap: one, its batches are then not prefetched); a decoded stream is scanned in its
     // segments: none (FASTA: one, for the 16-byte aligned copy its scan wants)
     int arc = 0;
-    static const bool no_fasta_prefetch = getenv("EXG_NO_FASTA_PREFETCH") != nullptr;
-    const int n_slots = r->format == EXG_FMT_FASTA ? (r->src || r->mem_cap || no_fasta_prefetch ? 1 : 2) : r->src ? 0 : 2;
+    const int n_slots = r->format == EXG_FMT_FASTA ? (r->src || r->mem_cap || switches().no_fasta_prefetch ? 1 : 2) : r->src ? 0 : 2;
     for (int k = 0; k < n_slots; k++)
         if ((arc = r->dev_alloc(&r->d_in_slot[k], cap + 64))) return arc;
     r->d_in = r->d_in_slot[0];
@@ -592,13 +612,674 @@ int ensure_device(exg_reader *r, uint64_t need_bytes) {
     return EXG_OK;
 }
 
-// Scan the next device batch of the current file.  On return r->batch holds its host vectors
-// (n_rows may be 0 when the file is exhausted).  count_only: no column leaves the device.
 int truncated_while_read(exg_reader *r) {
     if (!r->file || r->file->guard < 0 || !MapGuard::hit(r->file->guard)) return EXG_OK;
     return fail(r, EXG_E_IO, "'" + r->files[r->file_idx - 1] + "' was truncated while it was being read");
 }
 
+namespace {
+
+// What one attempt at a batch scans.  Re-made at the top of every attempt: a retry cannot read a field of the attempt before.
+struct BatchIn {
+    uint64_t n = 0;           // bytes of the attempt: behind file_pos until the input is bound, then all the scan is given (`lead` included)
+    uint64_t lead = 0;        // bytes of d_input in front of file_pos (the halo, and what a 16-byte boundary brings along)
+    uint64_t shard_halo = 0;  // first batch of a shard that begins inside the file: bytes in front of it that travel along
+    bool range_end = false;   // the batch reaches the end of this reader's bytes ...
+    bool eof = false;         // ... which is the end of the file unless a later shard follows
+    const void *d_input = nullptr;
+    const uint8_t *h = nullptr;  // host address of the byte at d_input[0] (the strings' payload_base)
+    uint64_t batch_end = 0;      // file offset one past the bytes of this batch
+    // a decoded stream: the bytes from file_pos on (and the halo in front) made contiguous in HBM — everything up to the end of
+    // the segment that holds them is this batch
+    const uint8_t *src_at = nullptr;  // device address of stream byte src_pos
+    uint64_t src_pos = 0;
+    std::shared_ptr<PinnedBlock> gz_payload;  // gzip: this batch's inflated bytes on the host (string_t payload)
+    std::shared_ptr<HostMirror> gz_mirror;    // ... when the producer sent them ahead (exg_rd_source.hpp); then only
+    uint64_t gz_front = 0;                    // ... the first gz_front bytes of the batch (the carried tail) are copied here
+    bool compact = false;                     // ... or: only the selected columns' out-of-line strings travel (a side buffer)
+    std::shared_ptr<Batch> b;  // FASTA: made in front of the scan (its pinned block takes the joined sequences); else by columns_to_host
+};
+
+// compact: the selected string columns' out-of-line bytes, closed up per column into ONE side buffer
+struct SideBuf {
+    struct Col {
+        uint64_t *d_goff = nullptr;
+        uint64_t total = 0, off = 0;
+    } col[9];
+    uint8_t *h = nullptr;
+};
+
+// The state of one next_batch call: its stages in the order the driver (next_batch, below) runs them.  A stage returns an error
+// code; what it hands to the stages behind it is in `in` (this attempt), `res` (the scan's result), `k` / `row_map` (the rows that
+// leave).
+struct BatchRun {
+    exg_reader *const r;
+    const bool count_only;
+    const bool no_store;  // a predicate needs the columns even for COUNT(*)
+    uint64_t want;        // bytes an attempt asks for: a device batch, doubled while a batch holds no complete record
+    BatchIn in;
+    exg_scan_result res;
+    uint64_t first_line_index = 0;
+    uint64_t k = 0;  // rows that leave: the scan's records, or those the predicate keeps (through row_map)
+    const uint32_t *row_map = nullptr;
+    double t_scan = 0;
+
+    BatchRun(exg_reader *reader, bool count) : r(reader), count_only(count), no_store(count && !reader->has_filter), want(reader->device_batch_bytes) {}
+
+    // ---- 1: the size of the attempt, from `want`, the ramp and the range (in.n == 0: nothing of this reader's is left)
+    void size_attempt() {
+        in = BatchIn();
+        // (the head of a text file: a small batch first — exg_reader.hpp ramp_bytes; the uploads behind it are sized where they are issued)
+        const bool ramp = r->ramp_bytes && !r->src && !r->pf.valid && want == r->device_batch_bytes && r->range_hi > r->file_pos;
+        const AttemptSize a = exg_rd::size_attempt(want, r->file_pos, r->range_hi, r->range_eof, ramp ? r->next_ramp() : ~0ull, r->shard_first,
+                                                   r->data_base, r->halo_want, r->src != nullptr);
+        in.n = a.n, in.range_end = a.range_end, in.eof = a.eof, in.shard_halo = a.shard_halo;
+    }
+
+    // ---- 2: a decoded stream — the segment that holds file_pos (in.n == 0: the stream has ended)
+    int acquire_segment() {
+        in.src_pos = r->file_pos - in.shard_halo;
+        uint64_t avail = 0;
+        bool src_eof = false;
+        std::string msg;
+        // What is asked of the stream is "the rest of the segment that holds file_pos", not a batch's worth of bytes: a
+        // segment shorter than a device batch (the first windows of a file are small on purpose: latency) used to be MERGED
+        // with the one behind it — a device copy of both, a pinned block of an odd size for the merged batch's payload
+        // (hipHostMalloc: ~1 ms per 10 MiB) and no host mirror.  Only a batch that held no complete record asks for more.
+        const uint64_t ask = (want > r->device_batch_bytes || r->format == EXG_FMT_FASTA) ? want : std::min<uint64_t>(want, 1u << 20);
+        const double t_acq = now_s();
+        int arc = r->src->acquire(in.src_pos, ask + in.shard_halo, &in.src_at, &avail, &src_eof, &msg);
+        TRACE("acquire(decoded segment)", t_acq);
+        trace_at("C acquired", r->n_batches);
+        if (arc) return fail(r, arc, msg + (msg.find(r->files[r->file_idx - 1]) == std::string::npos ? " in '" + r->files[r->file_idx - 1] + "'" : ""));
+        r->n_segments = r->src->segments_consumed() + 1;
+        if (avail <= in.shard_halo && src_eof) {  // nothing behind file_pos: the stream has ended
+            in.n = 0;
+            return EXG_OK;
+        }
+        in.n = avail - in.shard_halo;
+        in.range_end = src_eof;
+        in.eof = in.range_end && r->range_eof;
+        return r->fa_shard ? fasta_shard_end(avail) : EXG_OK;
+    }
+    // a shard of a compressed FASTA: where does the first record begin that is NOT this shard's?  (mark 1: the decoded offset behind
+    // its own members / frames — while it is not set, nothing handed out so far lies behind it)
+    int fasta_shard_end(uint64_t avail) {
+        uint64_t own_end = 0;
+        if (r->fa_end == ~0ull && r->src->peek_mark(1, &own_end)) {
+            if (own_end <= r->file_pos) {
+                r->fa_end = r->file_pos;
+            } else if (own_end < in.src_pos + avail) {
+                unsigned long long pos = ~0ull;
+                if (!r->d_phase && !(r->d_phase = dev_pool()->take(r->device, 4096))) return fail(r, EXG_E_HIP, "out of device memory");
+                int arc = exg_fasta_find_record(in.src_at, own_end - in.src_pos, avail, 0, (uint64_t *)r->d_phase, r->stream);
+                if (arc) return fail(r, arc, exg_last_error_message());
+                RD_HIP(r, hipMemcpyAsync(&pos, r->d_phase, 8, hipMemcpyDeviceToHost, r->stream));
+                RD_HIP(r, hipStreamSynchronize(r->stream));
+                if (pos != ~0ull) r->fa_end = in.src_pos + pos;
+            }
+        }
+        if (r->fa_end != ~0ull) {
+            in.n = r->fa_end <= r->file_pos ? 0 : r->fa_end - r->file_pos;
+            in.range_end = in.eof = true;
+        }
+        return EXG_OK;
+    }
+
+    // ---- 3: the input of the scan: the inflated bytes already in HBM (gzip), the prefetched slot, or a synchronous
+    // H2D copy.  In the first two cases the batch start is only byte aligned: the buffer starts at the
+    // 16-byte boundary below it and `lead` skips the tail of the previous record (whose last '\n' is
+    // then inside the buffer).
+    bool prefetch_covers_file_pos() const {
+        return r->pf.valid && want == r->device_batch_bytes && r->file_pos >= r->pf.file_start && r->file_pos < r->pf.file_start + r->pf.len;
+    }
+    // The batch about to be scanned is on its way (or there); if its upload is the one this call will use, the batch
+    // AFTER it starts travelling now, into the slot of the batch that was scanned last (free: its columns have left) —
+    // issued after this call's scan, an upload began only when the link had already been idle for a scan + a D2H.
+    void upload_second_ahead() {
+        if (switches().no_prefetch || r->pf2.valid || r->src || r->format == EXG_FMT_FASTA || !prefetch_covers_file_pos() ||
+            !r->d_in_slot[r->pf.slot ^ 1] || r->up_thread_of[r->pf.slot ^ 1].joinable())
+            return;
+        const uint64_t end1 = r->pf.file_start + r->pf.len;  // where the coming batch's bytes end
+        if (end1 >= r->range_hi) return;
+        const PrefetchWindow w = prefetch_window(r->file_pos, end1, kPrefetchSlack);
+        if (const uint64_t len = w.len(r->range_hi, r->next_ramp(), r->d_in_cap)) start_upload(r, &r->pf2, w.start, len, r->pf.slot ^ 1);
+    }
+    int bind_input() {
+        upload_second_ahead();
+        trace_at("N batch begins", r->n_batches);
+        if (int rc = r->join_prefetch()) return rc;  // the upload thread of the previous call (its error is this call's)
+        trace_at("N upload thread joined", r->n_batches);
+        in.h = (const uint8_t *)r->file->p + r->file_pos;
+        in.batch_end = r->file_pos + in.n;
+        if (r->src) return bind_decoded();
+        return prefetch_covers_file_pos() ? bind_prefetched() : bind_uploaded();
+    }
+    int bind_decoded() {
+        in.lead = in.shard_halo + (in.src_pos & 15);
+        in.d_input = in.src_at - (in.src_pos & 15);
+        in.n += in.lead;
+        if (r->format == EXG_FMT_FASTA) {
+            // the FASTA scan wants its batch on a 16-byte boundary with nothing in front: a device copy (the decoders
+            // in front of it run at a few percent of what a copy does)
+            if (in.shard_halo) return fail(r, EXG_E_INVALID_ARG, "internal: a FASTA batch has no halo");
+            in.n -= in.lead;
+            RD_HIP(r, hipMemcpyAsync(r->d_in_slot[0], in.src_at, in.n, hipMemcpyDeviceToDevice, r->stream));
+            RD_HIP(r, hipMemsetAsync((char *)r->d_in_slot[0] + in.n, 0, 16, r->stream));
+            r->d_in = r->d_in_slot[0];
+            in.d_input = r->d_in;
+            in.lead = 0;
+        }
+        return route_payload();
+    }
+    // where a decoded batch's strings will point: `in.h` and the payload route
+    int route_payload() {
+        // A projection that leaves payload-bearing columns out (SELECT name FROM read_fastq('x.fastq.gz'); chrom, pos, ref of a
+        // bgzip VCF): the decoded bytes stay in HBM, the out-of-line strings of the selected columns are closed up into a side
+        // buffer behind the scan and only that crosses PCIe (payload_*_from_col, repoint_strings).  Not when a nested VCF
+        // column is selected: its element views are cut out of the line's text by the emitter.
+        const bool to_host = !count_only && !r->arrow_emit;
+        const PayloadRoute route = to_host ? payload_route(r) : kPayloadNone;
+        in.compact = route == kPayloadCompact;
+        if (in.compact || !to_host) {
+            // (compact: a base the side buffer's pointers replace.)  COUNT(*) / the Arrow stream: no host copy; h is only the base the
+            // device subtracts again
+            in.h = (const uint8_t *)(uintptr_t)0x100000000000ull + (r->file_pos - in.lead);
+            return EXG_OK;
+        }
+        // The strings of this batch point into host memory that holds the decoded bytes.  From the first such batch on
+        // the producer sends every segment to the host as it hands it over (HostMirror: the copy runs while the segment
+        // waits in the queue and while this thread is busy with the batch in front): the batch then points into that
+        // block, and only the bytes in front of the segment's own — the tail carried over from the segment before —
+        // are copied here.  A segment without a mirror (pushed before the first call, a block of the consumer's own
+        // making, FASTA) is copied behind the scan as before.
+        const uint8_t *h_at = nullptr;
+        uint64_t m_from = 0;
+        if (route == kPayloadMirror) r->src->want_host_mirror();
+        if (route == kPayloadMirror && r->src->host_view((const uint8_t *)in.d_input, &h_at, &m_from, &in.gz_mirror)) {
+            const uint64_t first = in.src_pos - (in.src_pos & 15);  // the stream offset of d_input[0]
+            in.gz_payload = in.gz_mirror->blk;
+            in.h = h_at;
+            in.gz_front = m_from > first ? std::min<uint64_t>(in.n, m_from - first) : 0;
+            return EXG_OK;
+        }
+        in.gz_mirror.reset();
+        in.gz_payload = std::make_shared<PinnedBlock>();
+        size_t cap = in.n + 64;
+        in.gz_payload->p = global_pool()->take(&cap);
+        if (!in.gz_payload->p) return fail(r, EXG_E_HIP, "out of pinned host memory for the inflated bytes");
+        in.gz_payload->cap = cap;
+        in.gz_payload->pooled = true;
+        in.gz_payload->n = in.n;
+        in.h = (const uint8_t *)in.gz_payload->p;
+        return EXG_OK;
+    }
+    int bind_prefetched() {
+        const uint64_t off = r->file_pos - r->pf.file_start;
+        in.lead = off & 15;
+        r->cur_slot = r->pf.slot;
+        r->d_in = r->d_in_slot[r->cur_slot];
+        in.d_input = (const uint8_t *)r->d_in + (off - in.lead);
+        in.batch_end = r->pf.file_start + r->pf.len;
+        in.n = in.batch_end - r->file_pos + in.lead;
+        in.range_end = in.batch_end == r->range_hi;
+        in.eof = in.range_end && r->range_eof;
+        in.h -= in.lead;
+        r->pf.valid = false;
+        RD_HIP(r, hipStreamWaitEvent(r->stream, r->up_done_of[r->cur_slot], 0));
+        return EXG_OK;
+    }
+    int bind_uploaded() {
+        if (r->pf.valid) RD_HIP(r, hipStreamSynchronize(r->up_stream));  // a prefetch that missed: let it land first
+        r->pf.valid = false;
+        r->d_in = r->d_in_slot[r->cur_slot];
+        in.lead = in.shard_halo;
+        int rc;
+        if (r->format == EXG_FMT_FASTA && in.n > (512ull << 20)) {
+            // a whole genome in one batch: through two 256 MiB pinned windows, not one pinned block of its size
+            rc = upload_file(r, r->d_in, in.n, r->file_pos);
+            if (!rc && hipMemsetAsync((char *)r->d_in + in.n, 0, 16, r->stream) != hipSuccess) rc = fail(r, EXG_E_HIP, "hipMemsetAsync failed");
+        } else {
+            rc = upload_range(r, r->file_pos - in.lead, in.n + in.lead, r->cur_slot, r->stream);
+        }
+        if (rc) return rc;
+        in.d_input = r->d_in;
+        in.n += in.lead;
+        in.h -= in.lead;
+        return EXG_OK;
+    }
+    // While the columns travel back (and the consumer works through the chunks): the bytes the next batch will need
+    // move into the other slot — unless they left at the top of this call already (pf2), which is the steady state
+    void prefetch_next() {
+        // FASTA (round 6: its batches were uploaded, scanned and sent back one after the other — 22.7 GB/s end to end against
+        // FASTQ's 50): the scan wants its batch at a 16-byte boundary with nothing in front, and where the next batch begins —
+        // behind this one's last whole record — is known with the scan's result: its upload starts HERE, at exactly that file
+        // offset into the other slot's first byte (no slack, no lead), beside this batch's sequences on their way back
+        const bool fasta = r->format == EXG_FMT_FASTA;
+        const bool can = !in.range_end && !res.error_code && !r->src && want == r->device_batch_bytes && !switches().no_prefetch && (!fasta || res.n_records);
+        const PrefetchWindow w = prefetch_window(r->file_pos, in.batch_end, kPrefetchSlack, fasta ? r->file_pos + (res.consumed_bytes - in.lead) : ~0ull);
+        const int other = r->cur_slot ^ 1;
+        if (r->pf2.valid) {
+            // (its length was chosen where it was issued: a step of the ramp, or a full batch)
+            if (can && r->pf2.file_start == w.start && r->pf2.len > 0 && r->pf2.slot == other) {
+                r->pf = r->pf2;
+                r->pf2.valid = false;
+            } else {
+                r->drop_prefetch2();  // (the batch turned out otherwise: an error, a retry, the end of the range)
+            }
+        }
+        if (can && !r->pf.valid && r->d_in_slot[other] && !r->up_thread_of[other].joinable()) {
+            const uint64_t ramp_before = r->ramp_bytes;
+            if (const uint64_t len = w.len(r->range_hi, r->next_ramp(), r->d_in_cap)) start_upload(r, &r->pf, w.start, len, other);
+            else r->ramp_bytes = ramp_before;
+        }
+    }
+
+    // ---- 4: the first batch of a FASTQ shard — the 4-line phase of the line that holds the shard's first byte, from the bytes around
+    // the cut ('@' opens a record but also quality lines, so several records are looked at: exg_fastq_guess_phase)
+    int fastq_first_line_phase() {
+        first_line_index = 0;
+        if (!in.lead || !r->shard_first || r->format != EXG_FMT_FASTQ) return EXG_OK;
+        if (!r->d_phase && !(r->d_phase = exg_rd::dev_pool()->take(r->device, 4096))) return fail(r, EXG_E_HIP, "out of device memory");
+        uint32_t guess = 0xFFFFFFFFu;
+        int rc = exg_fastq_guess_phase(in.d_input, in.n, in.lead, (uint32_t *)r->d_phase, r->stream);
+        if (rc) return fail(r, rc, exg_last_error_message());
+        RD_HIP(r, hipMemcpyAsync(&guess, r->d_phase, 4, hipMemcpyDeviceToHost, r->stream));
+        RD_HIP(r, hipStreamSynchronize(r->stream));
+        if (guess <= 3) {
+            uint8_t prev = 0;
+            if (r->src) {
+                RD_HIP(r, hipMemcpyAsync(&prev, (const uint8_t *)in.d_input + in.lead - 1, 1, hipMemcpyDeviceToHost, r->stream));
+                RD_HIP(r, hipStreamSynchronize(r->stream));
+            } else {
+                prev = ((const uint8_t *)r->file->p)[r->file_pos - 1];
+            }
+            first_line_index = prev == '\n' ? guess : (guess + 3) % 4;
+        } else if (r->src) {
+            // a shard of a compressed input: exact when the halo begins with the file (the newlines in front are then all
+            // in HBM); else (few lines in view — records far longer than the halo — or several phases fit) the newlines in
+            // front of the shard's own bytes are counted by a decoder of their own, segment by segment
+            unsigned long long nl = 0;
+            if (r->data0_is_line_start && in.lead == r->file_pos) {
+                rc = exg_count_newlines(in.d_input, 0, in.lead, (uint64_t *)r->d_phase, r->stream);
+                if (rc) return fail(r, rc, exg_last_error_message());
+                RD_HIP(r, hipMemcpyAsync(&nl, r->d_phase, 8, hipMemcpyDeviceToHost, r->stream));
+                RD_HIP(r, hipStreamSynchronize(r->stream));
+            } else {
+                if (!r->exact_nl_known) {
+                    if ((rc = count_newlines_in_front(r, &r->exact_nl))) return rc;
+                    r->exact_nl_known = true;
+                }
+                nl = r->exact_nl;
+            }
+            first_line_index = nl;
+        } else {
+            // too few lines around the cut to tell (a tiny file, a tiny shard) or several phases fit: count the
+            // newlines in front of it — exact, and only as slow as a memchr over the page cache
+            const char *d = (const char *)r->file->p;
+            uint64_t nl = 0;
+            for (const char *q = d, *end = d + r->file_pos; q < end;) {
+                const void *hit = memchr(q, '\n', (size_t)(end - q));
+                if (!hit) break;
+                nl++;
+                q = (const char *)hit + 1;
+            }
+            first_line_index = nl;
+        }
+        return EXG_OK;
+    }
+
+    // ---- 5: the scan.  One launch function per format fills its args from `in`; `algo` is the reader's sticky choice, or
+    // EXG_ALGO_MULTIPASS for the rescan of a launch the fused kernels gave up
+    uint32_t scan_flags() const {
+        // a line starts at d_input[0] when the batch is record aligned, or when a shard's halo reaches back to the
+        // first byte behind the header
+        const bool at_line_start = in.lead == 0 || (r->shard_first && in.shard_halo && in.lead == in.shard_halo && r->data0_is_line_start &&
+                                                    r->file_pos - in.lead == r->data_base);
+        return (at_line_start ? EXG_F_BOF : 0u) | (in.eof ? EXG_F_EOF : 0u) | (no_store ? EXG_F_NO_STORE : 0u);
+    }
+    template <class Args>
+    void fill_common(Args *a) const {  // what every format's scan is told
+        memset(a, 0, sizeof *a);
+        a->d_input = in.d_input;
+        a->n_bytes = in.n;
+        a->payload_base = (uint64_t)(uintptr_t)in.h;
+        a->flags = scan_flags();
+        a->capacity_records = r->cap_records;
+        a->d_workspace = r->d_ws;
+        a->workspace_bytes = r->ws_bytes;
+        a->d_result = (exg_scan_result *)r->d_res;
+        a->stream = r->stream;
+    }
+    int launch_fastq(uint32_t algo) {
+        exg_fastq_scan_args a;
+        fill_common(&a);
+        a.lead = in.lead;
+        a.first_line_index = first_line_index;
+        a.algo = algo;
+        a.d_name = (exg_string_t *)r->d_cols[0];
+        a.d_description = (exg_string_t *)r->d_cols[1];
+        a.d_sequence = (exg_string_t *)r->d_cols[2];
+        a.d_quality = (exg_string_t *)r->d_cols[3];
+        a.d_description_validity = (uint64_t *)r->d_valid[0];
+        return scan_rc(exg_fastq_scan(&a));
+    }
+    int launch_vcf(uint32_t algo) {
+        exg_vcf_scan_args a;
+        fill_common(&a);
+        a.lead = in.lead;
+        a.algo = algo;
+        for (int c = 0; c < 9; c++) a.d_fields[c] = (exg_string_t *)r->d_cols[c];
+        if (!r->arrow_emit) {
+            // The projection reaches the kernel (a NULL column is skipped: 16 B per row less to write): POS / QUAL leave as
+            // numbers, their text is nobody's; CHROM / REF are written when they are selected or the predicate reads them.
+            // The other five feed the nested columns, which are built — and validated: a malformed value is the same error
+            // whether or not its column is selected — from their text
+            a.d_fields[1] = a.d_fields[5] = nullptr;
+            for (int c : {0, 3})
+                if (!r->want(c) && !((r->filter_cols >> c) & 1ull)) a.d_fields[c] = nullptr;
+        }
+        a.d_pos = (int64_t *)r->d_pos;
+        a.d_qual = (float *)r->d_qual;
+        a.d_qual_validity = (uint64_t *)r->d_valid[0];
+        a.d_formats_validity = (uint64_t *)r->d_valid[1];
+        if (r->flat_pending) {  // (the batch before: its flat columns' copies read what this scan writes)
+            RD_HIP(r, hipStreamWaitEvent(r->stream, r->flat_ev, 0));
+            r->flat_pending = false;
+        }
+        return scan_rc(exg_vcf_scan(&a));
+    }
+    int launch_fasta() {
+        in.b = std::make_shared<Batch>();
+        if (!count_only) {
+            in.b->payload = in.b->host.alloc(in.n + 64);
+            if (!in.b->payload) return fail(r, EXG_E_HIP, "out of pinned host memory");
+        }
+        exg_fasta_scan_args a;
+        fill_common(&a);
+        a.seq_payload_base = (uint64_t)(uintptr_t)in.b->payload;
+        a.d_id = (exg_string_t *)r->d_cols[0];
+        a.d_description = (exg_string_t *)r->d_cols[1];
+        a.d_sequence = (exg_string_t *)r->d_cols[2];
+        a.d_description_validity = (uint64_t *)r->d_valid[0];
+        a.d_seq_payload = (uint8_t *)r->d_payload;
+        return scan_rc(exg_fasta_scan(&a));
+    }
+    int scan_rc(int rc) { return rc ? fail(r, rc, exg_last_error_message()) : EXG_OK; }
+    int launch_scan(uint32_t algo) { return r->format == EXG_FMT_FASTQ ? launch_fastq(algo) : r->format == EXG_FMT_VCF ? launch_vcf(algo) : launch_fasta(); }
+    int scan() {
+        int rc = launch_scan(r->fused_algo);
+        if (rc) return rc;
+        r->n_batches++;
+        t_scan = now_s();
+        rc = exg_fetch_result((const exg_scan_result *)r->d_res, r->stream, &res);
+        if (rc) return fail(r, rc, exg_last_error_message());
+        if (r->format != EXG_FMT_FASTA && (res.flags & EXG_RF_FALLBACK)) {
+            // (no fused launch gives a batch up any more — long records, dense halves and bytes >= 0x80 are the any-shape
+            // scan's —; should one ever say so, the general path takes the batch)
+            if ((rc = launch_scan(EXG_ALGO_MULTIPASS))) return rc;
+            rc = exg_fetch_result((const exg_scan_result *)r->d_res, r->stream, &res);
+            if (rc) return fail(r, rc, exg_last_error_message());
+            res.flags |= EXG_RF_FALLBACK;
+        }
+        return EXG_OK;
+    }
+
+    // ---- 6: what the result means for the attempt (the driver's switch acts on it), and for the scan the next batch starts with
+    BatchVerdict judge() {
+        const uint64_t tile_bytes = r->format == EXG_FMT_FASTQ ? 3u * 16384u : 2u * 16384u;
+        const bool vcf = r->format == EXG_FMT_VCF;
+        const bool no_index = vcf && getenv("EXG_NO_VCF_INDEX") != nullptr;  // (per batch: the tests switch it inside one process)
+        r->fused_algo = sticky_algo(r->fused_algo, res, in.n, in.lead, tile_bytes, vcf, no_index);
+        TRACE("wait(h2d) + scan", t_scan);
+        trace_at("N scan result", r->n_batches);
+        const JudgeState s = {r->mem_cap != 0, r->ws_full, r->worst_case_rows, no_store, r->shard_first, in.eof, in.range_end,
+                              r->file_pos - in.shard_halo <= r->data_base};
+        return judge_batch(res.flags, res.n_records, res.error_code, s);
+    }
+    // The record that ends behind the cut begins in front of the halo (a long read, a very wide VCF line): it belongs
+    // to this shard, so this shard looks further back — eight times as far, up to the first byte of the data — and
+    // scans the batch again.  (The shard in front leaves the record alone: it ends behind ITS range.)
+    int look_further_back() {
+        RD_HIP(r, hipStreamSynchronize(r->stream));
+        r->halo_want = grow_halo(r->halo_want);
+        if (!r->src) return EXG_OK;
+        // a decoded stream begins with its halo: its members / frames are chosen again
+        r->src.reset();
+        r->file_idx--;
+        return open_next_file(r);
+    }
+    // the same batch again with larger device buffers (ensure_device provisions them: `flag` says which)
+    int provision_again(bool *flag) {
+        RD_HIP(r, hipStreamSynchronize(r->stream));
+        r->free_device();
+        *flag = true;
+        return EXG_OK;
+    }
+
+    // ---- 7: rows where the predicate is TRUE -> row map; the columns are gathered through it on their way out
+    int select_rows() {
+        namespace ea = exg::arrow;
+        ea::FilterCols fc;
+        memset(&fc, 0, sizeof fc);
+        const int nsc = n_string_cols(r->format);
+        for (int c = 0; c < nsc; c++) {
+            fc.kind[c] = ea::kColStr;
+            fc.data[c] = r->d_cols[c];
+            fc.d_base[c] = (const uint8_t *)in.d_input;
+            fc.payload_base[c] = (uint64_t)(uintptr_t)in.h;
+        }
+        if (r->format == EXG_FMT_VCF) {
+            fc.kind[1] = ea::kColI64, fc.data[1] = r->d_pos;
+            fc.kind[5] = ea::kColF32, fc.data[5] = r->d_qual, fc.validity[5] = (const uint64_t *)r->d_valid[0];
+            fc.validity[8] = (const uint64_t *)r->d_valid[1];
+        } else {
+            fc.validity[1] = (const uint64_t *)r->d_valid[0];
+            if (r->format == EXG_FMT_FASTA) {
+                fc.d_base[2] = (const uint8_t *)r->d_payload;
+                fc.payload_base[2] = (uint64_t)(uintptr_t)(in.b ? in.b->payload : nullptr);
+            }
+        }
+        uint64_t *d_goff = (uint64_t *)r->d_filter_tmp, *d_tmp = d_goff + r->cap_records + 1;
+        ea::FilterCols *d_fc = (ea::FilterCols *)r->d_gather;  // the scratch column is free until the gathers
+        RD_HIP(r, ea::select_rows(fc, (const ea::FilterProgram *)r->d_filter_prog, (const uint8_t *)r->d_filter_consts, k, d_goff, d_tmp,
+                                  (uint32_t *)r->d_row_map, d_fc, r->stream, &k));
+        row_map = (const uint32_t *)r->d_row_map;
+        return EXG_OK;
+    }
+
+    // ---- 8: the rows leave.  new_reader: the columns stay in HBM and become Arrow buffers there (exg_arrow_stream.cpp)
+    ScanCtx scan_ctx() const { return ScanCtx{in.d_input, in.h, k, res, in.b ? (const uint8_t *)in.b->payload : nullptr}; }
+    int arrow_emit() {
+        const double t_emit = now_s();
+        if (k)
+            if (int rc = r->arrow_emit(r, scan_ctx())) return rc;
+        TRACE("arrow emit", t_emit);
+        return EXG_OK;
+    }
+    // ... or the batch's host vectors: columns -> host
+    int columns_to_host() {
+        TraceRange d2h_range("exg: columns -> host");
+        if (!in.b) in.b = std::make_shared<Batch>();
+        Batch *b = in.b.get();
+        b->host.reserve(r->host_hint);
+        b->file = in.gz_payload ? in.gz_payload : r->file;
+        // the projection (exg_open_args.columns): every column was parsed and validated above, only the wanted ones travel.
+        // A decoded input's bytes are what its strings point into: they travel when any string column does
+        const int ns = n_string_cols(r->format);
+        const bool any_strings = r->format == EXG_FMT_VCF ? (r->want_cols & 0x1DDull) != 0 : (r->want_cols & ((1ull << ns) - 1)) != 0;
+        if (in.gz_payload && any_strings && !in.gz_mirror) RD_HIP(r, hipMemcpyAsync(in.gz_payload->p, in.d_input, in.n, hipMemcpyDeviceToHost, r->stream));
+        if (in.gz_mirror && in.gz_front) RD_HIP(r, hipMemcpyAsync(const_cast<uint8_t *>(in.h), in.d_input, in.gz_front, hipMemcpyDeviceToHost, r->stream));
+        b->n_rows = k;
+        SideBuf side;
+        SideScratch side_scratch{r->device, r->stream, {}};
+        int rc;
+        if (in.compact && (rc = side_buffer(&side, &side_scratch))) return rc;
+        b->n_cols = ns;  // schema order (exg_schema_of): VCF exposes parsed POS / QUAL in place of their raw text
+        ColDrain col_drain;
+        hipStream_t cs = r->stream;
+        if ((rc = columns_stream(&cs, &col_drain))) return rc;
+        if ((rc = flat_columns(side, cs))) return rc;
+        if (r->format == EXG_FMT_VCF) {
+            if ((rc = vcf_nested_columns(cs, &col_drain))) return rc;
+        } else if (r->want(1) && (rc = column_to_host(r, b, 1, nullptr, 0, r->d_valid[0], k, row_map, r->d_gather, cs))) {
+            return rc;
+        }
+        if (r->format == EXG_FMT_FASTA && res.payload_bytes && r->want(2) && (rc = fasta_sequences(cs))) return rc;
+        const double t_cols = now_s();
+        RD_HIP(r, hipStreamSynchronize(r->stream));
+        if (r->col_stream && !b->landed) RD_HIP(r, hipStreamSynchronize(r->col_stream));
+        col_drain.cs = nullptr;
+        TRACE("wait(columns -> host)", t_cols);
+        const double t_mir = now_s();
+        if (in.gz_mirror) RD_HIP(r, hipEventSynchronize(in.gz_mirror->ev));  // the segment's own bytes have arrived
+        if (in.gz_mirror) TRACE("wait(host mirror of the segment)", t_mir);
+        trace_at("C batch-done", r->n_batches);
+        r->host_hint = b->host.total + b->host.total / 8 + (1u << 20);
+        b->seq = r->batch_seq++;
+        r->batch = in.b;
+        return EXG_OK;
+    }
+    // compact: the selected string columns' out-of-line bytes, closed up per column into ONE side buffer
+    int side_buffer(SideBuf *side, SideScratch *scratch) {
+        namespace ea = exg::arrow;
+        const int ns = n_string_cols(r->format);
+        uint64_t *d_tmp = (uint64_t *)scratch->take((ea::scan_tmp_entries(k) + 2) * 8);
+        if (!d_tmp) return fail(r, EXG_E_HIP, "out of device memory");
+        for (int c = 0; c < ns; c++) {
+            if (!r->want(c) || (r->format == EXG_FMT_VCF && c != 0 && c != 3) || (r->format == EXG_FMT_FASTA && c == 2)) continue;
+            if (!(side->col[c].d_goff = (uint64_t *)scratch->take((k + 2) * 8))) return fail(r, EXG_E_HIP, "out of device memory");
+            const ea::StrCol sc{(const exg_string_t *)r->d_cols[c], (const uint8_t *)in.d_input, (uint64_t)(uintptr_t)in.h};
+            ea::payload_goff_from_col(sc, row_map, k, side->col[c].d_goff, d_tmp, r->stream);
+            RD_HIP(r, hipMemcpyAsync(&side->col[c].total, side->col[c].d_goff + k, 8, hipMemcpyDeviceToHost, r->stream));
+        }
+        RD_HIP(r, hipStreamSynchronize(r->stream));
+        uint64_t side_total = 0;
+        for (int c = 0; c < ns; c++) side->col[c].off = side_total, side_total += (side->col[c].total + 15) & ~15ull;
+        if (!side_total) return EXG_OK;
+        if (!(side->h = (uint8_t *)in.b->host.alloc(side_total + 64))) return fail(r, EXG_E_HIP, "out of pinned host memory");
+        const uint32_t big_cap = (uint32_t)(side_total / 8192 + 1);
+        uint32_t *d_big = (uint32_t *)scratch->take(4 * ((size_t)big_cap + 1));
+        uint8_t *d_side = (uint8_t *)scratch->take(side_total + 64);
+        if (!d_side || !d_big) return fail(r, EXG_E_HIP, "out of device memory");
+        for (int c = 0; c < ns; c++) {
+            if (!side->col[c].d_goff || !side->col[c].total) continue;
+            const ea::StrCol sc{(const exg_string_t *)r->d_cols[c], (const uint8_t *)in.d_input, (uint64_t)(uintptr_t)in.h};
+            ea::payload_copy_from_col(sc, row_map, k, side->col[c].d_goff, d_side + side->col[c].off, d_big, big_cap, r->stream);
+        }
+        RD_HIP(r, hipMemcpyAsync(side->h, d_side, side_total, hipMemcpyDeviceToHost, r->stream));
+        return EXG_OK;
+    }
+    // the stream the vectors travel on (*cs: the scan's when this returns without a word), and whether the batch is handed on while
+    // they still do (r->lazy_landing)
+    int columns_stream(hipStream_t *cs, ColDrain *col_drain) {
+        // read_vcf: behind the flat columns come the nested ones' kernels (nested_emit: dozens of small launches that build — or,
+        // for columns the projection leaves out, only validate — id / alt / filter / info / formats).  In one stream the
+        // 200 MB of flat vectors (3.7 ms of the link) stood in front of them; on a stream of their own the copies run beside
+        // them (chrom, pos, ref of a 2 GB file: 70.6 -> 49.4 ms = 42 GB/s, COUNT(*) 47 ms: A/B in one box, EXG_VCF_ONE_STREAM)
+        // (FASTA, round 6: its joined sequences are as many bytes as the batch itself — on the scan's stream they shared a copy
+        // engine with the next batch's upload, which landed 5 ms behind them: 9.7 ms per 256 MiB batch where the two directions
+        // should overlap)
+        // (EXG_VCF_ONE_STREAM is read per batch: the tests switch it inside one process)
+        if ((r->format == EXG_FMT_VCF || r->format == EXG_FMT_FASTA || (!r->src && !switches().fastq_one_stream)) && !in.compact &&
+            !getenv("EXG_VCF_ONE_STREAM")) {
+            if (!r->col_stream) {
+                RD_HIP(r, stream_pool()->take_d2h(r->device, &r->col_stream, /*calibrate=*/r->file && r->file->n >= (512ull << 20) && !r->mem_cap));
+                RD_HIP(r, hipEventCreateWithFlags(&r->col_ev, hipEventDisableTiming));
+                RD_HIP(r, hipEventCreateWithFlags(&r->flat_ev, hipEventDisableTiming));
+            }
+            RD_HIP(r, hipEventRecord(r->col_ev, r->stream));  // (the scan, the predicate's row map)
+            RD_HIP(r, hipStreamWaitEvent(r->col_stream, r->col_ev, 0));
+            *cs = col_drain->cs = r->col_stream;
+        }
+        // read_vcf hands its batch on while the vectors are still travelling (Batch::landed): the batch behind it — upload wait,
+        // scan, the nested columns' kernels — is made beside them, and the link back to the host does not idle between batches
+        r->lazy_landing = r->format == EXG_FMT_VCF && *cs == r->col_stream && *cs != r->stream && !switches().vcf_eager_landing;
+        return EXG_OK;
+    }
+    // the flat columns the projection wants, each gathered through the row map and copied back
+    int flat_columns(const SideBuf &side, hipStream_t cs) {
+        Batch *b = in.b.get();
+        const bool nested_vcf = r->format == EXG_FMT_VCF;  // id, alt, filter, info, formats: built by nested_emit (vcf_nested_columns)
+        for (int c = 0; c < b->n_cols; c++) {
+            b->elem[c] = 0;
+            b->cols[c] = nullptr;
+            if ((nested_vcf && (c == 2 || c == 4 || c >= 6)) || !r->want(c)) continue;
+            const void *src = r->d_cols[c];
+            uint32_t es = 16;
+            if (r->format == EXG_FMT_VCF && c == 1) src = r->d_pos, es = 8;
+            if (r->format == EXG_FMT_VCF && c == 5) src = r->d_qual, es = 4;
+            b->elem[c] = es;
+            int rc;
+            if (in.compact && es == 16 && side.col[c].d_goff) {
+                // (gathers through the row map itself; in place without one: the column is the scan's scratch from here on)
+                void *dst = row_map ? r->d_gather : r->d_cols[c];
+                exg::arrow::repoint_strings((const exg_string_t *)r->d_cols[c], row_map, k, side.col[c].d_goff, (uint64_t)(uintptr_t)(side.h + side.col[c].off),
+                                            (exg_string_t *)dst, r->stream);
+                rc = column_to_host(r, b, c, dst, es, nullptr, k, nullptr, nullptr, r->stream);
+            } else {
+                rc = column_to_host(r, b, c, src, es, nullptr, k, row_map, r->d_gather, cs);
+            }
+            if (rc) return rc;
+        }
+        return EXG_OK;
+    }
+    // read_vcf: QUAL's validity, then the hand-over to the nested columns' emitter (id, alt, filter, info, formats)
+    int vcf_nested_columns(hipStream_t cs, ColDrain *col_drain) {
+        Batch *b = in.b.get();
+        int rc;
+        if (r->want(5) && (rc = column_to_host(r, b, 5, nullptr, 0, r->d_valid[0], k, row_map, r->d_gather, cs))) return rc;
+        if (r->lazy_landing) {
+            RD_HIP(r, hipEventRecord(r->flat_ev, cs));  // (the scan's columns are free again behind this)
+            r->flat_pending = true;
+        }
+        if (!r->nested_state && (rc = nested_prepare(r))) return rc;
+        const ScanCtx ctx = scan_ctx();
+        uint64_t deliver = k;
+        const double t_ne = now_s();
+        trace_at("N nested begins", r->n_batches);
+        if ((rc = nested_emit(r, ctx, b, row_map, &deliver))) return rc;
+        trace_at("N nested landed", r->n_batches);
+        TRACE("nested columns (kernels + their way back)", t_ne);
+        b->n_rows = deliver;
+        if (r->lazy_landing) {
+            RD_HIP(r, hipEventCreateWithFlags(&b->landed, hipEventDisableTiming));
+            RD_HIP(r, hipEventRecord(b->landed, cs));
+            col_drain->cs = nullptr;
+        }
+        return EXG_OK;
+    }
+    // FASTA: the joined sequences
+    int fasta_sequences(hipStream_t cs) {
+        Batch *b = in.b.get();
+        // by a kernel's stores, not by a copy engine: the next batch's upload (slices that each take whichever engine is free
+        // when they are enqueued) ended up behind this copy on ITS engine every other batch and landed 5 ms late
+        // (a decoded stream: no upload beside it, the engine is faster)
+        if (switches().fasta_d2h_engine || r->src || (((uintptr_t)b->payload | (uintptr_t)r->d_payload) & 15)) {
+            RD_HIP(r, hipMemcpyAsync(b->payload, r->d_payload, res.payload_bytes, hipMemcpyDeviceToHost, cs));
+        } else if (int prc = exg::stream_to_host(b->payload, r->d_payload, res.payload_bytes, cs)) {
+            return fail(r, prc, exg_last_error_message());
+        }
+        r->host_vector_bytes += res.payload_bytes;  // (the joined sequences: the strings' payload is made on the device)
+        return EXG_OK;
+    }
+
+    // ---- 9: the position behind the batch
+    void commit_position() {
+        r->shard_first = false;
+        if (res.error_code || in.eof) {
+            r->file_done = true;
+        } else {
+            r->file_pos += res.consumed_bytes - in.lead;
+            if (in.range_end) r->file_done = true;  // what is left belongs to the next shard, whose halo reaches back to where that record begins
+        }
+    }
+};
+
+}  // namespace
+
+// Scan the next device batch of the current file.  On return r->batch holds its host vectors
+// (n_rows may be 0 when the file is exhausted).  count_only: no column leaves the device.
 int next_batch(exg_reader *r, bool count_only, uint64_t *n_records_out) {
     *n_records_out = 0;
     r->batch.reset();
@@ -606,698 +1287,55 @@ int next_batch(exg_reader *r, bool count_only, uint64_t *n_records_out) {
     if (int trc = truncated_while_read(r)) return trc;
     if (r->file_done) return EXG_OK;  // (opening the file found nothing of this shard's in it)
     if (r->format == EXG_FMT_BAM) return bam_next_batch(r, count_only, n_records_out);
-    uint64_t want = r->device_batch_bytes;
-    double t_batch = now_s();
+    BatchRun run(r, count_only);
+    const BatchIn &in = run.in;
+    const double t_batch = now_s();
     for (;;) {
-        const uint64_t remaining = r->range_hi > r->file_pos ? r->range_hi - r->file_pos : 0;
-        if (remaining == 0) {
+        int rc;
+        run.size_attempt();
+        if (in.n && r->src && (rc = run.acquire_segment())) return rc;
+        if (!in.n) {
             r->file_done = true;
             return EXG_OK;
         }
-        uint64_t n = std::min<uint64_t>(want, remaining);
-        // (the head of a text file: a small batch first — exg_reader.hpp ramp_bytes; the uploads behind it are sized where they are issued)
-        if (r->ramp_bytes && !r->src && !r->pf.valid && want == r->device_batch_bytes) n = std::min<uint64_t>(n, r->next_ramp());
-        bool range_end = n == remaining;                    // the batch reaches the end of this reader's bytes ...
-        bool eof = range_end && r->range_eof;               // ... which is the end of the file unless a later shard follows
-        // first batch of a shard that begins inside the file: up to 1 MiB in front of it travels along (`lead`), so that
-        // the record / line that ends behind the cut — it belongs to this shard — has its beginning in the buffer
-        uint64_t shard_halo = 0;
-        if (r->shard_first) {
-            const uint64_t halo_max = r->halo_want;
-            const uint64_t base = r->data_base;
-            const uint64_t from = r->file_pos - std::min<uint64_t>(halo_max, r->file_pos - base);
-            // (a buffer that already lives in HBM must be entered at a 16-byte boundary: a few bytes of the header's
-            // last line may then come along in front — they end inside the halo and are nobody's rows)
-            shard_halo = r->file_pos - (r->src ? (std::max<uint64_t>(base, from) & ~15ull) : std::max<uint64_t>(base, from & ~15ull));
-        }
-        // a decoded stream: the bytes from file_pos on (and the halo in front) made contiguous in HBM — everything up to the end of
-        // the segment that holds them is this batch
-        const uint8_t *src_at = nullptr;  // device address of stream byte src_pos
-        uint64_t src_pos = 0;
-        bool src_eof = false;
-        if (r->src) {
-            src_pos = r->file_pos - shard_halo;
-            uint64_t avail = 0;
-            std::string msg;
-            // What is asked of the stream is "the rest of the segment that holds file_pos", not a batch's worth of bytes: a
-            // segment shorter than a device batch (the first windows of a file are small on purpose: latency) used to be MERGED
-            // with the one behind it — a device copy of both, a pinned block of an odd size for the merged batch's payload
-            // (hipHostMalloc: ~1 ms per 10 MiB) and no host mirror.  Only a batch that held no complete record asks for more.
-            const uint64_t ask = (want > r->device_batch_bytes || r->format == EXG_FMT_FASTA) ? want : std::min<uint64_t>(want, 1u << 20);
-            const double t_acq = now_s();
-            int arc = r->src->acquire(src_pos, ask + shard_halo, &src_at, &avail, &src_eof, &msg);
-            TRACE("acquire(decoded segment)", t_acq);
-            trace_at("C acquired", r->n_batches);
-            if (arc) return fail(r, arc, msg + (msg.find(r->files[r->file_idx - 1]) == std::string::npos ? " in '" + r->files[r->file_idx - 1] + "'" : ""));
-            r->n_segments = r->src->segments_consumed() + 1;
-            if (avail <= shard_halo && src_eof) {  // nothing behind file_pos: the stream has ended
-                r->file_done = true;
-                return EXG_OK;
-            }
-            n = avail - shard_halo;
-            range_end = src_eof;
-            eof = range_end && r->range_eof;
-            if (r->fa_shard) {
-                // where does the first record begin that is NOT this shard's?  (mark 1: the decoded offset behind its own
-                // members / frames — while it is not set, nothing handed out so far lies behind it)
-                uint64_t own_end = 0;
-                if (r->fa_end == ~0ull && r->src->peek_mark(1, &own_end)) {
-                    if (own_end <= r->file_pos) {
-                        r->fa_end = r->file_pos;
-                    } else if (own_end < src_pos + avail) {
-                        unsigned long long pos = ~0ull;
-                        if (!r->d_phase && !(r->d_phase = dev_pool()->take(r->device, 4096))) return fail(r, EXG_E_HIP, "out of device memory");
-                        arc = exg_fasta_find_record(src_at, own_end - src_pos, avail, 0, (uint64_t *)r->d_phase, r->stream);
-                        if (arc) return fail(r, arc, exg_last_error_message());
-                        RD_HIP(r, hipMemcpyAsync(&pos, r->d_phase, 8, hipMemcpyDeviceToHost, r->stream));
-                        RD_HIP(r, hipStreamSynchronize(r->stream));
-                        if (pos != ~0ull) r->fa_end = src_pos + pos;
-                    }
-                }
-                if (r->fa_end != ~0ull) {
-                    if (r->fa_end <= r->file_pos) {
-                        r->file_done = true;
-                        return EXG_OK;
-                    }
-                    n = r->fa_end - r->file_pos;
-                    range_end = eof = true;
-                }
-            }
-        }
-        int rc = ensure_device(r, n + shard_halo + 16);
-        if (rc) return rc;
-        // Input of the scan: the inflated bytes already in HBM (gzip), the prefetched slot, or a synchronous
-        // H2D copy.  In the first two cases the batch start is only byte aligned: the buffer starts at the
-        // 16-byte boundary below it and `lead` skips the tail of the previous record (whose last '\n' is
-        // then inside the buffer).
-        // The batch about to be scanned is on its way (or there); if its upload is the one this call will use, the batch
-        // AFTER it starts travelling now, into the slot of the batch that was scanned last (free: its columns have left) —
-        // issued after this call's scan, an upload began only when the link had already been idle for a scan + a D2H.
-        static const bool no_prefetch = getenv("EXG_NO_PREFETCH") != nullptr;
-        if (!no_prefetch && r->pf.valid && !r->pf2.valid && !r->src && r->format != EXG_FMT_FASTA && want == r->device_batch_bytes &&
-            r->file_pos >= r->pf.file_start && r->file_pos < r->pf.file_start + r->pf.len && r->d_in_slot[r->pf.slot ^ 1] &&
-            !r->up_thread_of[r->pf.slot ^ 1].joinable()) {
-            const uint64_t end1 = r->pf.file_start + r->pf.len;  // where the coming batch's bytes end
-            if (end1 < r->range_hi) {
-                const uint64_t slack = std::min<uint64_t>(kPrefetchSlack, (end1 - r->file_pos) / 2);
-                const uint64_t start = (end1 - slack) & ~15ull;
-                const uint64_t len = std::min<uint64_t>(r->range_hi - start, r->next_ramp() + slack);
-                if (len + 16 <= r->d_in_cap) start_upload(r, &r->pf2, start, len, r->pf.slot ^ 1);
-            }
-        }
-        trace_at("N batch begins", r->n_batches);
-        if ((rc = r->join_prefetch())) return rc;  // the upload thread of the previous call (its error is this call's)
-        trace_at("N upload thread joined", r->n_batches);
-        const uint8_t *h = (const uint8_t *)r->file->p + r->file_pos;
-        const void *d_input = nullptr;
-        uint64_t lead = 0;
-        uint64_t batch_end = r->file_pos + n;  // file offset one past the bytes of this batch
-        std::shared_ptr<PinnedBlock> gz_payload;  // gzip: this batch's inflated bytes on the host (string_t payload)
-        std::shared_ptr<HostMirror> gz_mirror;    // ... when the producer sent them ahead (exg_rd_source.hpp); then only
-        uint64_t gz_front = 0;                    // ... the first gz_front bytes of the batch (the carried tail) are copied here
-        bool compact = false;                     // ... or: only the selected columns' out-of-line strings travel (a side buffer)
-        if (r->src) {
-            lead = shard_halo + (src_pos & 15);
-            d_input = src_at - (src_pos & 15);
-            n += lead;
-            if (r->format == EXG_FMT_FASTA) {
-                // the FASTA scan wants its batch on a 16-byte boundary with nothing in front: a device copy (the decoders
-                // in front of it run at a few percent of what a copy does)
-                if (shard_halo) return fail(r, EXG_E_INVALID_ARG, "internal: a FASTA batch has no halo");
-                n -= lead;
-                RD_HIP(r, hipMemcpyAsync(r->d_in_slot[0], src_at, n, hipMemcpyDeviceToDevice, r->stream));
-                RD_HIP(r, hipMemsetAsync((char *)r->d_in_slot[0] + n, 0, 16, r->stream));
-                r->d_in = r->d_in_slot[0];
-                d_input = r->d_in;
-                lead = 0;
-            }
-            // A projection that leaves payload-bearing columns out (SELECT name FROM read_fastq('x.fastq.gz'); chrom, pos, ref of a
-            // bgzip VCF): the decoded bytes stay in HBM, the out-of-line strings of the selected columns are closed up into a side
-            // buffer behind the scan and only that crosses PCIe (payload_*_from_col, repoint_strings).  Not when a nested VCF
-            // column is selected: its element views are cut out of the line's text by the emitter.
-            const PayloadRoute route = (!count_only && !r->arrow_emit) ? payload_route(r) : kPayloadNone;
-            compact = route == kPayloadCompact;
-            if (compact) {
-                h = (const uint8_t *)(uintptr_t)0x100000000000ull + (r->file_pos - lead);  // (a base the side buffer's pointers replace)
-            } else if (!count_only && !r->arrow_emit) {
-                // The strings of this batch point into host memory that holds the decoded bytes.  From the first such batch on
-                // the producer sends every segment to the host as it hands it over (HostMirror: the copy runs while the segment
-                // waits in the queue and while this thread is busy with the batch in front): the batch then points into that
-                // block, and only the bytes in front of the segment's own — the tail carried over from the segment before —
-                // are copied here.  A segment without a mirror (pushed before the first call, a block of the consumer's own
-                // making, FASTA) is copied behind the scan as before.
-                const uint8_t *h_at = nullptr;
-                uint64_t m_from = 0;
-                if (route == kPayloadMirror) r->src->want_host_mirror();
-                if (route == kPayloadMirror && r->src->host_view((const uint8_t *)d_input, &h_at, &m_from, &gz_mirror)) {
-                    gz_payload = gz_mirror->blk;
-                    h = h_at;
-                    gz_front = m_from > src_pos - (src_pos & 15) ? std::min<uint64_t>(n, m_from - (src_pos - (src_pos & 15))) : 0;
-                } else {
-                    gz_mirror.reset();
-                    gz_payload = std::make_shared<PinnedBlock>();
-                    size_t cap = n + 64;
-                    gz_payload->p = global_pool()->take(&cap);
-                    if (!gz_payload->p) return fail(r, EXG_E_HIP, "out of pinned host memory for the inflated bytes");
-                    gz_payload->cap = cap;
-                    gz_payload->pooled = true;
-                    gz_payload->n = n;
-                    h = (const uint8_t *)gz_payload->p;
-                }
-            } else {
-                // COUNT(*) / the Arrow stream: no host copy; h is only the base the device subtracts again
-                h = (const uint8_t *)(uintptr_t)0x100000000000ull + (r->file_pos - lead);
-            }
-        } else if (r->pf.valid && want == r->device_batch_bytes && r->file_pos >= r->pf.file_start &&
-                   r->file_pos < r->pf.file_start + r->pf.len) {
-            const uint64_t off = r->file_pos - r->pf.file_start;
-            lead = off & 15;
-            r->cur_slot = r->pf.slot;
-            r->d_in = r->d_in_slot[r->cur_slot];
-            d_input = (const uint8_t *)r->d_in + (off - lead);
-            batch_end = r->pf.file_start + r->pf.len;
-            n = batch_end - r->file_pos + lead;
-            range_end = batch_end == r->range_hi;
-            eof = range_end && r->range_eof;
-            h -= lead;
-            r->pf.valid = false;
-            RD_HIP(r, hipStreamWaitEvent(r->stream, r->up_done_of[r->cur_slot], 0));
-        } else {
-            if (r->pf.valid) RD_HIP(r, hipStreamSynchronize(r->up_stream));  // a prefetch that missed: let it land first
-            r->pf.valid = false;
-            r->d_in = r->d_in_slot[r->cur_slot];
-            lead = shard_halo;
-            int rc2;
-            if (r->format == EXG_FMT_FASTA && n > (512ull << 20)) {
-                // a whole genome in one batch: through two 256 MiB pinned windows, not one pinned block of its size
-                rc2 = upload_file(r, r->d_in, n, r->file_pos);
-                if (!rc2 && hipMemsetAsync((char *)r->d_in + n, 0, 16, r->stream) != hipSuccess)
-                    rc2 = fail(r, EXG_E_HIP, "hipMemsetAsync failed");
-            } else {
-                rc2 = upload_range(r, r->file_pos - lead, n + lead, r->cur_slot, r->stream);
-            }
-            if (rc2) return rc2;
-            d_input = r->d_in;
-            n += lead;
-            h -= lead;
-        }
-        uint64_t first_line_index = 0;
-        if (lead && r->shard_first && r->format == EXG_FMT_FASTQ) {
-            // the 4-line phase of the line that holds the shard's first byte, from the bytes around the cut ('@' opens a
-            // record but also quality lines, so several records are looked at: exg_fastq_guess_phase)
-            if (!r->d_phase && !(r->d_phase = exg_rd::dev_pool()->take(r->device, 4096))) return fail(r, EXG_E_HIP, "out of device memory");
-            uint32_t guess = 0xFFFFFFFFu;
-            rc = exg_fastq_guess_phase(d_input, n, lead, (uint32_t *)r->d_phase, r->stream);
-            if (rc) return fail(r, rc, exg_last_error_message());
-            RD_HIP(r, hipMemcpyAsync(&guess, r->d_phase, 4, hipMemcpyDeviceToHost, r->stream));
-            RD_HIP(r, hipStreamSynchronize(r->stream));
-            if (guess <= 3) {
-                uint8_t prev = 0;
-                if (r->src) {
-                    RD_HIP(r, hipMemcpyAsync(&prev, (const uint8_t *)d_input + lead - 1, 1, hipMemcpyDeviceToHost, r->stream));
-                    RD_HIP(r, hipStreamSynchronize(r->stream));
-                } else {
-                    prev = ((const uint8_t *)r->file->p)[r->file_pos - 1];
-                }
-                first_line_index = prev == '\n' ? guess : (guess + 3) % 4;
-            } else if (r->src) {
-                // a shard of a compressed input: exact when the halo begins with the file (the newlines in front are then all
-                // in HBM); else (few lines in view — records far longer than the halo — or several phases fit) the newlines in
-                // front of the shard's own bytes are counted by a decoder of their own, segment by segment
-                unsigned long long nl = 0;
-                if (r->data0_is_line_start && lead == r->file_pos) {
-                    rc = exg_count_newlines(d_input, 0, lead, (uint64_t *)r->d_phase, r->stream);
-                    if (rc) return fail(r, rc, exg_last_error_message());
-                    RD_HIP(r, hipMemcpyAsync(&nl, r->d_phase, 8, hipMemcpyDeviceToHost, r->stream));
-                    RD_HIP(r, hipStreamSynchronize(r->stream));
-                } else {
-                    if (!r->exact_nl_known) {
-                        if ((rc = count_newlines_in_front(r, &r->exact_nl))) return rc;
-                        r->exact_nl_known = true;
-                    }
-                    nl = r->exact_nl;
-                }
-                first_line_index = nl;
-            } else {
-                // too few lines around the cut to tell (a tiny file, a tiny shard) or several phases fit: count the
-                // newlines in front of it — exact, and only as slow as a memchr over the page cache
-                const char *d = (const char *)r->file->p;
-                uint64_t nl = 0;
-                for (const char *q = d, *end = d + r->file_pos; q < end;) {
-                    const void *hit = memchr(q, '\n', (size_t)(end - q));
-                    if (!hit) break;
-                    nl++;
-                    q = (const char *)hit + 1;
-                }
-                first_line_index = nl;
-            }
-        }
-        exg_scan_result res;
+        if ((rc = ensure_device(r, in.n + in.shard_halo + 16))) return rc;
+        if ((rc = run.bind_input())) return rc;
+        if ((rc = run.fastq_first_line_phase())) return rc;
         TraceRange scan_range(r->format == EXG_FMT_FASTQ ? "exg: scan fastq batch" : r->format == EXG_FMT_VCF ? "exg: scan vcf batch" : "exg: scan fasta batch");
-        const bool no_store = count_only && !r->has_filter;  // a predicate needs the columns even for COUNT(*)
-        // a line starts at d_input[0] when the batch is record aligned, or when a shard's halo reaches back to the
-        // first byte behind the header
-        const bool at_line_start = lead == 0 || (r->shard_first && shard_halo && lead == shard_halo && r->data0_is_line_start &&
-                                                 r->file_pos - lead == r->data_base);
-        const uint32_t fl = (at_line_start ? EXG_F_BOF : 0u) | (eof ? EXG_F_EOF : 0u) | (no_store ? EXG_F_NO_STORE : 0u);
-        std::shared_ptr<Batch> b;
-        bool fused_first = false;
-        std::function<int()> rescan_general;
-        if (r->format == EXG_FMT_FASTQ) {
-            exg_fastq_scan_args a;
-            memset(&a, 0, sizeof a);
-            a.d_input = d_input;
-            a.n_bytes = n;
-            a.lead = lead;
-            a.first_line_index = first_line_index;
-            a.payload_base = (uint64_t)(uintptr_t)h;
-            a.flags = fl;
-            a.algo = r->fused_algo;
-            a.d_name = (exg_string_t *)r->d_cols[0];
-            a.d_description = (exg_string_t *)r->d_cols[1];
-            a.d_sequence = (exg_string_t *)r->d_cols[2];
-            a.d_quality = (exg_string_t *)r->d_cols[3];
-            a.d_description_validity = (uint64_t *)r->d_valid[0];
-            a.capacity_records = r->cap_records;
-            a.d_workspace = r->d_ws;
-            a.workspace_bytes = r->ws_bytes;
-            a.d_result = (exg_scan_result *)r->d_res;
-            a.stream = r->stream;
-            rc = exg_fastq_scan(&a);
-            fused_first = true;
-            rescan_general = [a]() mutable {
-                a.algo = EXG_ALGO_MULTIPASS;
-                return exg_fastq_scan(&a);
-            };
-        } else if (r->format == EXG_FMT_VCF) {
-            exg_vcf_scan_args a;
-            memset(&a, 0, sizeof a);
-            a.d_input = d_input;
-            a.n_bytes = n;
-            a.lead = lead;
-            a.payload_base = (uint64_t)(uintptr_t)h;
-            a.flags = fl;
-            a.algo = r->fused_algo;
-            for (int c = 0; c < 9; c++) a.d_fields[c] = (exg_string_t *)r->d_cols[c];
-            if (!r->arrow_emit) {
-                // The projection reaches the kernel (a NULL column is skipped: 16 B per row less to write): POS / QUAL leave as
-                // numbers, their text is nobody's; CHROM / REF are written when they are selected or the predicate reads them.
-                // The other five feed the nested columns, which are built — and validated: a malformed value is the same error
-                // whether or not its column is selected — from their text
-                a.d_fields[1] = a.d_fields[5] = nullptr;
-                for (int c : {0, 3})
-                    if (!r->want(c) && !((r->filter_cols >> c) & 1ull)) a.d_fields[c] = nullptr;
-            }
-            a.d_pos = (int64_t *)r->d_pos;
-            a.d_qual = (float *)r->d_qual;
-            a.d_qual_validity = (uint64_t *)r->d_valid[0];
-            a.d_formats_validity = (uint64_t *)r->d_valid[1];
-            a.capacity_records = r->cap_records;
-            a.d_workspace = r->d_ws;
-            a.workspace_bytes = r->ws_bytes;
-            a.d_result = (exg_scan_result *)r->d_res;
-            a.stream = r->stream;
-            if (r->flat_pending) {  // (the batch before: its flat columns' copies read what this scan writes)
-                RD_HIP(r, hipStreamWaitEvent(r->stream, r->flat_ev, 0));
-                r->flat_pending = false;
-            }
-            rc = exg_vcf_scan(&a);
-            fused_first = true;
-            rescan_general = [a]() mutable {
-                a.algo = EXG_ALGO_MULTIPASS;
-                return exg_vcf_scan(&a);
-            };
-        } else {
-            b = std::make_shared<Batch>();
-            if (!count_only) {
-                b->payload = b->host.alloc(n + 64);
-                if (!b->payload) return fail(r, EXG_E_HIP, "out of pinned host memory");
-            }
-            exg_fasta_scan_args a;
-            memset(&a, 0, sizeof a);
-            a.d_input = d_input;
-            a.n_bytes = n;
-            a.payload_base = (uint64_t)(uintptr_t)h;
-            a.seq_payload_base = (uint64_t)(uintptr_t)b->payload;
-            a.flags = fl;
-            a.d_id = (exg_string_t *)r->d_cols[0];
-            a.d_description = (exg_string_t *)r->d_cols[1];
-            a.d_sequence = (exg_string_t *)r->d_cols[2];
-            a.d_description_validity = (uint64_t *)r->d_valid[0];
-            a.d_seq_payload = (uint8_t *)r->d_payload;
-            a.capacity_records = r->cap_records;
-            a.d_workspace = r->d_ws;
-            a.workspace_bytes = r->ws_bytes;
-            a.d_result = (exg_scan_result *)r->d_res;
-            a.stream = r->stream;
-            rc = exg_fasta_scan(&a);
+        if ((rc = run.scan())) return rc;
+        switch (run.judge()) {  // (the only place that scans the batch again)
+            case kAccept: break;
+            case kRetryHalo:
+                if ((rc = run.look_further_back())) return rc;
+                continue;
+            case kRetryFullWorkspace:
+                if ((rc = run.provision_again(&r->ws_full))) return rc;
+                continue;
+            case kRetryWorstCaseRows:
+                if ((rc = run.provision_again(&r->worst_case_rows))) return rc;
+                continue;
+            case kWiden: run.want *= 2; continue;
+            case kFailIndexOverflow: return fail(r, EXG_E_CAPACITY, "line index overflow in the general path (pathological line density)");
+            case kFailCapacity: return fail(r, EXG_E_CAPACITY, "more rows than bytes allow: internal error");
         }
-        if (rc) return fail(r, rc, exg_last_error_message());
-        r->n_batches++;
-        double t_scan = now_s();
-        rc = exg_fetch_result((const exg_scan_result *)r->d_res, r->stream, &res);
-        if (rc) return fail(r, rc, exg_last_error_message());
-        if (fused_first && (res.flags & EXG_RF_FALLBACK)) {
-            // (no fused launch gives a batch up any more — long records, dense halves and bytes >= 0x80 are the any-shape
-            // scan's —; should one ever say so, the general path takes the batch)
-            rc = rescan_general();
-            if (rc) return fail(r, rc, exg_last_error_message());
-            rc = exg_fetch_result((const exg_scan_result *)r->d_res, r->stream, &res);
-            if (rc) return fail(r, rc, exg_last_error_message());
-            res.flags |= EXG_RF_FALLBACK;
+        if (run.res.error_code) {
+            r->pending_error = run.res.error_code;
+            r->pending_error_offset = r->file_pos - in.lead + run.res.error_offset;
         }
-        if (res.flags & EXG_RF_REDO) {
-            // sticky (exg_reader.hpp) — when the marks are the input's shape: more than an eighth of the batch's super-tiles.  The
-            // odd long read in a short-read file is cheaper redone (its tiles only) than paid for by the any-shape scan's ~20 % on
-            // every batch behind it
-            const uint64_t tile_bytes = r->format == EXG_FMT_FASTQ ? 3u * 16384u : 2u * 16384u;
-            if (res.redo_tiles * 8 > n / tile_bytes) r->fused_algo = EXG_ALGO_FUSED_FULL;
-        }
-        if (r->format == EXG_FMT_VCF && res.n_lines) {
-            // the any-shape scan on WIDE lines (cohort VCFs) leaves the rows to a kernel of their own (EXG_ALGO_FUSED_INDEX: exg_vcf.hip):
-            // measured over line widths (tools/vcf_index_crossover.py, TB/s indexed against rows inside): level at 483 B a line, 2.72
-            // against 2.21 at 882 B, 3.13 against 2.15 at 1.7 kB, 3.82 against 2.28 at 10 kB — the switch at an average of 640 B;
-            // sticky both ways with a gap between the thresholds (EXG_NO_VCF_INDEX: never — A/B)
-            const bool no_index = getenv("EXG_NO_VCF_INDEX") != nullptr;  // (per batch: the tests switch it inside one process)
-            const uint64_t per_line = (n - lead) / res.n_lines;
-            if (r->fused_algo == EXG_ALGO_FUSED_FULL && per_line >= 640 && !no_index) r->fused_algo = EXG_ALGO_FUSED_INDEX;
-            else if (r->fused_algo == EXG_ALGO_FUSED_INDEX && per_line < 448) r->fused_algo = EXG_ALGO_FUSED_FULL;
-        }
-        TRACE("wait(h2d) + scan", t_scan);
-        trace_at("N scan result", r->n_batches);
-        if (r->shard_first && (res.flags & EXG_RF_HEAD_UNRESOLVED) && r->file_pos - shard_halo > r->data_base) {
-            // The record that ends behind the cut begins in front of the halo (a long read, a very wide VCF line): it belongs
-            // to this shard, so this shard looks further back — eight times as far, up to the first byte of the data — and
-            // scans the batch again.  (The shard in front leaves the record alone: it ends behind ITS range.)
-            RD_HIP(r, hipStreamSynchronize(r->stream));
-            r->halo_want = r->halo_want > (~0ull >> 4) ? ~0ull : r->halo_want * 8;
-            if (r->src) {
-                // a decoded stream begins with its halo: its members / frames are chosen again
-                r->src.reset();
-                r->file_idx--;
-                if ((rc = open_next_file(r))) return rc;
-            }
-            continue;
-        }
-        if ((res.flags & EXG_RF_INDEX_OVERFLOW) && r->mem_cap && !r->ws_full) {
-            RD_HIP(r, hipStreamSynchronize(r->stream));  // denser lines than the budgeted workspace indexes: the full one, same batch again
-            r->free_device();
-            r->ws_full = true;
-            continue;
-        }
-        if (res.flags & EXG_RF_INDEX_OVERFLOW)
-            return fail(r, EXG_E_CAPACITY, "line index overflow in the general path (pathological line density)");
-        if ((res.flags & EXG_RF_CAPACITY) && !no_store) {
-            if (r->worst_case_rows) return fail(r, EXG_E_CAPACITY, "more rows than bytes allow: internal error");
-            RD_HIP(r, hipStreamSynchronize(r->stream));  // denser rows than provisioned: worst-case vectors, same batch again
-            r->free_device();
-            r->worst_case_rows = true;
-            continue;
-        }
-        if (res.n_records == 0 && !res.error_code && !eof && !range_end) {
-            want *= 2;  // not even one complete record in the batch: widen it
-            continue;
-        }
-        if (res.error_code) {
-            r->pending_error = res.error_code;
-            r->pending_error_offset = r->file_pos - lead + res.error_offset;
-        }
-        double t_pf = now_s();
-        // While the columns travel back (and the consumer works through the chunks): the bytes the next batch will need
-        // move into the other slot — unless they left at the top of this call already (pf2), which is the steady state
-        {
-            // FASTA (round 6: its batches were uploaded, scanned and sent back one after the other — 22.7 GB/s end to end against
-            // FASTQ's 50): the scan wants its batch at a 16-byte boundary with nothing in front, and where the next batch begins —
-            // behind this one's last whole record — is known with the scan's result: its upload starts HERE, at exactly that file
-            // offset into the other slot's first byte (no slack, no lead), beside this batch's sequences on their way back
-            const bool fasta = r->format == EXG_FMT_FASTA;
-            const bool can = !range_end && !res.error_code && !r->src && want == r->device_batch_bytes && !no_prefetch && (!fasta || res.n_records);
-            const uint64_t slack = fasta ? 0 : std::min<uint64_t>(kPrefetchSlack, (batch_end - r->file_pos) / 2);
-            const uint64_t start = fasta ? r->file_pos + (res.consumed_bytes - lead) : (batch_end - slack) & ~15ull;
-            const int other = r->cur_slot ^ 1;
-            if (r->pf2.valid) {
-                // (its length was chosen where it was issued: a step of the ramp, or a full batch)
-                if (can && r->pf2.file_start == start && r->pf2.len > 0 && r->pf2.slot == other) {
-                    r->pf = r->pf2;
-                    r->pf2.valid = false;
-                } else {
-                    r->drop_prefetch2();  // (the batch turned out otherwise: an error, a retry, the end of the range)
-                }
-            }
-            if (can && !r->pf.valid && r->d_in_slot[other] && !r->up_thread_of[other].joinable()) {
-                const uint64_t ramp_before = r->ramp_bytes;
-                const uint64_t len = std::min<uint64_t>(r->range_hi - start, r->next_ramp() + slack);
-                if (len + 16 <= r->d_in_cap) start_upload(r, &r->pf, start, len, other);
-                else r->ramp_bytes = ramp_before;
-            }
-        }
+        const double t_pf = now_s();
+        run.prefetch_next();
         TRACE("prefetch issue", t_pf);
-        uint64_t k = res.n_records;
-        const uint32_t *row_map = nullptr;
-        if (r->has_filter && k && !r->arrow_emit) {
-            // rows where the predicate is TRUE -> row map; the columns are gathered through it on their way out
-            namespace ea = exg::arrow;
-            ea::FilterCols fc;
-            memset(&fc, 0, sizeof fc);
-            const int nsc = n_string_cols(r->format);
-            for (int c = 0; c < nsc; c++) {
-                fc.kind[c] = ea::kColStr;
-                fc.data[c] = r->d_cols[c];
-                fc.d_base[c] = (const uint8_t *)d_input;
-                fc.payload_base[c] = (uint64_t)(uintptr_t)h;
-            }
-            if (r->format == EXG_FMT_VCF) {
-                fc.kind[1] = ea::kColI64, fc.data[1] = r->d_pos;
-                fc.kind[5] = ea::kColF32, fc.data[5] = r->d_qual, fc.validity[5] = (const uint64_t *)r->d_valid[0];
-                fc.validity[8] = (const uint64_t *)r->d_valid[1];
-            } else {
-                fc.validity[1] = (const uint64_t *)r->d_valid[0];
-                if (r->format == EXG_FMT_FASTA) {
-                    fc.d_base[2] = (const uint8_t *)r->d_payload;
-                    fc.payload_base[2] = (uint64_t)(uintptr_t)(b ? b->payload : nullptr);
-                }
-            }
-            uint64_t *d_goff = (uint64_t *)r->d_filter_tmp, *d_tmp = d_goff + r->cap_records + 1;
-            ea::FilterCols *d_fc = (ea::FilterCols *)r->d_gather;  // the scratch column is free until the gathers
-            RD_HIP(r, hipMemcpyAsync(d_fc, &fc, sizeof fc, hipMemcpyHostToDevice, r->stream));
-            ea::filter_rows((const ea::FilterProgram *)r->d_filter_prog, d_fc, (const uint8_t *)r->d_filter_consts, k, d_goff,
-                            d_tmp, (uint32_t *)r->d_row_map, r->stream);
-            uint64_t n_sel = 0;
-            RD_HIP(r, hipMemcpyAsync(&n_sel, d_goff + k, 8, hipMemcpyDeviceToHost, r->stream));
-            RD_HIP(r, hipStreamSynchronize(r->stream));
-            k = n_sel;
-            row_map = (const uint32_t *)r->d_row_map;
-        }
-        *n_records_out = k;
-        if (r->arrow_emit && !count_only) {
-            // new_reader: the columns stay in HBM and become Arrow buffers there (exg_arrow_stream.cpp)
-            ScanCtx ctx;
-            ctx.d_input = d_input;
-            ctx.h = h;
-            ctx.n_records = k;
-            ctx.res = res;
-            ctx.h_seq_payload = b ? (const uint8_t *)b->payload : nullptr;
-            double t_emit = now_s();
-            if (k && (rc = r->arrow_emit(r, ctx))) return rc;
-            TRACE("arrow emit", t_emit);
-        } else if (k && !count_only) {
-            TraceRange d2h_range("exg: columns -> host");
-            if (!b) b = std::make_shared<Batch>();
-            b->host.reserve(r->host_hint);
-            b->file = gz_payload ? gz_payload : r->file;
-            // the projection (exg_open_args.columns): every column was parsed and validated above, only the wanted ones travel.
-            // A decoded input's bytes are what its strings point into: they travel when any string column does
-            const bool any_strings = r->format == EXG_FMT_VCF ? (r->want_cols & 0x1DDull) != 0 : (r->want_cols & ((1ull << n_string_cols(r->format)) - 1)) != 0;
-            if (gz_payload && any_strings && !gz_mirror) RD_HIP(r, hipMemcpyAsync(gz_payload->p, d_input, n, hipMemcpyDeviceToHost, r->stream));
-            if (gz_mirror && gz_front) RD_HIP(r, hipMemcpyAsync(const_cast<uint8_t *>(h), d_input, gz_front, hipMemcpyDeviceToHost, r->stream));
-            b->n_rows = k;
-            const int ns = n_string_cols(r->format);
-            // compact: the selected string columns' out-of-line bytes, closed up per column into ONE side buffer
-            struct SideCol {
-                uint64_t *d_goff = nullptr;
-                uint64_t total = 0, off = 0;
-            } side[9];
-            struct SideScratch {  // pooled device scratch of this batch's side buffer
-                int dev;
-                hipStream_t st;
-                std::vector<std::pair<void *, size_t>> blocks;
-                void *take(size_t n) {
-                    void *p = dev_pool()->take(dev, n);
-                    if (p) blocks.emplace_back(p, n);
-                    return p;
-                }
-                ~SideScratch() {
-                    if (!blocks.empty()) (void)hipStreamSynchronize(st);  // (an early return: kernels may still read them)
-                    for (auto &bl : blocks) dev_pool()->give(dev, bl.first, bl.second);
-                }
-            } side_scratch{r->device, r->stream, {}};
-            uint8_t *h_side = nullptr, *d_side = nullptr;
-            if (compact) {
-                namespace ea = exg::arrow;
-                uint64_t *d_tmp = (uint64_t *)side_scratch.take((ea::scan_tmp_entries(k) + 2) * 8);
-                if (!d_tmp) return fail(r, EXG_E_HIP, "out of device memory");
-                for (int c = 0; c < ns; c++) {
-                    if (!r->want(c) || (r->format == EXG_FMT_VCF && c != 0 && c != 3) || (r->format == EXG_FMT_FASTA && c == 2)) continue;
-                    if (!(side[c].d_goff = (uint64_t *)side_scratch.take((k + 2) * 8))) return fail(r, EXG_E_HIP, "out of device memory");
-                    const ea::StrCol sc{(const exg_string_t *)r->d_cols[c], (const uint8_t *)d_input, (uint64_t)(uintptr_t)h};
-                    ea::payload_goff_from_col(sc, row_map, k, side[c].d_goff, d_tmp, r->stream);
-                    RD_HIP(r, hipMemcpyAsync(&side[c].total, side[c].d_goff + k, 8, hipMemcpyDeviceToHost, r->stream));
-                }
-                RD_HIP(r, hipStreamSynchronize(r->stream));
-                uint64_t side_total = 0;
-                for (int c = 0; c < ns; c++) side[c].off = side_total, side_total += (side[c].total + 15) & ~15ull;
-                if (side_total) {
-                    if (!(h_side = (uint8_t *)b->host.alloc(side_total + 64))) return fail(r, EXG_E_HIP, "out of pinned host memory");
-                    const uint32_t big_cap = (uint32_t)(side_total / 8192 + 1);
-                    uint32_t *d_big = (uint32_t *)side_scratch.take(4 * ((size_t)big_cap + 1));
-                    if (!(d_side = (uint8_t *)side_scratch.take(side_total + 64)) || !d_big) return fail(r, EXG_E_HIP, "out of device memory");
-                    for (int c = 0; c < ns; c++) {
-                        if (!side[c].d_goff || !side[c].total) continue;
-                        const ea::StrCol sc{(const exg_string_t *)r->d_cols[c], (const uint8_t *)d_input, (uint64_t)(uintptr_t)h};
-                        ea::payload_copy_from_col(sc, row_map, k, side[c].d_goff, d_side + side[c].off, d_big, big_cap, r->stream);
-                    }
-                    RD_HIP(r, hipMemcpyAsync(h_side, d_side, side_total, hipMemcpyDeviceToHost, r->stream));
-                }
-            }
-            // schema order (exg_schema_of): VCF exposes parsed POS / QUAL in place of their raw text
-            b->n_cols = ns;
-            const size_t vw = (size_t)((k + 63) / 64) * 8;
-            // read_vcf: behind the flat columns come the nested ones' kernels (nested_emit: dozens of small launches that build — or,
-            // for columns the projection leaves out, only validate — id / alt / filter / info / formats).  In one stream the
-            // 200 MB of flat vectors (3.7 ms of the link) stood in front of them; on a stream of their own the copies run beside
-            // them (chrom, pos, ref of a 2 GB file: 70.6 -> 49.4 ms = 42 GB/s, COUNT(*) 47 ms: A/B in one box, EXG_VCF_ONE_STREAM)
-            hipStream_t cs = r->stream;
-            // (whatever way this block is left once copies are on the columns' stream: they have landed — or the batch carries the
-            // event that says when — before its pinned blocks can go back to the pool)
-            struct ColDrain {
-                hipStream_t cs = nullptr;
-                ~ColDrain() {
-                    if (cs) (void)hipStreamSynchronize(cs);
-                }
-            } col_drain;
-            // (FASTA, round 6: its joined sequences are as many bytes as the batch itself — on the scan's stream they shared a copy
-            // engine with the next batch's upload, which landed 5 ms behind them: 9.7 ms per 256 MiB batch where the two directions
-            // should overlap)
-            static const bool fastq_cols_on_scan_stream = getenv("EXG_FASTQ_ONE_STREAM") != nullptr;  // (A/B)
-            if ((r->format == EXG_FMT_VCF || r->format == EXG_FMT_FASTA || (!r->src && !fastq_cols_on_scan_stream)) && !compact && !getenv("EXG_VCF_ONE_STREAM")) {
-                if (!r->col_stream) {
-                    RD_HIP(r, stream_pool()->take_d2h(r->device, &r->col_stream, /*calibrate=*/r->file && r->file->n >= (512ull << 20) && !r->mem_cap));
-                    RD_HIP(r, hipEventCreateWithFlags(&r->col_ev, hipEventDisableTiming));
-                    RD_HIP(r, hipEventCreateWithFlags(&r->flat_ev, hipEventDisableTiming));
-                }
-                RD_HIP(r, hipEventRecord(r->col_ev, r->stream));          // (the scan, the predicate's row map)
-                RD_HIP(r, hipStreamWaitEvent(r->col_stream, r->col_ev, 0));
-                cs = r->col_stream;
-                col_drain.cs = cs;
-            }
-            // read_vcf hands its batch on while the vectors are still travelling (Batch::landed): the batch behind it — upload wait,
-            // scan, the nested columns' kernels — is made beside them, and the link back to the host does not idle between batches
-            static const bool eager_landing = getenv("EXG_VCF_EAGER_LANDING") != nullptr;
-            r->lazy_landing = r->format == EXG_FMT_VCF && cs == r->col_stream && cs != r->stream && !eager_landing;
-            const bool nested_vcf = r->format == EXG_FMT_VCF;  // id, alt, filter, info, formats: built by nested_emit below
-            for (int c = 0; c < ns; c++) {
-                if ((nested_vcf && (c == 2 || c == 4 || c >= 6)) || !r->want(c)) {
-                    b->elem[c] = 0;
-                    b->cols[c] = nullptr;
-                    continue;
-                }
-                const void *src = r->d_cols[c];
-                uint32_t es = 16;
-                if (r->format == EXG_FMT_VCF && c == 1) src = r->d_pos, es = 8;
-                if (r->format == EXG_FMT_VCF && c == 5) src = r->d_qual, es = 4;
-                b->elem[c] = es;
-                if (!(b->cols[c] = b->host.alloc(k * es))) return fail(r, EXG_E_HIP, "out of pinned host memory");
-                if (compact && es == 16 && side[c].d_goff) {
-                    // (gathers through the row map itself; in place without one: the column is the scan's scratch from here on)
-                    void *dst = row_map ? r->d_gather : r->d_cols[c];
-                    exg::arrow::repoint_strings((const exg_string_t *)r->d_cols[c], row_map, k, side[c].d_goff, (uint64_t)(uintptr_t)(h_side + side[c].off),
-                                                (exg_string_t *)dst, r->stream);
-                    src = dst;
-                } else if (row_map) {
-                    if (es == 16)
-                        exg::arrow::gather_u128(src, row_map, k, r->d_gather, cs);
-                    else if (es == 8)
-                        exg::arrow::gather_u64((const uint64_t *)src, row_map, k, (uint64_t *)r->d_gather, cs);
-                    else
-                        exg::arrow::gather_u32((const uint32_t *)src, row_map, k, (uint32_t *)r->d_gather, cs);
-                    src = r->d_gather;
-                }
-                RD_HIP(r, hipMemcpyAsync(b->cols[c], src, k * es, hipMemcpyDeviceToHost, compact && es == 16 && side[c].d_goff ? r->stream : cs));
-                r->host_vector_bytes += k * es;
-            }
-            auto copy_validity = [&](int col, const void *d) -> int {
-                if (!(b->validity[col] = b->host.alloc(vw))) return fail(r, EXG_E_HIP, "out of pinned host memory");
-                if (row_map) {
-                    exg::arrow::gather_bits((const uint64_t *)d, row_map, k, (uint64_t *)r->d_gather, cs);
-                    d = r->d_gather;
-                }
-                RD_HIP(r, hipMemcpyAsync(b->validity[col], d, vw, hipMemcpyDeviceToHost, cs));
-                r->host_vector_bytes += vw;
-                return EXG_OK;
-            };
-            if (r->format == EXG_FMT_VCF) {
-                if (r->want(5) && (rc = copy_validity(5, r->d_valid[0]))) return rc;
-                if (r->lazy_landing) {
-                    RD_HIP(r, hipEventRecord(r->flat_ev, cs));  // (the scan's columns are free again behind this)
-                    r->flat_pending = true;
-                }
-                if (!r->nested_state && (rc = nested_prepare(r))) return rc;
-                ScanCtx ctx;
-                ctx.d_input = d_input;
-                ctx.h = h;
-                ctx.n_records = k;
-                ctx.res = res;
-                ctx.h_seq_payload = nullptr;
-                uint64_t deliver = k;
-                const double t_ne = now_s();
-                trace_at("N nested begins", r->n_batches);
-                if ((rc = nested_emit(r, ctx, b.get(), row_map, &deliver))) return rc;
-                trace_at("N nested landed", r->n_batches);
-                TRACE("nested columns (kernels + their way back)", t_ne);
-                b->n_rows = deliver;
-                if (r->lazy_landing) {
-                    RD_HIP(r, hipEventCreateWithFlags(&b->landed, hipEventDisableTiming));
-                    RD_HIP(r, hipEventRecord(b->landed, cs));
-                    col_drain.cs = nullptr;
-                }
-            } else {
-                if (r->want(1) && (rc = copy_validity(1, r->d_valid[0]))) return rc;
-            }
-            if (r->format == EXG_FMT_FASTA && res.payload_bytes && r->want(2)) {
-                // by a kernel's stores, not by a copy engine: the next batch's upload (slices that each take whichever engine is free
-                // when they are enqueued) ended up behind this copy on ITS engine every other batch and landed 5 ms late
-                static const bool by_engine = getenv("EXG_FASTA_D2H_ENGINE") != nullptr;  // (A/B)
-                if (by_engine || r->src || (((uintptr_t)b->payload | (uintptr_t)r->d_payload) & 15)) {  // (a decoded stream: no upload beside it, the engine is faster)
-                    RD_HIP(r, hipMemcpyAsync(b->payload, r->d_payload, res.payload_bytes, hipMemcpyDeviceToHost, cs));
-                } else if (int prc = exg::stream_to_host(b->payload, r->d_payload, res.payload_bytes, cs)) {
-                    return fail(r, prc, exg_last_error_message());
-                }
-                r->host_vector_bytes += res.payload_bytes;  // (the joined sequences: the strings' payload is made on the device)
-            }
-            const double t_cols = now_s();
-            RD_HIP(r, hipStreamSynchronize(r->stream));
-            if (r->col_stream && !b->landed) RD_HIP(r, hipStreamSynchronize(r->col_stream));
-            col_drain.cs = nullptr;
-            TRACE("wait(columns -> host)", t_cols);
-            const double t_mir = now_s();
-            if (gz_mirror) RD_HIP(r, hipEventSynchronize(gz_mirror->ev));  // the segment's own bytes have arrived
-            if (gz_mirror) TRACE("wait(host mirror of the segment)", t_mir);
-            trace_at("C batch-done", r->n_batches);
-            r->host_hint = b->host.total + b->host.total / 8 + (1u << 20);
-            b->seq = r->batch_seq++;
-            r->batch = b;
-        }
-        r->shard_first = false;
-        if (res.error_code || eof) {
-            r->file_done = true;
-        } else {
-            r->file_pos += res.consumed_bytes - lead;
-            if (range_end) r->file_done = true;  // what is left belongs to the next shard, whose halo reaches back to where that record begins
-        }
+        run.k = run.res.n_records;
+        if (r->has_filter && run.k && !r->arrow_emit && (rc = run.select_rows())) return rc;
+        *n_records_out = run.k;
+        if (r->arrow_emit && !count_only) rc = run.arrow_emit();
+        else rc = run.k && !count_only ? run.columns_to_host() : EXG_OK;
+        if (rc) return rc;
+        run.commit_position();
         TRACE("batch (h2d+scan+d2h)", t_batch);
         if (trace_on())
             fprintf(stderr, "[exg] device bytes held: %.2f MiB now, %.2f MiB at the peak (batch of %llu bytes, %llu rows)\n", r->meter.cur.load() / 1048576.0,
-                    r->meter.peak.load() / 1048576.0, (unsigned long long)n, (unsigned long long)k);
+                    r->meter.peak.load() / 1048576.0, (unsigned long long)in.n, (unsigned long long)run.k);
         return EXG_OK;
     }
 }

@@ -7,7 +7,9 @@
 //   exg_rd_gzip.cpp    the gzip / BGZF producer;  exg_rd_zstd.cpp  the zstd producer;  exg_rd_bzip2.cpp  the bzip2 producer
 //   exg_zstd_index.cpp host only: the zstd frame / block walk and a round's block list (no HIP call; under ASan as above)
 //   exg_rd_fanout.cpp  host only: stripes of one input read by worker threads on N devices (exg_rd_fanout.hpp)
-//   exg_rd_batch.cpp   open_next_file, next_batch: one device batch -> host vectors
+//   exg_rd_batch.cpp   open_next_file, next_batch: one device batch -> host vectors, as a driver over named stages
+//   exg_rd_stages.hpp  host only: the stages' decisions that make no HIP call — attempt size and halo, the upload window, what a
+//                      scan's result means (under ASan as above)
 //   exg_reader.cpp     the C entry points (exg_open ... exg_close) and the chunk slicing
 #pragma once
 #include <stdio.h>
@@ -101,6 +103,28 @@ struct PoolBuf {
     }
     ~PoolBuf() { release(); }
 };
+struct SideScratch {  // pooled device scratch of one batch's side buffer (next_batch: the compact payload route)
+    int dev;
+    hipStream_t st;
+    std::vector<std::pair<void *, size_t>> blocks;
+    void *take(size_t n) {
+        void *p = dev_pool()->take(dev, n);
+        if (p) blocks.emplace_back(p, n);
+        return p;
+    }
+    ~SideScratch() {
+        if (!blocks.empty()) (void)hipStreamSynchronize(st);  // (an early return: kernels may still read them)
+        for (auto &bl : blocks) dev_pool()->give(dev, bl.first, bl.second);
+    }
+};
+// (whatever way next_batch's columns -> host is left once copies are on the columns' stream: they have landed — or the batch
+// carries the event that says when — before its pinned blocks can go back to the pool)
+struct ColDrain {
+    hipStream_t cs = nullptr;
+    ~ColDrain() {
+        if (cs) (void)hipStreamSynchronize(cs);
+    }
+};
 
 // bytes in front of a shard that travel with its first batch (the beginning of the record that ends behind the cut);
 // grown by the reader when the record turns out to begin further back
@@ -142,6 +166,10 @@ void start_upload(exg_reader *r, exg_reader::Prefetch *which, uint64_t start, ui
 // fd bytes [off, off + n) -> host memory `dst` by up to 8 threads pinned to the device's NUMA node; when d_dst != NULL every
 // slice is sent on to d_dst + (its offset) on `st` as soon as it has been read.  false: short read (*hip_failed: a copy failed)
 bool pread_parallel(int device, int fd, uint64_t off, size_t n, char *dst, char *d_dst, hipStream_t st, bool *hip_failed);
+// Column c of a batch's k rows -> pinned vectors of `b` on `st`: its values (d_col, `es` = 4, 8 or 16 bytes each; NULL: none)
+// and its validity bits (d_valid; NULL: none), each gathered through row_map into d_gather first when there is one
+int column_to_host(exg_reader *r, Batch *b, int c, const void *d_col, uint32_t es, const void *d_valid, uint64_t k, const uint32_t *row_map,
+                   void *d_gather, hipStream_t st);
 
 // ---- exg_rd_bgzf.cpp (host only)
 // The few bytes the BGZF walk looks at — a member's header, the trailer right in front of the next header — read with pread

@@ -15,6 +15,7 @@
 #include <atomic>
 #include <thread>
 
+#include "exg_arrow.hpp"
 #include "exg_rd_fanout.hpp"
 #include "exg_map_guard.hpp"
 #include "exg_rd_source.hpp"
@@ -481,6 +482,33 @@ void start_upload(exg_reader *r, exg_reader::Prefetch *which, uint64_t start, ui
     which->file_start = start;
     which->len = len;
     which->slot = slot;
+}
+
+int column_to_host(exg_reader *r, Batch *b, int c, const void *d_col, uint32_t es, const void *d_valid, uint64_t k, const uint32_t *row_map,
+                   void *d_gather, hipStream_t st) {
+    namespace ea = exg::arrow;
+    if (d_col) {
+        if (!(b->cols[c] = b->host.alloc(k * es))) return fail(r, EXG_E_HIP, "out of pinned host memory");
+        if (row_map) {
+            if (es == 16) ea::gather_u128(d_col, row_map, k, d_gather, st);
+            else if (es == 8) ea::gather_u64((const uint64_t *)d_col, row_map, k, (uint64_t *)d_gather, st);
+            else ea::gather_u32((const uint32_t *)d_col, row_map, k, (uint32_t *)d_gather, st);
+            d_col = d_gather;
+        }
+        RD_HIP(r, hipMemcpyAsync(b->cols[c], d_col, k * es, hipMemcpyDeviceToHost, st));
+        r->host_vector_bytes += k * es;
+    }
+    if (d_valid) {
+        const size_t vw = (size_t)((k + 63) / 64) * 8;
+        if (!(b->validity[c] = b->host.alloc(vw))) return fail(r, EXG_E_HIP, "out of pinned host memory");
+        if (row_map) {
+            ea::gather_bits((const uint64_t *)d_valid, row_map, k, (uint64_t *)d_gather, st);
+            d_valid = d_gather;
+        }
+        RD_HIP(r, hipMemcpyAsync(b->validity[c], d_valid, vw, hipMemcpyDeviceToHost, st));
+        r->host_vector_bytes += vw;
+    }
+    return EXG_OK;
 }
 
 }  // namespace exg_rd

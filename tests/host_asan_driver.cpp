@@ -2,7 +2,8 @@
 // -fsanitize=address,undefined and runs it): the gzip member index (exg_gzip.cpp), the BGZF member walk of the streaming
 // reader (exg_rd_bgzf.cpp), the zstd frame / block walk (exg_zstd_index.cpp), the VCF header parser (exg_vcf_header.cpp)
 // and the `filters` parser (exg_filter.hpp) on valid inputs, on truncations of them and on random mutations — every byte
-// these parsers read comes from a user's file or query text.
+// these parsers read comes from a user's file or query text.  Also what else of the host path makes no HIP call: next_batch's
+// decisions (exg_rd_stages.hpp), the shard planner, the pinned-block pool, the map guard, the fan-out's run-ahead.
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -10,6 +11,7 @@
 #include <unistd.h>
 #include <time.h>
 
+#include <algorithm>
 #include <random>
 #include <string>
 #include <vector>
@@ -18,6 +20,7 @@
 #include "exg_filter.hpp"
 #include "exg_rd_fanout.hpp"
 #include "exg_rd_internal.hpp"
+#include "exg_rd_stages.hpp"
 #include "exg_vcf_header.hpp"
 #include "exg_xxh64.hpp"
 #include <sys/mman.h>
@@ -285,6 +288,94 @@ int main(int argc, char **argv) {
     for (int i = 0; i < 100; i++) big += " AND pos>" + std::to_string(i);
     exg_rd::FilterParser fp(big, cols);
     if (fp.parse()) return 4;
+    // the decisions of next_batch that make no HIP call (exg_rd_stages.hpp)
+    {
+        using namespace exg_rd;
+        // what a scan's result means: every combination of the flags and the state the judge reads.  The expected verdict is the
+        // first row of this table that matches — the reader's precedence: head unresolved, index overflow, capacity, widen
+        enum { HU = 1, IO = 2, CAP = 4, NOREC = 8, ERR = 16, MEMCAP = 32, WSFULL = 64, WORST = 128, NOSTORE = 256, FIRST = 512, EOF_ = 1024, REND = 2048, ATBASE = 4096, ALL = 8192 };
+        const struct { unsigned care, is; BatchVerdict v; } rows[] = {
+            {HU | FIRST | ATBASE, HU | FIRST, kRetryHalo},
+            {IO | MEMCAP | WSFULL, IO | MEMCAP, kRetryFullWorkspace},
+            {IO, IO, kFailIndexOverflow},
+            {CAP | NOSTORE | WORST, CAP | WORST, kFailCapacity},
+            {CAP | NOSTORE, CAP, kRetryWorstCaseRows},
+            {NOREC | ERR | EOF_ | REND, NOREC, kWiden},
+            {0, 0, kAccept},
+        };
+        auto verdict_of = [](unsigned m) {
+            const JudgeState s = {(m & MEMCAP) != 0, (m & WSFULL) != 0, (m & WORST) != 0, (m & NOSTORE) != 0, (m & FIRST) != 0, (m & EOF_) != 0, (m & REND) != 0, (m & ATBASE) != 0};
+            const uint32_t flags = (m & HU ? EXG_RF_HEAD_UNRESOLVED : 0u) | (m & IO ? EXG_RF_INDEX_OVERFLOW : 0u) | (m & CAP ? EXG_RF_CAPACITY : 0u) |
+                                   EXG_RF_NON_ASCII | EXG_RF_REDO;  // (flags the judge does not read)
+            return judge_batch(flags, m & NOREC ? 0 : 5, m & ERR ? 3 : 0, s);
+        };
+        for (unsigned m = 0; m < ALL; m++) {
+            BatchVerdict want = kAccept;
+            for (const auto &row : rows)
+                if ((m & row.care) == row.is) {
+                    want = row.v;
+                    break;
+                }
+            if (verdict_of(m) != want) return 14;
+            runs++;
+        }
+        // ... and a few spelt out: everything at once looks further back first; a halo that is at the data's first byte already does
+        // not; COUNT(*) ignores the rows' capacity and widens an empty batch; an error, the end of the range or of the file never widens
+        if (verdict_of(HU | IO | CAP | NOREC | MEMCAP | FIRST) != kRetryHalo) return 14;
+        if (verdict_of(HU | IO | CAP | NOREC | MEMCAP | FIRST | ATBASE) != kRetryFullWorkspace) return 14;
+        if (verdict_of(HU | IO | MEMCAP | WSFULL) != kFailIndexOverflow || verdict_of(IO) != kFailIndexOverflow) return 14;
+        if (verdict_of(CAP | NOREC | NOSTORE) != kWiden || verdict_of(CAP | NOREC) != kRetryWorstCaseRows || verdict_of(CAP | WORST) != kFailCapacity) return 14;
+        if (verdict_of(NOREC | ERR) != kAccept || verdict_of(NOREC | EOF_ | REND) != kAccept || verdict_of(NOREC | REND) != kAccept || verdict_of(0) != kAccept) return 14;
+        // the halo of a shard's first batch.  A mapped file is entered anywhere (the upload's start is rounded down, never below the
+        // data's first byte); a decoded stream lives in HBM and is entered at a 16-byte boundary.  Where the data begin at such a
+        // boundary neither reaches in front of them; where they do not (a VCF header of any length in front), a decoded stream's halo
+        // may take up to 15 bytes of the header's last line along — they end inside the halo and are nobody's rows
+        for (const uint64_t data_base : {(uint64_t)0, (uint64_t)4096, (uint64_t)1003})
+            for (const uint64_t past : {0, 1, 15, 16, 17, 5000})
+                for (const uint64_t halo_want : {(uint64_t)16, (uint64_t)4096, ~(uint64_t)0})
+                    for (const bool decoded : {false, true}) {
+                        const uint64_t file_pos = data_base + past;
+                        const uint64_t halo = shard_halo_bytes(file_pos, data_base, halo_want, decoded), start = file_pos - halo;
+                        if (halo > file_pos) return 15;
+                        if (data_base % 16 == 0 || !decoded) {
+                            if (halo > file_pos - data_base) return 15;
+                        } else if (start + 15 < data_base) {
+                            return 15;
+                        }
+                        if (decoded && start % 16) return 15;
+                        if (halo < std::min<uint64_t>(halo_want, past)) return 15;  // (it reaches back as far as asked, or to the data's first byte)
+                        const AttemptSize a = size_attempt(1u << 20, file_pos, file_pos + 100, true, ~0ull, true, data_base, halo_want, decoded);
+                        if (a.shard_halo != halo || a.n != 100 || !a.range_end || !a.eof) return 15;
+                        if (size_attempt(1u << 20, file_pos, file_pos + 100, true, ~0ull, false, data_base, halo_want, decoded).shard_halo) return 15;
+                        runs++;
+                    }
+        if (grow_halo(16) != 128 || grow_halo(~0ull >> 4) != (~0ull >> 4) * 8 || grow_halo((~0ull >> 4) + 1) != ~0ull || grow_halo(~0ull >> 1) != ~0ull ||
+            grow_halo(~0ull) != ~0ull)
+            return 15;
+        {   // the size of an attempt: the range's end, the ramp's step, nothing left
+            const AttemptSize a = size_attempt(256, 1000, 2000, false, ~0ull, false, 0, 0, false), b = size_attempt(256, 1900, 2000, false, ~0ull, false, 0, 0, false);
+            if (a.n != 256 || a.range_end || a.eof || b.n != 100 || !b.range_end || b.eof) return 15;
+            if (size_attempt(256, 1000, 2000, true, 32, false, 0, 0, false).n != 32 || size_attempt(256, 2000, 2000, true, ~0ull, true, 0, 16, false).n != 0) return 15;
+        }
+        // the file bytes an upload ahead carries: [start, start + len) ends inside the reader's range and fits an input slot (or there
+        // is no upload), begins at a 16-byte boundary inside the batch in front — but where the FASTA scan says the next record begins
+        const uint64_t range_hi = (1ull << 30) + 5, step = 32u << 20;
+        for (const uint64_t below : {(uint64_t)0, (uint64_t)1, (uint64_t)(1u << 20)})
+            for (const uint64_t batch : {(uint64_t)(64u << 20) + 3, (uint64_t)kPrefetchSlack * 2 - 9, (uint64_t)4097, (uint64_t)1})
+                for (const uint64_t d_in_cap : {step + kPrefetchSlack + 64, step, (uint64_t)4096}) {
+                    const uint64_t end1 = range_hi - below, begin = end1 - batch;
+                    const PrefetchWindow w = prefetch_window(begin, end1, kPrefetchSlack);
+                    const uint64_t len = w.len(range_hi, step, d_in_cap);
+                    if (w.start % 16 || w.slack > kPrefetchSlack || w.slack > batch / 2 || w.start > end1 - w.slack || w.start + 15 < end1 - w.slack) return 16;
+                    if (len && (w.start + len > range_hi || len + 16 > d_in_cap)) return 16;
+                    if (!len && std::min<uint64_t>(range_hi - w.start, step + w.slack) + 16 <= d_in_cap) return 16;  // (refused only for lack of room)
+                    const PrefetchWindow f = prefetch_window(begin, end1, kPrefetchSlack, begin + batch / 3);
+                    const uint64_t flen = f.len(range_hi, step, d_in_cap);
+                    if (f.start != begin + batch / 3 || f.slack != 0) return 16;
+                    if (flen && (f.start + flen > range_hi || flen + 16 > d_in_cap || flen > step)) return 16;
+                    runs++;
+                }
+    }
     // host XXH64 (the checksum of big zstd frames): the specification's known answers, and any way of cutting the input
     // into updates gives the one-shot digest
     {

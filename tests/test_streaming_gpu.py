@@ -289,3 +289,56 @@ def test_bgzf_shard_whose_phase_is_counted_holds_no_prefix(gpu, oracle, tmp_path
     rows, peaks = _shard_rows(p, "fastq", 5)
     assert rows == want
     assert max(peaks) <= (4 * CAP_MB) << 20, [x >> 20 for x in peaks]
+
+
+def _rows_then_error(path, fmt):
+    """(the rows that arrive, the message of the error behind them or None)"""
+    import ctypes as C
+
+    from exon_duckdb_amd import ExgError, reader as rd
+    r = _open(path, fmt)
+    rows, msg = [], None
+    try:
+        while True:
+            ch = rd.Chunk()
+            rc = r._l.exg_next_chunk(r._r, C.byref(ch))
+            if rc != 0:
+                r._fail(rc)
+            if int(ch.n_rows) == 0:
+                break
+            rows.extend(zip(*[rd.decode_vector(ch.vectors[k].contents, r.trees[k]) for k in range(len(r.names))]))
+            r._l.exg_release_chunk(r._r, C.byref(ch))
+    except ExgError as e:
+        msg = str(e)
+    batches = r.stats()["device_batches"]
+    r.close()
+    return rows, msg, batches
+
+
+@pytest.mark.parametrize("batch", [0, 65536])
+@pytest.mark.parametrize("shape", ["fastq-5-bytes", "fastq-6-bytes", "vcf-2-bytes"])
+def test_rows_denser_than_the_vectors_are_provisioned_for(gpu, oracle, tmp_path, monkeypatch, shape, batch):
+    """The row vectors are provisioned for one FASTQ record per 32 bytes and one VCF line per 16; a denser batch is scanned again
+    with vectors for the worst case (EXG_RF_CAPACITY).  200 000 FASTQ records of 5 bytes ("@", "", "+": the fourth line is the
+    next record's "@" — one row, then an error, for the oracle as well) and of 6 (well formed: every row), 100 000 VCF lines
+    of 2 bytes behind a minimal header (an error at the first): the oracle's rows, then the oracle's error."""
+    if batch:
+        monkeypatch.setenv("EXG_DEVICE_BATCH_BYTES", str(batch))
+    if shape.startswith("fastq"):
+        fmt, data = "fastq", (b"@\n\n+\n" if shape == "fastq-5-bytes" else b"@\n\n+\n\n") * 200000
+        exp = oracle.fastq_parse(data, want_string_t=False)
+        want = list(zip(*[exp.columns[c].to_list() for c in ["name", "description", "sequence", "quality_scores"]]))
+    else:
+        fmt, data = "vcf", b"##fileformat=VCFv4.2\n#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n" + b"a\n" * 100000
+        exp = oracle.vcf_parse(data, want_string_t=False)
+        want = []
+        assert exp.n_rows == 0 and exp.error_code
+    p = tmp_path / ("dense." + fmt)
+    p.write_bytes(data)
+    rows, msg, batches = _rows_then_error(p, fmt)
+    print(shape, batch, "rows", len(rows), "error", msg, "device batches", batches)
+    assert len(rows) == exp.n_rows and rows == want
+    if exp.error_code:
+        assert msg and exp.error_message in msg and f"at byte {exp.error_offset} " in msg, (msg, exp.error_message, exp.error_offset)
+    else:
+        assert msg is None
