@@ -32,9 +32,17 @@ EXG_PE_BAM_REFERENCE_ID = 18
 EXG_PE_BAM_FIELD_LENGTHS = 19
 EXG_PE_BAM_CIGAR_OP = 20
 EXG_PE_BAM_QUALITY = 21
+EXG_PE_BED_FIELD_COUNT = 22
+EXG_PE_BED_REFERENCE_NAME = 23
+EXG_PE_BED_POSITION = 24
+EXG_PE_BED_SCORE = 25
+EXG_PE_BED_STRAND = 26
+EXG_PE_BED_COLOR = 27
+EXG_PE_BED_BLOCKS = 28
 
-EXG_FMT_FASTA, EXG_FMT_FASTQ, EXG_FMT_VCF, EXG_FMT_BAM = 1, 2, 3, 4
+EXG_FMT_FASTA, EXG_FMT_FASTQ, EXG_FMT_VCF, EXG_FMT_BAM, EXG_FMT_BED = 1, 2, 3, 4, 5
 EXG_BAM_COLUMNS = 10
+EXG_BED_COLUMNS = 12
 EXG_F_BOF, EXG_F_EOF, EXG_F_NO_STORE = 1, 2, 4
 EXG_RF_NON_ASCII, EXG_RF_HEAD_UNRESOLVED, EXG_RF_FALLBACK, EXG_RF_CAPACITY, EXG_RF_INDEX_OVERFLOW = 1, 2, 4, 8, 16
 EXG_RF_QUAL_RANGE = 32
@@ -162,6 +170,24 @@ class BamScanArgs(C.Structure):
     ]
 
 
+class BedScanArgs(C.Structure):
+    _fields_ = [
+        ("d_input", C.c_void_p),
+        ("n_bytes", C.c_uint64),
+        ("lead", C.c_uint64),
+        ("payload_base", C.c_uint64),
+        ("flags", C.c_uint32),
+        ("algo", C.c_uint32),
+        ("d_columns", C.c_void_p * 12),
+        ("d_validity", C.c_void_p * 12),
+        ("capacity_records", C.c_uint64),
+        ("d_workspace", C.c_void_p),
+        ("workspace_bytes", C.c_uint64),
+        ("d_result", C.c_void_p),
+        ("stream", C.c_void_p),
+    ]
+
+
 class QualityListArgs(C.Structure):
     _fields_ = [
         ("d_strings", C.c_void_p),
@@ -204,6 +230,7 @@ SIGNATURES = {
     "exg_vcf_scan": (C.c_int, [C.POINTER(VcfScanArgs)]),
     "exg_fasta_scan": (C.c_int, [C.POINTER(FastaScanArgs)]),
     "exg_bam_scan": (C.c_int, [C.POINTER(BamScanArgs)]),
+    "exg_bed_scan": (C.c_int, [C.POINTER(BedScanArgs)]),
     "exg_gzip_index": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),
                                  C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
     "exg_inflate_members": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),

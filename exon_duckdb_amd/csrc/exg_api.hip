@@ -71,12 +71,28 @@ extern "C" const char *exg_parse_error_string(uint32_t code) {
         case EXG_PE_BAM_FIELD_LENGTHS: return "field lengths exceed block_size";
         case EXG_PE_BAM_CIGAR_OP: return "invalid CIGAR operation";
         case EXG_PE_BAM_QUALITY: return "quality score above 93";
+        case EXG_PE_BED_FIELD_COUNT: return "invalid number of BED fields (3 to 9, or 12)";
+        case EXG_PE_BED_REFERENCE_NAME: return "missing reference sequence name";
+        case EXG_PE_BED_POSITION: return "invalid BED position or block count";
+        case EXG_PE_BED_SCORE: return "invalid BED score";
+        case EXG_PE_BED_STRAND: return "invalid strand";
+        case EXG_PE_BED_COLOR: return "invalid color";
+        case EXG_PE_BED_BLOCKS: return "invalid block sizes or block starts";
         default: return "unknown parse error";
     }
 }
 
 extern "C" uint64_t exg_scan_workspace_bytes(int format, uint64_t n_bytes) {
     if (format == EXG_FMT_BAM) return exg::bam::workspace_bytes(n_bytes);
+    if (format == EXG_FMT_BED) {
+        // the single-pass scan needs the per-tile arrays only; the general path's line index is provisioned for one line per
+        // 16 bytes (a BED3 line is 16 bytes and more), never less than min(n, 1 Mi) lines: half a byte per input byte where
+        // the other text formats take one.  A denser input is reported (EXG_RF_INDEX_OVERFLOW: a larger workspace indexes it)
+        const FastqWsLayout l = fastq_ws_layout(n_bytes, 0);
+        const uint64_t small = n_bytes < (1ull << 20) ? n_bytes : (1ull << 20);
+        const uint64_t lines = (n_bytes / 16 > small ? n_bytes / 16 : small) + 8;
+        return l.off_nl_pos + (lines + 2) * 8;
+    }
     return fastq_ws_layout(n_bytes, 0, format == EXG_FMT_FASTA ? 4 : 1).total_bytes;
 }
 

@@ -70,7 +70,7 @@ struct FilterOp {
     double f;
 };
 static constexpr int kMaxFilterOps = 32;
-static constexpr int kMaxFilterCols = 10;  // (read_bam_file_records has ten columns)
+static constexpr int kMaxFilterCols = 12;  // (read_bed_file has twelve columns)
 struct FilterProgram {  // postfix
     uint32_t n_ops;
     FilterOp ops[kMaxFilterOps];

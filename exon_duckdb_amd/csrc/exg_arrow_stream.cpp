@@ -1524,6 +1524,8 @@ extern "C" ReaderResult new_reader(ArrowArrayStream *stream_ptr, const char *uri
     if (!stream_ptr || !uri || !file_format) return result_error("new_reader: null argument");
     if (strcasecmp(file_format, "bam") == 0)
         return result_error("new_reader: BAM is served at the chunk boundary only (exg_open / read_bam_file_records); the Arrow boundary for BAM is not built");
+    if (strcasecmp(file_format, "bed") == 0)
+        return result_error("new_reader: BED is served at the chunk boundary only (exg_open / read_bed_file); the Arrow boundary for BED is not built");
     exg_open_args oa;
     memset(&oa, 0, sizeof oa);
     oa.path = uri;

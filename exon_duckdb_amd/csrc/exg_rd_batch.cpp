@@ -195,12 +195,15 @@ static int plan_bgzf_shard(exg_reader *r, const std::string &path, uint64_t n, u
 // needed for the definition lines' strings alone, 2 % of it (the whole text went along until then: a bgzip FASTA into DataChunks
 // sent every byte back twice, 92 ms for 1.96 GB).
 enum PayloadRoute { kPayloadNone, kPayloadCompact, kPayloadMirror };
+// read_bed_file: the VARCHAR columns (0, 3, 5, 8, 10, 11) as a mask; the other six are BIGINT
+static constexpr uint64_t kBedStringCols = 0xD29ull;
+static inline bool bed_is_string(int c) { return (kBedStringCols >> c) & 1ull; }
 static PayloadRoute payload_route(const exg_reader *r) {
     if (r->format == EXG_FMT_BAM) return kPayloadNone;  // (a BAM segment is never mirrored: its strings are produced into a side buffer)
     if (r->format == EXG_FMT_FASTA) {
         return (r->want_cols & 3ull) && !switches().fasta_whole_text ? kPayloadCompact : kPayloadNone;
     }
-    const uint64_t strs = r->format == EXG_FMT_VCF ? 0x1DDull : 0xFull, nested = r->format == EXG_FMT_VCF ? 0x1D4ull : 0ull;
+    const uint64_t strs = r->format == EXG_FMT_VCF ? 0x1DDull : r->format == EXG_FMT_BED ? kBedStringCols : 0xFull, nested = r->format == EXG_FMT_VCF ? 0x1D4ull : 0ull;
     const uint64_t sel = r->want_cols & strs;
     if (!sel) return kPayloadNone;
     if (!switches().no_payload_compact && sel != strs && !(sel & nested)) return kPayloadCompact;
@@ -519,7 +522,8 @@ int open_next_file(exg_reader *r) {
     return r->fa_shard || r->range_preset || r->shard_count > 1 ? place_shard(r, *blk) : EXG_OK;
 }
 
-int n_string_cols(int format) { return format == EXG_FMT_FASTQ ? 4 : format == EXG_FMT_FASTA ? 3 : 9; }
+// the columns a text format's scan writes (BED: its twelve, the BIGINT ones among them — bed_is_string tells them apart)
+int n_string_cols(int format) { return format == EXG_FMT_FASTQ ? 4 : format == EXG_FMT_FASTA ? 3 : format == EXG_FMT_BED ? EXG_BED_COLUMNS : 9; }
 
 int next_batch(exg_reader *r, bool count_only, uint64_t *n_records_out);
 
@@ -597,7 +601,10 @@ int ensure_device(exg_reader *r, uint64_t need_bytes) {
     for (int k = 0; k < 2; k++)
         if ((arc = r->dev_alloc(&r->d_valid[k], (r->cap_records + 63) / 64 * 8))) return arc;
     for (int c = 0; c < n_string_cols(r->format); c++)
-        if ((arc = r->dev_alloc(&r->d_cols[c], r->cap_records * 16))) return arc;
+        if ((arc = r->dev_alloc(&r->d_cols[c], r->cap_records * (r->format == EXG_FMT_BED && !bed_is_string(c) ? 8 : 16)))) return arc;
+    if (r->format == EXG_FMT_BED)
+        for (int c = 3; c < EXG_BED_COLUMNS; c++)
+            if ((arc = r->dev_alloc(&r->d_bed_valid[c], (r->cap_records + 63) / 64 * 8))) return arc;
     if (r->format == EXG_FMT_VCF) {
         if ((arc = r->dev_alloc(&r->d_pos, r->cap_records * 8))) return arc;
         if ((arc = r->dev_alloc(&r->d_qual, r->cap_records * 4))) return arc;
@@ -645,7 +652,7 @@ struct SideBuf {
     struct Col {
         uint64_t *d_goff = nullptr;
         uint64_t total = 0, off = 0;
-    } col[9];
+    } col[12];
     uint8_t *h = nullptr;
 };
 
@@ -989,6 +996,20 @@ struct BatchRun {
         }
         return scan_rc(exg_vcf_scan(&a));
     }
+    int launch_bed(uint32_t algo) {
+        exg_bed_scan_args a;
+        fill_common(&a);
+        a.lead = in.lead;
+        a.algo = algo;
+        // the projection reaches the kernel (a NULL column is validated, not written): a column is produced when it is selected or
+        // the predicate reads it
+        for (int c = 0; c < EXG_BED_COLUMNS; c++) {
+            if (!r->want(c) && !((r->filter_cols >> c) & 1ull)) continue;
+            a.d_columns[c] = r->d_cols[c];
+            a.d_validity[c] = (uint64_t *)r->d_bed_valid[c];
+        }
+        return scan_rc(exg_bed_scan(&a));
+    }
     int launch_fasta() {
         in.b = std::make_shared<Batch>();
         if (!count_only) {
@@ -1006,7 +1027,9 @@ struct BatchRun {
         return scan_rc(exg_fasta_scan(&a));
     }
     int scan_rc(int rc) { return rc ? fail(r, rc, exg_last_error_message()) : EXG_OK; }
-    int launch_scan(uint32_t algo) { return r->format == EXG_FMT_FASTQ ? launch_fastq(algo) : r->format == EXG_FMT_VCF ? launch_vcf(algo) : launch_fasta(); }
+    int launch_scan(uint32_t algo) {
+        return r->format == EXG_FMT_FASTQ ? launch_fastq(algo) : r->format == EXG_FMT_VCF ? launch_vcf(algo) : r->format == EXG_FMT_BED ? launch_bed(algo) : launch_fasta();
+    }
     int scan() {
         int rc = launch_scan(r->fused_algo);
         if (rc) return rc;
@@ -1069,7 +1092,12 @@ struct BatchRun {
             fc.d_base[c] = (const uint8_t *)in.d_input;
             fc.payload_base[c] = (uint64_t)(uintptr_t)in.h;
         }
-        if (r->format == EXG_FMT_VCF) {
+        if (r->format == EXG_FMT_BED) {
+            for (int c = 0; c < nsc; c++) {
+                if (!bed_is_string(c)) fc.kind[c] = ea::kColI64;
+                fc.validity[c] = (const uint64_t *)r->d_bed_valid[c];
+            }
+        } else if (r->format == EXG_FMT_VCF) {
             fc.kind[1] = ea::kColI64, fc.data[1] = r->d_pos;
             fc.kind[5] = ea::kColF32, fc.data[5] = r->d_qual, fc.validity[5] = (const uint64_t *)r->d_valid[0];
             fc.validity[8] = (const uint64_t *)r->d_valid[1];
@@ -1107,7 +1135,9 @@ struct BatchRun {
         // the projection (exg_open_args.columns): every column was parsed and validated above, only the wanted ones travel.
         // A decoded input's bytes are what its strings point into: they travel when any string column does
         const int ns = n_string_cols(r->format);
-        const bool any_strings = r->format == EXG_FMT_VCF ? (r->want_cols & 0x1DDull) != 0 : (r->want_cols & ((1ull << ns) - 1)) != 0;
+        const bool any_strings = r->format == EXG_FMT_VCF   ? (r->want_cols & 0x1DDull) != 0
+                                 : r->format == EXG_FMT_BED ? (r->want_cols & kBedStringCols) != 0
+                                                            : (r->want_cols & ((1ull << ns) - 1)) != 0;
         if (in.gz_payload && any_strings && !in.gz_mirror) RD_HIP(r, hipMemcpyAsync(in.gz_payload->p, in.d_input, in.n, hipMemcpyDeviceToHost, r->stream));
         if (in.gz_mirror && in.gz_front) RD_HIP(r, hipMemcpyAsync(const_cast<uint8_t *>(in.h), in.d_input, in.gz_front, hipMemcpyDeviceToHost, r->stream));
         b->n_rows = k;
@@ -1122,6 +1152,9 @@ struct BatchRun {
         if ((rc = flat_columns(side, cs))) return rc;
         if (r->format == EXG_FMT_VCF) {
             if ((rc = vcf_nested_columns(cs, &col_drain))) return rc;
+        } else if (r->format == EXG_FMT_BED) {
+            for (int c = 3; c < EXG_BED_COLUMNS; c++)
+                if (r->want(c) && (rc = column_to_host(r, b, c, nullptr, 0, r->d_bed_valid[c], k, row_map, r->d_gather, cs))) return rc;
         } else if (r->want(1) && (rc = column_to_host(r, b, 1, nullptr, 0, r->d_valid[0], k, row_map, r->d_gather, cs))) {
             return rc;
         }
@@ -1147,7 +1180,9 @@ struct BatchRun {
         uint64_t *d_tmp = (uint64_t *)scratch->take((ea::scan_tmp_entries(k) + 2) * 8);
         if (!d_tmp) return fail(r, EXG_E_HIP, "out of device memory");
         for (int c = 0; c < ns; c++) {
-            if (!r->want(c) || (r->format == EXG_FMT_VCF && c != 0 && c != 3) || (r->format == EXG_FMT_FASTA && c == 2)) continue;
+            if (!r->want(c) || (r->format == EXG_FMT_VCF && c != 0 && c != 3) || (r->format == EXG_FMT_FASTA && c == 2) ||
+                (r->format == EXG_FMT_BED && !bed_is_string(c)))
+                continue;
             if (!(side->col[c].d_goff = (uint64_t *)scratch->take((k + 2) * 8))) return fail(r, EXG_E_HIP, "out of device memory");
             const ea::StrCol sc{(const exg_string_t *)r->d_cols[c], (const uint8_t *)in.d_input, (uint64_t)(uintptr_t)in.h};
             ea::payload_goff_from_col(sc, row_map, k, side->col[c].d_goff, d_tmp, r->stream);
@@ -1209,6 +1244,7 @@ struct BatchRun {
             uint32_t es = 16;
             if (r->format == EXG_FMT_VCF && c == 1) src = r->d_pos, es = 8;
             if (r->format == EXG_FMT_VCF && c == 5) src = r->d_qual, es = 4;
+            if (r->format == EXG_FMT_BED && !bed_is_string(c)) es = 8;
             b->elem[c] = es;
             int rc;
             if (in.compact && es == 16 && side.col[c].d_goff) {
@@ -1301,7 +1337,7 @@ int next_batch(exg_reader *r, bool count_only, uint64_t *n_records_out) {
         if ((rc = ensure_device(r, in.n + in.shard_halo + 16))) return rc;
         if ((rc = run.bind_input())) return rc;
         if ((rc = run.fastq_first_line_phase())) return rc;
-        TraceRange scan_range(r->format == EXG_FMT_FASTQ ? "exg: scan fastq batch" : r->format == EXG_FMT_VCF ? "exg: scan vcf batch" : "exg: scan fasta batch");
+        TraceRange scan_range(r->format == EXG_FMT_FASTQ ? "exg: scan fastq batch" : r->format == EXG_FMT_VCF ? "exg: scan vcf batch" : r->format == EXG_FMT_BED ? "exg: scan bed batch" : "exg: scan fasta batch");
         if ((rc = run.scan())) return rc;
         switch (run.judge()) {  // (the only place that scans the batch again)
             case kAccept: break;

@@ -207,6 +207,7 @@ extern "C" ReplacementScanResult replacement_scan(const char *uri) {
     if (ext == "fastq" || ext == "fq") res.file_type = "FASTQ";
     if (ext == "vcf") res.file_type = "VCF";
     if (ext == "bam") res.file_type = "BAM";
+    if (ext == "bed") res.file_type = "BED";  // (the reference's glue throws for it, module.cpp:376-379: not reproduced)
     return res;
 }
 
@@ -216,6 +217,7 @@ extern "C" ReplacementScanResult replacement_scan(const char *uri) {
 // hundred bytes), a 16 KiB half with more lines than its list holds (FASTQ 512: lines of < 32 bytes on average; VCF 1024), bytes
 // >= 0x80 (UTF-8 validation).  A sample of the first MiB tells all of that apart.
 extern "C" int exg_scan_algo_hint(int format, const void *sample, uint64_t n_bytes) {
+    if (format == EXG_FMT_BED) return EXG_ALGO_FUSED_FULL;  // (BED has the any-shape scan only)
     if (format != EXG_FMT_FASTQ && format != EXG_FMT_VCF) return EXG_ALGO_FUSED;  // (FASTA has one scan)
     const uint8_t *p = (const uint8_t *)sample;
     const uint64_t n = n_bytes < (1u << 20) ? n_bytes : (1u << 20);

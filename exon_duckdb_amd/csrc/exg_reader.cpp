@@ -39,6 +39,8 @@ extern "C" int exg_open(const exg_open_args *args, exg_reader **out) {
         r->format = EXG_FMT_VCF;
     else if (fmt == "bam")
         r->format = EXG_FMT_BAM;
+    else if (fmt == "bed")
+        r->format = EXG_FMT_BED, r->fused_algo = EXG_ALGO_FUSED_FULL;  // (one single-pass scan: exg_bed.hip)
     else if (fmt == "sam") {
         exg::set_error("file_format sam is not supported: the SAM text tokeniser is not built (read_bam_file_records reads BAM)");
         return EXG_E_UNSUPPORTED;
@@ -70,7 +72,9 @@ extern "C" int exg_open(const exg_open_args *args, exg_reader **out) {
         // (24 for FASTQ: with 20 a single-member gzip under a 16 MiB cap peaked between 15.4 and 17.3 MB depending on how far the
         // decoder thread happened to run ahead of the scan — the first round's symbol buffer is sized for the worst ratio)
         // (BAM: segments as above, a workspace of ~0.8 B, a side buffer of ~1.25 B and ~2 B of vectors per decoded byte)
-        const uint64_t div = r->format == EXG_FMT_VCF ? 64 : r->format == EXG_FMT_FASTA || r->format == EXG_FMT_BAM ? 32 : 24;
+        // (BED: 9 B of vectors + 1.5 B of workspace per byte of an input slot, two slots, and a slot is a batch + 1 MiB of prefetch
+        // slack: measured 17.0 MiB under a 16 MiB cap with batches of 256 KiB — a quarter of VCF's batch stays under it)
+        const uint64_t div = r->format == EXG_FMT_BED ? 256 : r->format == EXG_FMT_VCF ? 64 : r->format == EXG_FMT_FASTA || r->format == EXG_FMT_BAM ? 32 : 24;
         if (r->mem_cap) r->device_batch_bytes = std::max<uint64_t>(64u << 10, std::min<uint64_t>(r->device_batch_bytes, (r->mem_cap / div) & ~15ull));
     }
     r->halo_want = getenv("EXG_SHARD_HALO") ? std::max<uint64_t>(16, strtoull(getenv("EXG_SHARD_HALO"), nullptr, 10)) : kShardHalo;
@@ -241,6 +245,17 @@ static void flat_schema(const exg_reader *r, exg_schema *out) {
                                            {EXG_TYPE_VARCHAR, 0, "sequence", 0, nullptr},       {EXG_TYPE_VARCHAR, 0, "quality_score", 0, nullptr}};
         out->n_columns = 10;
         for (int i = 0; i < 10; i++) out->names[i] = bam_t[i].name, out->types[i] = bam_t[i].type, out->nullable[i] = bam_t[i].nullable, out->tree[i] = &bam_t[i];
+    } else if (r->format == EXG_FMT_BED) {
+        // order pinned by test_bed_io.test:4-18; names and types as exon 0.2.6 is recalled to declare them ([RECALLED])
+        static const exg_type bed_t[EXG_BED_COLUMNS] = {
+            {EXG_TYPE_VARCHAR, 0, "reference_sequence_name", 0, nullptr}, {EXG_TYPE_BIGINT, 0, "start", 0, nullptr},
+            {EXG_TYPE_BIGINT, 0, "end", 0, nullptr},                      {EXG_TYPE_VARCHAR, 1, "name", 0, nullptr},
+            {EXG_TYPE_BIGINT, 1, "score", 0, nullptr},                    {EXG_TYPE_VARCHAR, 1, "strand", 0, nullptr},
+            {EXG_TYPE_BIGINT, 1, "thick_start", 0, nullptr},              {EXG_TYPE_BIGINT, 1, "thick_end", 0, nullptr},
+            {EXG_TYPE_VARCHAR, 1, "color", 0, nullptr},                   {EXG_TYPE_BIGINT, 1, "block_count", 0, nullptr},
+            {EXG_TYPE_VARCHAR, 1, "block_sizes", 0, nullptr},             {EXG_TYPE_VARCHAR, 1, "block_starts", 0, nullptr}};
+        out->n_columns = EXG_BED_COLUMNS;
+        for (int i = 0; i < EXG_BED_COLUMNS; i++) out->names[i] = bed_t[i].name, out->types[i] = bed_t[i].type, out->nullable[i] = bed_t[i].nullable, out->tree[i] = &bed_t[i];
     } else {
         // test_vcf_record_scan.test:10-19: alt is a LIST, info a STRUCT (module.cpp:126-147 maps exon's Arrow schema)
         static const char *n[] = {"chrom", "pos", "id", "ref", "alt", "qual", "filter", "info", "formats"};

@@ -320,9 +320,9 @@ struct Batch {  // host vectors of one device batch, shared by its chunks
     std::shared_ptr<PinnedBlock> file;
     HostArena host;
     int n_cols = 0;
-    void *cols[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    uint32_t elem[10] = {16, 16, 16, 16, 16, 16, 16, 16, 16, 16};  // bytes per row
-    void *validity[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // NULL => all valid
+    void *cols[12] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    uint32_t elem[12] = {16, 16, 16, 16, 16, 16, 16, 16, 16, 16, 16, 16};  // bytes per row
+    void *validity[12] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // NULL => all valid
     void *payload = nullptr;  // FASTA: compacted sequences
     uint64_t n_rows = 0;
     uint64_t seq = 0;          // which device batch of its reader this is (exg_chunk.batch_no)
@@ -463,7 +463,8 @@ struct exg_reader {
     size_t filter_prog_bytes = 0, filter_consts_bytes = 0;
     void *d_row_map = nullptr, *d_gather = nullptr, *d_filter_tmp = nullptr;  // output vectors sized for the densest possible input (after an overflow)
     void *d_valid[2] = {nullptr, nullptr};
-    void *d_cols[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    void *d_cols[12] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    void *d_bed_valid[12] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // BED: columns 3 .. 11
     void *d_pos = nullptr, *d_qual = nullptr, *d_payload = nullptr;
     uint64_t d_in_cap = 0, ws_bytes = 0, cap_records = 0;
     uint64_t vcf_header_bytes = 0;

@@ -333,3 +333,88 @@ class BamScan:
                         vals.append(s)
             out.append([v if valid is None or valid[i] else None for i, v in enumerate(vals)])
         return list(zip(*out))
+
+
+class BedScan:
+    """exg_bed_scan on BED text resident in HBM: buffers for all twelve columns; rows() decodes what came back into the
+    tuples tests compare (bytes / int / None), the strings out of the input bytes the caller hands it."""
+    NAMES = ["reference_sequence_name", "start", "end", "name", "score", "strand", "thick_start", "thick_end", "color",
+             "block_count", "block_sizes", "block_starts"]
+    INT_COLS, NULLABLE = (1, 2, 4, 6, 7, 9), tuple(range(3, 12))
+    PAYLOAD_BASE = 1 << 44
+
+    def __init__(self, n_bytes, capacity_records=None, device="cuda"):
+        torch = _torch()
+        self.lib = load_library()
+        self.n_bytes = n_bytes
+        self.capacity = int(capacity_records if capacity_records is not None else n_bytes // 2 + 16)
+        cap = max(self.capacity, 1)
+        self.cols = [torch.empty((cap,), dtype=torch.int64, device=device) if c in self.INT_COLS else
+                     torch.empty((cap, 2), dtype=torch.int64, device=device) for c in range(abi.EXG_BED_COLUMNS)]
+        self.validity = {c: torch.empty(((cap + 63) // 64,), dtype=torch.int64, device=device) for c in self.NULLABLE}
+        self.ws_bytes = int(self.lib.exg_scan_workspace_bytes(abi.EXG_FMT_BED, n_bytes))
+        self.ws = torch.empty((self.ws_bytes + 255) // 8, dtype=torch.int64, device=device)
+        self.result = torch.zeros(8, dtype=torch.int64, device=device)
+        self.args = abi.BedScanArgs()
+
+    def launch(self, d_input, n_bytes=None, lead=0, payload_base=None, flags=abi.EXG_F_BOF | abi.EXG_F_EOF,
+               algo=abi.EXG_ALGO_AUTO, project=None):
+        a = self.args
+        a.d_input = d_input.data_ptr()
+        a.n_bytes = self.n_bytes if n_bytes is None else n_bytes
+        a.lead = lead
+        a.payload_base = self.PAYLOAD_BASE if payload_base is None else payload_base
+        a.flags, a.algo = flags, algo
+        for c in range(abi.EXG_BED_COLUMNS):
+            on = project is None or c in project
+            a.d_columns[c] = self.cols[c].data_ptr() if on else None
+            a.d_validity[c] = self.validity[c].data_ptr() if on and c in self.validity else None
+        a.capacity_records = self.capacity
+        a.d_workspace, a.workspace_bytes = self.ws.data_ptr(), self.ws_bytes
+        a.d_result = self.result.data_ptr()
+        a.stream = stream_ptr().value
+        check(self.lib.exg_bed_scan(C.byref(a)))
+
+    def fetch(self):
+        r = abi.ScanResult()
+        check(self.lib.exg_fetch_result(C.c_void_p(self.result.data_ptr()), stream_ptr(), C.byref(r)))
+        return r
+
+    def host(self, n):
+        """raw columns ([n,16] uint8 string_t / int64) and validity words of the first n rows"""
+        nw = (n + 63) // 64
+        cols = [self.cols[c][:n].cpu().numpy() if c in self.INT_COLS else self.cols[c][:n].cpu().numpy().view(np.uint8).reshape(n, 16)
+                for c in range(abi.EXG_BED_COLUMNS)]
+        return cols, {c: v[:nw].cpu().numpy().view(np.uint64) for c, v in self.validity.items()}
+
+    def rows(self, n, data: bytes, columns=None, payload_base=None):
+        """the first n rows as tuples of the (selected) columns; `data`: the bytes d_input holds"""
+        base = self.PAYLOAD_BASE if payload_base is None else payload_base
+        cols, words = self.host(n)
+        out = []
+        for c in (range(abi.EXG_BED_COLUMNS) if columns is None else columns):
+            valid = np.unpackbits(words[c].view(np.uint8), bitorder="little")[:n] if c in words else None
+            if c in self.INT_COLS:
+                vals = cols[c].tolist()
+            else:
+                raw = cols[c]
+                lens = raw[:, :4].copy().view(np.uint32).reshape(n)
+                ptrs = raw[:, 8:16].copy().view(np.uint64).reshape(n)
+                vals = []
+                for i in range(n):
+                    ln = int(lens[i])
+                    if ln <= 12:
+                        assert not raw[i, 4 + ln:].any(), "inlined string_t is not zero padded"
+                        vals.append(raw[i, 4:4 + ln].tobytes())
+                    else:
+                        o = int(ptrs[i]) - base
+                        s = data[o:o + ln]
+                        assert 0 <= o and len(s) == ln and s[:4] == raw[i, 4:8].tobytes(), "string_t outside the input, or a wrong prefix"
+                        vals.append(s)
+            if valid is not None:
+                for i in range(n):
+                    if not valid[i]:
+                        assert not np.asarray(cols[c][i]).any(), "a NULL value does not hold zeros"
+                        vals[i] = None
+            out.append(vals)
+        return list(zip(*out))

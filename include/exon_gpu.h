@@ -43,6 +43,8 @@
 extern "C" {
 #endif
 
+/* 9 still: read_bed_file (EXG_FMT_BED, exg_bed_scan, EXG_PE_BED_*) is a pure addition — no existing struct, constant or
+ * entry point changed. */
 #define EXG_ABI_VERSION 9
 
 /* DuckDB v0.8.1 STANDARD_VECTOR_SIZE; the reference asks the Rust side for
@@ -85,6 +87,13 @@ extern "C" {
 #define EXG_PE_BAM_FIELD_LENGTHS 19   /* BAM: the declared field lengths do not fit in block_size */
 #define EXG_PE_BAM_CIGAR_OP 20        /* BAM: a CIGAR operation code above 8 */
 #define EXG_PE_BAM_QUALITY 21         /* BAM: a quality byte above 93 (and the qualities are not all 0xFF = absent) */
+#define EXG_PE_BED_FIELD_COUNT 22     /* BED: a line with a field count other than 3, 4, 5, 6, 7, 8, 9 or 12 */
+#define EXG_PE_BED_REFERENCE_NAME 23  /* BED: empty reference sequence name */
+#define EXG_PE_BED_POSITION 24        /* BED: start, end, thick_start, thick_end or block_count is not an integer in range */
+#define EXG_PE_BED_SCORE 25           /* BED: score is neither `0` nor an integer in 1..1000 */
+#define EXG_PE_BED_STRAND 26          /* BED: strand is not `+`, `-` or `.` */
+#define EXG_PE_BED_COLOR 27           /* BED: color is neither `0` nor r,g,b with three decimals in 0..255 */
+#define EXG_PE_BED_BLOCKS 28          /* BED: block_sizes / block_starts hold fewer than block_count integers */
 
 /* ---- duckdb::string_t, bit-for-bit (v0.8.1 duckdb/common/types/string_type.hpp)
  * length <= 12: bytes inlined, zero padded.  Otherwise 4-byte prefix + pointer.
@@ -108,6 +117,7 @@ typedef union exg_string_t {
 #define EXG_FMT_FASTQ 2
 #define EXG_FMT_VCF 3
 #define EXG_FMT_BAM 4 /* reader level + exg_bam_scan; the chunk boundary only (new_reader refuses it) */
+#define EXG_FMT_BED 5 /* reader level + exg_bed_scan; the chunk boundary only (new_reader refuses it) */
 
 /* ---- scan flags ------------------------------------------------------------ */
 #define EXG_F_BOF 1u /* a line starts at d_input[0] (start of file, or a record-aligned batch) */
@@ -279,6 +289,37 @@ typedef struct exg_bam_scan_args {
     void *stream;
 } exg_bam_scan_args;
 
+/* BED (read_bed_file): one row per line, twelve columns (order pinned by test_bed_io.test:4-18; the value rules are
+ * INTEGRATION.md's):
+ *   0 reference_sequence_name VARCHAR, 1 start BIGINT (field 2 + 1), 2 end BIGINT, 3 name VARCHAR?, 4 score BIGINT?,
+ *   5 strand VARCHAR?, 6 thick_start BIGINT? (field 7 + 1), 7 thick_end BIGINT?, 8 color VARCHAR?, 9 block_count BIGINT?,
+ *   10 block_sizes VARCHAR?, 11 block_starts VARCHAR?
+ * Every line of the input is a record (no header, no comments); a line has 3..9 or 12 tab-separated fields, the columns
+ * behind its last field are NULL.  Strings are zero-copy slices of the input (payload_base + offset; up to 12 bytes
+ * inlined): there is no side buffer.  A NULL value holds zeros (16 bytes / 8 bytes).  lead, flags and the result block
+ * are exg_vcf_scan's: a line belongs to the buffer it ENDS in at an offset >= lead; EXG_RF_HEAD_UNRESOLVED when the first
+ * owned line begins in front of d_input[0]; the rows in front of the first failing line are produced.
+ * algo: EXG_ALGO_MULTIPASS is the general path (line index + a thread per line reading global memory);
+ * EXG_ALGO_AUTO / EXG_ALGO_FUSED / EXG_ALGO_FUSED_FULL all run the single-pass any-shape scan (there is no lean instance);
+ * EXG_ALGO_FUSED_INDEX is EXG_E_INVALID_ARG. */
+#define EXG_BED_COLUMNS 12
+typedef struct exg_bed_scan_args {
+    const void *d_input; /* device pointer, 16-byte aligned, readable up to round_up(n_bytes,16) */
+    uint64_t n_bytes;
+    uint64_t lead;
+    uint64_t payload_base;
+    uint32_t flags;
+    uint32_t algo;
+    void *d_columns[EXG_BED_COLUMNS];      /* device: exg_string_t[capacity_records] for columns 0, 3, 5, 8, 10, 11; int64_t[] for 1, 2, 4,
+                                            * 6, 7, 9.  NULL = not produced, still validated */
+    uint64_t *d_validity[EXG_BED_COLUMNS]; /* device: ceil(capacity / 64) words for columns 3..11 (when produced) */
+    uint64_t capacity_records;
+    void *d_workspace; /* device, exg_scan_workspace_bytes(EXG_FMT_BED, n_bytes), 256-byte aligned */
+    uint64_t workspace_bytes;
+    exg_scan_result *d_result; /* device, 64 bytes */
+    void *stream;
+} exg_bed_scan_args;
+
 /* ---- library / device ------------------------------------------------------ */
 int exg_abi_version(void);
 /* Number of visible HIP devices, or EXG_E_NO_DEVICE. Does not initialise a context. */
@@ -295,6 +336,8 @@ int exg_vcf_scan(const exg_vcf_scan_args *args);
 int exg_fasta_scan(const exg_fasta_scan_args *args);
 /* Synchronises args->stream (see exg_bam_scan_args).  The 64-byte result comes back with exg_fetch_result, like the others'. */
 int exg_bam_scan(const exg_bam_scan_args *args);
+/* Enqueue on args->stream; asynchronous (the result through exg_fetch_result). */
+int exg_bed_scan(const exg_bed_scan_args *args);
 /* Synchronising copy of the 64-byte result to the host. */
 int exg_fetch_result(const exg_scan_result *d_result, void *stream, exg_scan_result *out);
 /* '\n' count of d_input[begin,end) into *d_count (device u64); used for the shard phase exchange. */
@@ -447,9 +490,10 @@ typedef struct exg_reader exg_reader;
 
 typedef struct exg_open_args {
     const char *path;        /* local file or directory (the reference lists directories: test_fasta_scan.test:55-59) */
-    const char *file_format; /* "fasta" | "fastq" | "vcf" | "bam" (the reference's file_type strings, exon_extension.cpp:47-58).  A BAM
-                              * file is always read as gzip members (BGZF), whatever `compression` says, and as ONE shard
-                              * (shard_count > 1: EXG_E_UNSUPPORTED); "sam" is refused */
+    const char *file_format; /* "fasta" | "fastq" | "vcf" | "bam" | "bed" (the reference's file_type strings, exon_extension.cpp:47-58;
+                              * any case).  A BAM file is always read as gzip members (BGZF), whatever `compression` says, and as
+                              * ONE shard (shard_count > 1: EXG_E_UNSUPPORTED); "sam" is refused.  "bed": text without a header,
+                              * every line a record; batches, decoders, shards and fan-out as for VCF */
     const char *compression; /* NULL = infer from extension like arrow_reader.rs:60-75; "gzip","zstd","uncompressed",... */
     uint64_t batch_rows;     /* rows per chunk; 0 => EXG_VECTOR_SIZE */
     int device;              /* HIP device ordinal */
@@ -589,7 +633,7 @@ void exg_close(exg_reader *r);
 /* ---- (3) reference-FFI compatible ------------------------------------------------------ */
 /* exon/include/rust.hpp:11-13 */
 typedef struct ReplacementScanResult {
-    const char *file_type; /* "FASTA" | "FASTQ" | "VCF" | "BAM" (static storage) or NULL */
+    const char *file_type; /* "FASTA" | "FASTQ" | "VCF" | "BAM" | "BED" (static storage) or NULL */
 } ReplacementScanResult;
 /* exon/include/rust.hpp:48, rust/src/arrow_reader.rs:173-197: last extension, skipping one
  * compression extension (gz, gzip, zst, zstd, bz2, bzip2, xz). */
@@ -648,7 +692,7 @@ typedef struct ReaderResult {
  * the `filters` predicate and the Arrow buffers themselves (offsets, values, validity) are produced
  * on the device; the host only copies them back and wires the ArrowArray structs.
  *   compression: NULL = by extension (:60-75), else DataFusion's FileCompressionType names (:77-91)
- *   file_format: "fasta" | "fastq" | "vcf" ("bam" is refused: BAM is served at the chunk boundary, exg_open, only)
+ *   file_format: "fasta" | "fastq" | "vcf" ("bam" and "bed" are refused: they are served at the chunk boundary, exg_open, only)
  *   filters:     NULL / "" or the predicate text FilterToString renders (module.cpp:158-214):
  *                <column> (= | != | <> | < | <= | > | >=) <literal>, <column> IS [NOT] NULL, AND, OR
  *                with SQL precedence; it is applied as `SELECT * FROM exon_table WHERE <filters>` (:125-141). */
