@@ -7,6 +7,7 @@
 #include "exg_arrow.hpp"
 #include "exg_bam.hpp"
 #include "exg_fastq.hpp"
+#include "exg_rd_format.hpp"
 
 namespace exg {
 
@@ -93,7 +94,7 @@ extern "C" uint64_t exg_scan_workspace_bytes(int format, uint64_t n_bytes) {
         const uint64_t lines = (n_bytes / 16 > small ? n_bytes / 16 : small) + 8;
         return l.off_nl_pos + (lines + 2) * 8;
     }
-    return fastq_ws_layout(n_bytes, 0, format == EXG_FMT_FASTA ? 4 : 1).total_bytes;
+    return fastq_ws_layout(n_bytes, 0, exg_rd::format_desc(format).line_index_arrays).total_bytes;  // (FASTA keeps four arrays)
 }
 
 extern "C" int exg_fetch_result(const exg_scan_result *d_result, void *stream, exg_scan_result *out) {

@@ -470,7 +470,7 @@ int build_nested(Emit &em, const ScanCtx &ctx, uint64_t B, const bool *want, boo
     memset(&b, 0, sizeof b);
     const int src_col[5] = {2, 4, 6, 7, 8};
     for (int c = 0; c < 5; c++) b.col[c] = (const exg_string_t *)r->d_cols[src_col[c]];
-    b.rest_valid = (const uint64_t *)r->d_valid[1];
+    b.rest_valid = (const uint64_t *)r->d_col_valid[8];  // (formats: the lines that have a FORMAT field)
     b.row_map = em.d_row_map;
     b.d_base = d_base;
     b.payload_base = pb;
@@ -766,19 +766,15 @@ int arrow_emit(exg_reader *r, const ScanCtx &ctx) {
     if (st->has_filter) {
         ea::FilterCols fc;
         memset(&fc, 0, sizeof fc);
-        for (size_t c = 0; c < st->schema.size() && c < (size_t)ea::kMaxFilterCols; c++) {
-            const std::string &f = st->schema[c].format;
-            ea::StrCol sc = str_col((int)c);
-            fc.kind[c] = f == "l" ? ea::kColI64 : f == "f" ? ea::kColF32 : ea::kColStr;
-            fc.data[c] = f == "l" ? r->d_pos : f == "f" ? r->d_qual : (const void *)sc.d_col;
+        const FormatDesc &f = format_desc(r->format);
+        for (int c = 0; c < f.n_columns; c++) {
+            const ea::StrCol sc = str_col(c);
+            fc.kind[c] = filter_col_kind(f.col[c]);
+            fc.data[c] = r->column_data(c).data;
             fc.d_base[c] = sc.d_base;
             fc.payload_base[c] = sc.payload_base;
-            fc.validity[c] = nullptr;
+            fc.validity[c] = (const uint64_t *)r->d_col_valid[c];
         }
-        if (r->format == EXG_FMT_VCF)
-            fc.validity[5] = (const uint64_t *)r->d_valid[0];
-        else
-            fc.validity[1] = (const uint64_t *)r->d_valid[0];
         uint64_t *d_goff = (uint64_t *)em.dalloc((em.n + 1) * 8);
         uint64_t *d_tmp = (uint64_t *)em.dalloc(ea::scan_tmp_entries(em.n) * 8);
         uint32_t *d_map = (uint32_t *)em.dalloc(em.n * 4 + 4);
@@ -795,10 +791,9 @@ int arrow_emit(exg_reader *r, const ScanCtx &ctx) {
         return EXG_OK;
     }
     std::vector<AColumn> &cols = batch->cols;
-    if (r->format == EXG_FMT_FASTQ || r->format == EXG_FMT_FASTA) {
-        const int nc = r->format == EXG_FMT_FASTQ ? 4 : 3;
-        for (int c = 0; c < nc && !em.rc; c++)
-            cols.push_back(em.utf8_top(str_col(c), c == 1 ? (const uint64_t *)r->d_valid[0] : nullptr));
+    if (r->format == EXG_FMT_FASTQ || r->format == EXG_FMT_FASTA) {  // every column is a flat string
+        for (int c = 0; c < format_desc(r->format).n_columns && !em.rc; c++)
+            cols.push_back(em.utf8_top(str_col(c), (const uint64_t *)r->d_col_valid[c]));
     } else {
         auto prim = [&](const void *d_src, int es, const uint64_t *d_valid_src) {
             AColumn col;
@@ -820,9 +815,10 @@ int arrow_emit(exg_reader *r, const ScanCtx &ctx) {
             return col;
         };
         cols.push_back(em.utf8_top(str_col(0), nullptr));                              // chrom
-        cols.push_back(prim(r->d_pos, 8, nullptr));                                     // pos
+        const exg_reader::ColumnData pos = r->column_data(1), qual = r->column_data(5);
+        cols.push_back(prim(pos.data, (int)pos.elem, nullptr));                          // pos
         AColumn c_ref = em.utf8_top(str_col(3), nullptr);
-        AColumn c_qual = prim(r->d_qual, 4, (const uint64_t *)r->d_valid[0]);
+        AColumn c_qual = prim(qual.data, (int)qual.elem, (const uint64_t *)r->d_col_valid[5]);
         if (em.rc) return em.rc;
         EM_TRACE("flat");
         // id / alt / filter / info / formats: made on the device in DuckDB's layouts (exg_vcf_nested.hpp), converted here to Arrow's
@@ -1261,16 +1257,16 @@ int nested_prepare(exg_reader *r) {
         const uint64_t keys = st->info_keys.size() + st->format_keys.size();
         if (keys > 64) r->device_batch_bytes = std::max<uint64_t>(8ull << 20, (r->device_batch_bytes * 64 / keys) & ~0xFFFFFull);
     }
+    // the flat columns as the table has them; the nested ones by hand, under the table's names
+    const FormatDesc &f = format_desc(EXG_FMT_VCF);
     exg_type *t = st->type_roots;
-    t[0] = leaf(EXG_TYPE_VARCHAR, "chrom", 0);
-    t[1] = leaf(EXG_TYPE_BIGINT, "pos", 0);
-    t[2] = list_of(st.get(), "id", leaf(EXG_TYPE_VARCHAR, "item", 1), 1);
-    t[3] = leaf(EXG_TYPE_VARCHAR, "ref", 0);
-    t[4] = list_of(st.get(), "alt", leaf(EXG_TYPE_VARCHAR, "item", 1), 1);
-    t[5] = leaf(EXG_TYPE_FLOAT, "qual", 1);
-    t[6] = list_of(st.get(), "filter", leaf(EXG_TYPE_VARCHAR, "item", 1), 1);
-    t[7] = struct_of(st.get(), "info", st->info_keys, 1);
-    t[8] = list_of(st.get(), "formats", struct_of(st.get(), "item", st->format_keys, 1), 1);
+    for (int c = 0; c < f.n_columns; c++)
+        if (!f.col[c].nested) t[c] = *flat_tree(EXG_FMT_VCF, c);
+    t[2] = list_of(st.get(), f.col[2].name, leaf(EXG_TYPE_VARCHAR, "item", 1), 1);                      // id
+    t[4] = list_of(st.get(), f.col[4].name, leaf(EXG_TYPE_VARCHAR, "item", 1), 1);                      // alt
+    t[6] = list_of(st.get(), f.col[6].name, leaf(EXG_TYPE_VARCHAR, "item", 1), 1);                      // filter
+    t[7] = struct_of(st.get(), f.col[7].name, st->info_keys, 1);                                        // info
+    t[8] = list_of(st.get(), f.col[8].name, struct_of(st.get(), "item", st->format_keys, 1), 1);        // formats
     r->nested_state = st;
     return EXG_OK;
 }
@@ -1441,38 +1437,28 @@ static int build_stream(const exg_open_args &oa, const char *filters, std::share
         *err = "could not register table: " + r->error;
         return EXG_E_IO;
     }
-    auto utf8 = [](const char *name, bool nullable) {
+    // the flat fields as the table has them (Arrow's format strings are the parser's kinds: "u" Utf8, "l" Int64, "f" Float32)
+    const FormatDesc &fd = format_desc(r->format);
+    for (int c = 0; c < fd.n_columns; c++) {
         Field f;
-        f.name = name;
-        f.format = "u";
-        f.nullable = nullable;
-        return f;
-    };
-    if (r->format == EXG_FMT_FASTQ) {
-        st->schema = {utf8("name", false), utf8("description", true), utf8("sequence", false), utf8("quality_scores", false)};
-    } else if (r->format == EXG_FMT_FASTA) {
-        st->schema = {utf8("id", false), utf8("description", true), utf8("sequence", false)};
-    } else {
+        f.name = fd.col[c].name;
+        f.nullable = fd.col[c].nullable;
+        if (!fd.col[c].nested) f.format = std::string(1, filter_kind(fd.col[c]));
+        st->schema.push_back(f);
+    }
+    if (r->format == EXG_FMT_VCF) {
+        // ... and the nested VCF fields by hand: id, alt, filter are lists of strings, info a struct of the header's INFO keys,
+        // formats a list of structs of its FORMAT keys
         parse_vcf_header((const char *)r->file->p, (size_t)r->vcf_header_bytes, &st->info_keys, &st->format_keys);
-        auto list_utf8 = [&](const char *name) {
-            Field f;
-            f.name = name;
-            f.format = "+l";
-            Field item = utf8("item", true);
-            f.children.push_back(item);
-            return f;
-        };
-        Field pos, qual, info, formats, item;
-        pos.name = "pos", pos.format = "l", pos.nullable = false;
-        qual.name = "qual", qual.format = "f";
-        info.name = "info", info.format = "+s";
-        for (auto &k : st->info_keys) info.children.push_back(key_field(k));
-        item.name = "item", item.format = "+s";
-        for (auto &k : st->format_keys) item.children.push_back(key_field(k));
-        formats.name = "formats", formats.format = "+l";
-        formats.children.push_back(item);
-        st->schema = {utf8("chrom", false), pos, list_utf8("id"), utf8("ref", false), list_utf8("alt"), qual,
-                      list_utf8("filter"), info, formats};
+        Field item, sample;
+        item.name = sample.name = "item";
+        item.format = "u";
+        sample.format = "+s";
+        for (auto &k : st->format_keys) sample.children.push_back(key_field(k));
+        for (int c : {2, 4, 6}) st->schema[c].format = "+l", st->schema[c].children.push_back(item);  // id, alt, filter
+        st->schema[7].format = "+s";                                                                     // info
+        for (auto &k : st->info_keys) st->schema[7].children.push_back(key_field(k));
+        st->schema[8].format = "+l", st->schema[8].children.push_back(sample);                          // formats
         if ((rc = upload_keys(r, st->info_keys, &st->nk_info)) || (rc = upload_keys(r, st->format_keys, &st->nk_format))) {
             *err = "could not register table: " + r->error;
             return rc;
@@ -1487,8 +1473,7 @@ static int build_stream(const exg_open_args &oa, const char *filters, std::share
     if (filters && *filters) {
         // `SELECT * FROM exon_table WHERE <filters>` (arrow_reader.rs:125-141)
         std::string text = filters;
-        std::vector<exg_rd::FilterColumn> fcols;
-        for (auto &f : st->schema) fcols.push_back({f.name, f.format == "u" ? 'u' : f.format == "l" ? 'l' : f.format == "f" ? 'f' : 'x'});
+        const std::vector<exg_rd::FilterColumn> fcols = exg_rd::filter_columns(fd);
         exg_rd::FilterParser fp(text, fcols);
         bool parsed = false;
         try {

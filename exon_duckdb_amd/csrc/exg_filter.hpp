@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "exg_arrow.hpp"
+#include "exg_rd_format.hpp"
 
 namespace exg_rd {
 namespace ea = exg::arrow;
@@ -22,6 +23,16 @@ struct FilterColumn {
     std::string name;
     char kind;  // 'u' Utf8 / VARCHAR, 'l' Int64, 'i' Int32, 'f' Float32, anything else: not filterable (nested)
 };
+// the columns of a format as the parser sees them, and a column as the predicate's kernel does (ea::kCol*)
+inline std::vector<FilterColumn> filter_columns(const FormatDesc &f) {
+    std::vector<FilterColumn> cols;
+    for (int c = 0; c < f.n_columns; c++) cols.push_back({f.col[c].name, filter_kind(f.col[c])});
+    return cols;
+}
+inline uint32_t filter_col_kind(const ColumnDesc &d) {
+    const char k = filter_kind(d);
+    return k == 'l' ? ea::kColI64 : k == 'i' ? ea::kColI32 : k == 'f' ? ea::kColF32 : ea::kColStr;
+}
 
 struct FilterParser {
     const std::string &s;

@@ -55,8 +55,7 @@ BamState *state_of(exg_reader *r) {
     return (BamState *)r->bam_state.get();
 }
 
-const bool kIsInt[EXG_BAM_COLUMNS] = {false, true, false, true, true, false, false, false, false, false};
-const bool kNullable[EXG_BAM_COLUMNS] = {false, false, true, true, true, true, false, true, false, false};
+const FormatDesc &kBam = format_desc(EXG_FMT_BAM);  // (the columns' widths and which are nullable: exg_rd_format.hpp)
 
 int ensure_buffers(exg_reader *r, BamState *s, uint64_t n, uint64_t side_bytes) {
     if (s->d_ws && n <= s->in_cap && side_bytes <= s->side_cap) return EXG_OK;
@@ -78,8 +77,8 @@ int ensure_buffers(exg_reader *r, BamState *s, uint64_t n, uint64_t side_bytes) 
     const uint64_t produce = r->want_cols | r->filter_cols;
     for (int c = 0; c < EXG_BAM_COLUMNS; c++) {
         if (!((produce >> c) & 1)) continue;
-        if ((rc = r->dev_alloc(&s->d_cols[c], s->cap_records * (kIsInt[c] ? 4 : 16)))) return rc;
-        if (kNullable[c] && (rc = r->dev_alloc(&s->d_valid[c], (s->cap_records + 63) / 64 * 8))) return rc;
+        if ((rc = r->dev_alloc(&s->d_cols[c], s->cap_records * kBam.col[c].elem))) return rc;
+        if (kBam.col[c].validity && (rc = r->dev_alloc(&s->d_valid[c], (s->cap_records + 63) / 64 * 8))) return rc;
     }
     if (r->has_filter) {
         if ((rc = r->dev_alloc(&s->d_row_map, s->cap_records * 4 + 64))) return rc;
@@ -160,7 +159,7 @@ int bam_select_rows(exg_reader *r, BamState *s, const exg_bam_scan_args &a, uint
     ea::FilterCols fc;
     memset(&fc, 0, sizeof fc);
     for (int c = 0; c < EXG_BAM_COLUMNS; c++) {
-        fc.kind[c] = kIsInt[c] ? ea::kColI32 : ea::kColStr;
+        fc.kind[c] = filter_col_kind(kBam.col[c]);
         fc.data[c] = s->d_cols[c];
         fc.validity[c] = (const uint64_t *)s->d_valid[c];
         const bool ref = c == 2 || c == 7;
@@ -184,8 +183,8 @@ int bam_columns_to_host(exg_reader *r, BamState *s, const std::shared_ptr<Batch>
     for (int c = 0; c < EXG_BAM_COLUMNS; c++) {
         b->elem[c] = 0, b->cols[c] = nullptr;
         if (!r->want(c)) continue;
-        b->elem[c] = kIsInt[c] ? 4 : 16;
-        if (int rc = column_to_host(r, b.get(), c, s->d_cols[c], b->elem[c], kNullable[c] ? s->d_valid[c] : nullptr, k, row_map, s->d_gather, r->stream))
+        b->elem[c] = kBam.col[c].elem;
+        if (int rc = column_to_host(r, b.get(), c, s->d_cols[c], b->elem[c], kBam.col[c].validity ? s->d_valid[c] : nullptr, k, row_map, s->d_gather, r->stream))
             return rc;
         any_side |= c == 0 || c == 6 || c == 8 || c == 9;
     }

@@ -195,18 +195,13 @@ static int plan_bgzf_shard(exg_reader *r, const std::string &path, uint64_t n, u
 // needed for the definition lines' strings alone, 2 % of it (the whole text went along until then: a bgzip FASTA into DataChunks
 // sent every byte back twice, 92 ms for 1.96 GB).
 enum PayloadRoute { kPayloadNone, kPayloadCompact, kPayloadMirror };
-// read_bed_file: the VARCHAR columns (0, 3, 5, 8, 10, 11) as a mask; the other six are BIGINT
-static constexpr uint64_t kBedStringCols = 0xD29ull;
-static inline bool bed_is_string(int c) { return (kBedStringCols >> c) & 1ull; }
 static PayloadRoute payload_route(const exg_reader *r) {
     if (r->format == EXG_FMT_BAM) return kPayloadNone;  // (a BAM segment is never mirrored: its strings are produced into a side buffer)
-    if (r->format == EXG_FMT_FASTA) {
-        return (r->want_cols & 3ull) && !switches().fasta_whole_text ? kPayloadCompact : kPayloadNone;
-    }
-    const uint64_t strs = r->format == EXG_FMT_VCF ? 0x1DDull : r->format == EXG_FMT_BED ? kBedStringCols : 0xFull, nested = r->format == EXG_FMT_VCF ? 0x1D4ull : 0ull;
-    const uint64_t sel = r->want_cols & strs;
+    const FormatDesc &f = format_desc(r->format);
+    const uint64_t strs = f.payload_mask(), sel = r->want_cols & strs;  // the columns whose strings point into the input
+    if (r->format == EXG_FMT_FASTA) return sel && !switches().fasta_whole_text ? kPayloadCompact : kPayloadNone;
     if (!sel) return kPayloadNone;
-    if (!switches().no_payload_compact && sel != strs && !(sel & nested)) return kPayloadCompact;
+    if (!switches().no_payload_compact && sel != strs && !(sel & f.nested_mask())) return kPayloadCompact;
     return switches().no_host_mirror ? kPayloadNone : kPayloadMirror;
 }
 
@@ -522,9 +517,6 @@ int open_next_file(exg_reader *r) {
     return r->fa_shard || r->range_preset || r->shard_count > 1 ? place_shard(r, *blk) : EXG_OK;
 }
 
-// the columns a text format's scan writes (BED: its twelve, the BIGINT ones among them — bed_is_string tells them apart)
-int n_string_cols(int format) { return format == EXG_FMT_FASTQ ? 4 : format == EXG_FMT_FASTA ? 3 : format == EXG_FMT_BED ? EXG_BED_COLUMNS : 9; }
-
 int next_batch(exg_reader *r, bool count_only, uint64_t *n_records_out);
 
 int advance_batch(exg_reader *r, bool *end) {
@@ -568,19 +560,18 @@ int ensure_device(exg_reader *r, uint64_t need_bytes) {
         need_bytes = std::max<uint64_t>(need_bytes, std::min<uint64_t>(r->device_batch_bytes, r->file->n) + kPrefetchSlack + 64);
     uint64_t cap = std::max<uint64_t>(need_bytes, 1 << 16);
     r->d_in_cap = cap;
-    // Rows the output vectors can hold.  Realistic density first (a FASTQ record under 32 bytes, a FASTA record
-    // or a VCF line under 16 would be unusual) — the worst case (FASTQ "@\n\n+\n" = 5 bytes, FASTA ">a\n" minus
-    // LF, a blank VCF line) would pin 16 B x 9 columns per input BYTE of device memory; a batch that does
+    // Rows the output vectors can hold.  Realistic density first (FormatDesc::bytes_per_row: a FASTQ record under 32 bytes, a FASTA
+    // record or a VCF line under 16 would be unusual) — the worst case (bytes_per_row_worst: FASTQ "@\n\n+\n" = 5 bytes, FASTA
+    // ">a\n" minus LF, a blank VCF line) would pin 16 B x 9 columns per input BYTE of device memory; a batch that does
     // overflow is reported by the kernels (EXG_RF_CAPACITY) and rescanned with worst-case vectors.
-    const uint64_t div = r->worst_case_rows ? (r->format == EXG_FMT_FASTQ ? 5 : r->format == EXG_FMT_FASTA ? 2 : 1)
-                                            : (r->format == EXG_FMT_FASTQ ? 32 : 16);
-    r->cap_records = cap / div + 4096;
+    const FormatDesc &f = format_desc(r->format);
+    r->cap_records = cap / (r->worst_case_rows ? f.bytes_per_row_worst : f.bytes_per_row) + 4096;
     r->ws_bytes = exg_scan_workspace_bytes(r->format, cap);
     if (r->mem_cap && !r->ws_full) {
         // The general path's line index is provisioned for min(n, 1 Mi) lines whatever the batch size (8 MiB; FASTA keeps
         // four such arrays): under a memory budget, one line per 8 bytes + 64 Ki — a denser batch is reported
         // (EXG_RF_INDEX_OVERFLOW) and scanned again with the full workspace
-        const uint64_t arrays = r->format == EXG_FMT_FASTA ? 4 : 1;
+        const uint64_t arrays = f.line_index_arrays;
         const exg::FastqWsLayout l = exg::fastq_ws_layout(cap, 0, arrays);
         const uint64_t lines = cap / 8 + 65536 + 8;
         r->ws_bytes = std::min<uint64_t>(r->ws_bytes, l.off_nl_pos + (lines + 2) * 8 * arrays);
@@ -598,17 +589,17 @@ int ensure_device(exg_reader *r, uint64_t need_bytes) {
         for (int k = 0; k < 2; k++) RD_HIP(r, hipEventCreateWithFlags(&r->up_done_of[k], hipEventDisableTiming));
     }
     if ((arc = r->dev_alloc(&r->d_ws, r->ws_bytes))) return arc;
-    for (int k = 0; k < 2; k++)
-        if ((arc = r->dev_alloc(&r->d_valid[k], (r->cap_records + 63) / 64 * 8))) return arc;
-    for (int c = 0; c < n_string_cols(r->format); c++)
-        if ((arc = r->dev_alloc(&r->d_cols[c], r->cap_records * (r->format == EXG_FMT_BED && !bed_is_string(c) ? 8 : 16)))) return arc;
-    if (r->format == EXG_FMT_BED)
-        for (int c = 3; c < EXG_BED_COLUMNS; c++)
-            if ((arc = r->dev_alloc(&r->d_bed_valid[c], (r->cap_records + 63) / 64 * 8))) return arc;
-    if (r->format == EXG_FMT_VCF) {
-        if ((arc = r->dev_alloc(&r->d_pos, r->cap_records * 8))) return arc;
-        if ((arc = r->dev_alloc(&r->d_qual, r->cap_records * 4))) return arc;
+    // per column: what the scan writes, the validity words of a nullable one, the vector of a number parsed beside its text
+    const uint64_t validity_bytes = (r->cap_records + 63) / 64 * 8;
+    for (int c = 0; c < f.n_columns; c++) {
+        const ColumnDesc &d = f.col[c];
+        if ((arc = r->dev_alloc(&r->d_cols[c], r->cap_records * f.scan_elem(c)))) return arc;
+        if (d.validity && (arc = r->dev_alloc(&r->d_col_valid[c], validity_bytes))) return arc;
+        if (void **parsed = r->parsed_vector(d.parsed))
+            if ((arc = r->dev_alloc(parsed, r->cap_records * d.elem))) return arc;
     }
+    for (uint32_t k = 0; k < f.spare_validity; k++)
+        if ((arc = r->dev_alloc(&r->d_valid_spare[k], validity_bytes))) return arc;
     if (r->format == EXG_FMT_FASTA && (arc = r->dev_alloc(&r->d_payload, cap + 64))) return arc;
     if (r->has_filter) {
         if ((arc = r->dev_alloc(&r->d_row_map, r->cap_records * 4 + 64))) return arc;
@@ -968,7 +959,7 @@ struct BatchRun {
         a.d_description = (exg_string_t *)r->d_cols[1];
         a.d_sequence = (exg_string_t *)r->d_cols[2];
         a.d_quality = (exg_string_t *)r->d_cols[3];
-        a.d_description_validity = (uint64_t *)r->d_valid[0];
+        a.d_description_validity = (uint64_t *)r->d_col_valid[1];
         return scan_rc(exg_fastq_scan(&a));
     }
     int launch_vcf(uint32_t algo) {
@@ -988,8 +979,8 @@ struct BatchRun {
         }
         a.d_pos = (int64_t *)r->d_pos;
         a.d_qual = (float *)r->d_qual;
-        a.d_qual_validity = (uint64_t *)r->d_valid[0];
-        a.d_formats_validity = (uint64_t *)r->d_valid[1];
+        a.d_qual_validity = (uint64_t *)r->d_col_valid[5];
+        a.d_formats_validity = (uint64_t *)r->d_col_valid[8];
         if (r->flat_pending) {  // (the batch before: its flat columns' copies read what this scan writes)
             RD_HIP(r, hipStreamWaitEvent(r->stream, r->flat_ev, 0));
             r->flat_pending = false;
@@ -1006,7 +997,7 @@ struct BatchRun {
         for (int c = 0; c < EXG_BED_COLUMNS; c++) {
             if (!r->want(c) && !((r->filter_cols >> c) & 1ull)) continue;
             a.d_columns[c] = r->d_cols[c];
-            a.d_validity[c] = (uint64_t *)r->d_bed_valid[c];
+            a.d_validity[c] = (uint64_t *)r->d_col_valid[c];
         }
         return scan_rc(exg_bed_scan(&a));
     }
@@ -1022,7 +1013,7 @@ struct BatchRun {
         a.d_id = (exg_string_t *)r->d_cols[0];
         a.d_description = (exg_string_t *)r->d_cols[1];
         a.d_sequence = (exg_string_t *)r->d_cols[2];
-        a.d_description_validity = (uint64_t *)r->d_valid[0];
+        a.d_description_validity = (uint64_t *)r->d_col_valid[1];
         a.d_seq_payload = (uint8_t *)r->d_payload;
         return scan_rc(exg_fasta_scan(&a));
     }
@@ -1050,7 +1041,7 @@ struct BatchRun {
 
     // ---- 6: what the result means for the attempt (the driver's switch acts on it), and for the scan the next batch starts with
     BatchVerdict judge() {
-        const uint64_t tile_bytes = r->format == EXG_FMT_FASTQ ? 3u * 16384u : 2u * 16384u;
+        const uint64_t tile_bytes = format_desc(r->format).tile_bytes;
         const bool vcf = r->format == EXG_FMT_VCF;
         const bool no_index = vcf && getenv("EXG_NO_VCF_INDEX") != nullptr;  // (per batch: the tests switch it inside one process)
         r->fused_algo = sticky_algo(r->fused_algo, res, in.n, in.lead, tile_bytes, vcf, no_index);
@@ -1085,28 +1076,17 @@ struct BatchRun {
         namespace ea = exg::arrow;
         ea::FilterCols fc;
         memset(&fc, 0, sizeof fc);
-        const int nsc = n_string_cols(r->format);
-        for (int c = 0; c < nsc; c++) {
-            fc.kind[c] = ea::kColStr;
-            fc.data[c] = r->d_cols[c];
+        const FormatDesc &f = format_desc(r->format);
+        for (int c = 0; c < f.n_columns; c++) {
+            fc.kind[c] = filter_col_kind(f.col[c]);
+            fc.data[c] = r->column_data(c).data;
+            fc.validity[c] = (const uint64_t *)r->d_col_valid[c];
             fc.d_base[c] = (const uint8_t *)in.d_input;
             fc.payload_base[c] = (uint64_t)(uintptr_t)in.h;
         }
-        if (r->format == EXG_FMT_BED) {
-            for (int c = 0; c < nsc; c++) {
-                if (!bed_is_string(c)) fc.kind[c] = ea::kColI64;
-                fc.validity[c] = (const uint64_t *)r->d_bed_valid[c];
-            }
-        } else if (r->format == EXG_FMT_VCF) {
-            fc.kind[1] = ea::kColI64, fc.data[1] = r->d_pos;
-            fc.kind[5] = ea::kColF32, fc.data[5] = r->d_qual, fc.validity[5] = (const uint64_t *)r->d_valid[0];
-            fc.validity[8] = (const uint64_t *)r->d_valid[1];
-        } else {
-            fc.validity[1] = (const uint64_t *)r->d_valid[0];
-            if (r->format == EXG_FMT_FASTA) {
-                fc.d_base[2] = (const uint8_t *)r->d_payload;
-                fc.payload_base[2] = (uint64_t)(uintptr_t)(in.b ? in.b->payload : nullptr);
-            }
+        if (r->format == EXG_FMT_FASTA) {  // its sequences are the joined payload, not the input
+            fc.d_base[2] = (const uint8_t *)r->d_payload;
+            fc.payload_base[2] = (uint64_t)(uintptr_t)(in.b ? in.b->payload : nullptr);
         }
         uint64_t *d_goff = (uint64_t *)r->d_filter_tmp, *d_tmp = d_goff + r->cap_records + 1;
         ea::FilterCols *d_fc = (ea::FilterCols *)r->d_gather;  // the scratch column is free until the gathers
@@ -1134,10 +1114,8 @@ struct BatchRun {
         b->file = in.gz_payload ? in.gz_payload : r->file;
         // the projection (exg_open_args.columns): every column was parsed and validated above, only the wanted ones travel.
         // A decoded input's bytes are what its strings point into: they travel when any string column does
-        const int ns = n_string_cols(r->format);
-        const bool any_strings = r->format == EXG_FMT_VCF   ? (r->want_cols & 0x1DDull) != 0
-                                 : r->format == EXG_FMT_BED ? (r->want_cols & kBedStringCols) != 0
-                                                            : (r->want_cols & ((1ull << ns) - 1)) != 0;
+        const FormatDesc &f = format_desc(r->format);
+        const bool any_strings = (r->want_cols & (f.string_mask() | f.nested_mask())) != 0;  // (a nested column's elements are strings too)
         if (in.gz_payload && any_strings && !in.gz_mirror) RD_HIP(r, hipMemcpyAsync(in.gz_payload->p, in.d_input, in.n, hipMemcpyDeviceToHost, r->stream));
         if (in.gz_mirror && in.gz_front) RD_HIP(r, hipMemcpyAsync(const_cast<uint8_t *>(in.h), in.d_input, in.gz_front, hipMemcpyDeviceToHost, r->stream));
         b->n_rows = k;
@@ -1145,19 +1123,17 @@ struct BatchRun {
         SideScratch side_scratch{r->device, r->stream, {}};
         int rc;
         if (in.compact && (rc = side_buffer(&side, &side_scratch))) return rc;
-        b->n_cols = ns;  // schema order (exg_schema_of): VCF exposes parsed POS / QUAL in place of their raw text
+        b->n_cols = f.n_columns;  // schema order (exg_schema_of): VCF exposes parsed POS / QUAL in place of their raw text
         ColDrain col_drain;
         hipStream_t cs = r->stream;
         if ((rc = columns_stream(&cs, &col_drain))) return rc;
         if ((rc = flat_columns(side, cs))) return rc;
-        if (r->format == EXG_FMT_VCF) {
-            if ((rc = vcf_nested_columns(cs, &col_drain))) return rc;
-        } else if (r->format == EXG_FMT_BED) {
-            for (int c = 3; c < EXG_BED_COLUMNS; c++)
-                if (r->want(c) && (rc = column_to_host(r, b, c, nullptr, 0, r->d_bed_valid[c], k, row_map, r->d_gather, cs))) return rc;
-        } else if (r->want(1) && (rc = column_to_host(r, b, 1, nullptr, 0, r->d_valid[0], k, row_map, r->d_gather, cs))) {
-            return rc;
-        }
+        // the validity words of every wanted nullable flat column (a nested column's validity is the emitter's)
+        for (int c = 0; c < f.n_columns; c++)
+            if (f.col[c].validity && !f.col[c].nested && r->want(c) &&
+                (rc = column_to_host(r, b, c, nullptr, 0, r->d_col_valid[c], k, row_map, r->d_gather, cs)))
+                return rc;
+        if (r->format == EXG_FMT_VCF && (rc = vcf_nested_columns(cs, &col_drain))) return rc;
         if (r->format == EXG_FMT_FASTA && res.payload_bytes && r->want(2) && (rc = fasta_sequences(cs))) return rc;
         const double t_cols = now_s();
         RD_HIP(r, hipStreamSynchronize(r->stream));
@@ -1176,13 +1152,13 @@ struct BatchRun {
     // compact: the selected string columns' out-of-line bytes, closed up per column into ONE side buffer
     int side_buffer(SideBuf *side, SideScratch *scratch) {
         namespace ea = exg::arrow;
-        const int ns = n_string_cols(r->format);
+        const FormatDesc &f = format_desc(r->format);
+        const int ns = f.n_columns;
+        const uint64_t compact = f.string_mask() & f.payload_mask();  // the flat strings that point into the input
         uint64_t *d_tmp = (uint64_t *)scratch->take((ea::scan_tmp_entries(k) + 2) * 8);
         if (!d_tmp) return fail(r, EXG_E_HIP, "out of device memory");
         for (int c = 0; c < ns; c++) {
-            if (!r->want(c) || (r->format == EXG_FMT_VCF && c != 0 && c != 3) || (r->format == EXG_FMT_FASTA && c == 2) ||
-                (r->format == EXG_FMT_BED && !bed_is_string(c)))
-                continue;
+            if (!r->want(c) || !((compact >> c) & 1ull)) continue;
             if (!(side->col[c].d_goff = (uint64_t *)scratch->take((k + 2) * 8))) return fail(r, EXG_E_HIP, "out of device memory");
             const ea::StrCol sc{(const exg_string_t *)r->d_cols[c], (const uint8_t *)in.d_input, (uint64_t)(uintptr_t)in.h};
             ea::payload_goff_from_col(sc, row_map, k, side->col[c].d_goff, d_tmp, r->stream);
@@ -1235,16 +1211,13 @@ struct BatchRun {
     // the flat columns the projection wants, each gathered through the row map and copied back
     int flat_columns(const SideBuf &side, hipStream_t cs) {
         Batch *b = in.b.get();
-        const bool nested_vcf = r->format == EXG_FMT_VCF;  // id, alt, filter, info, formats: built by nested_emit (vcf_nested_columns)
+        const FormatDesc &f = format_desc(r->format);
         for (int c = 0; c < b->n_cols; c++) {
             b->elem[c] = 0;
             b->cols[c] = nullptr;
-            if ((nested_vcf && (c == 2 || c == 4 || c >= 6)) || !r->want(c)) continue;
-            const void *src = r->d_cols[c];
-            uint32_t es = 16;
-            if (r->format == EXG_FMT_VCF && c == 1) src = r->d_pos, es = 8;
-            if (r->format == EXG_FMT_VCF && c == 5) src = r->d_qual, es = 4;
-            if (r->format == EXG_FMT_BED && !bed_is_string(c)) es = 8;
+            if (f.col[c].nested || !r->want(c)) continue;  // (VCF id, alt, filter, info, formats: built by nested_emit — vcf_nested_columns)
+            const void *src = r->column_data(c).data;
+            const uint32_t es = r->column_data(c).elem;
             b->elem[c] = es;
             int rc;
             if (in.compact && es == 16 && side.col[c].d_goff) {
@@ -1260,11 +1233,11 @@ struct BatchRun {
         }
         return EXG_OK;
     }
-    // read_vcf: QUAL's validity, then the hand-over to the nested columns' emitter (id, alt, filter, info, formats)
+    // read_vcf: behind the flat columns (QUAL's validity the last of them), the hand-over to the nested columns' emitter (id, alt,
+    // filter, info, formats)
     int vcf_nested_columns(hipStream_t cs, ColDrain *col_drain) {
         Batch *b = in.b.get();
         int rc;
-        if (r->want(5) && (rc = column_to_host(r, b, 5, nullptr, 0, r->d_valid[0], k, row_map, r->d_gather, cs))) return rc;
         if (r->lazy_landing) {
             RD_HIP(r, hipEventRecord(r->flat_ev, cs));  // (the scan's columns are free again behind this)
             r->flat_pending = true;
@@ -1337,7 +1310,7 @@ int next_batch(exg_reader *r, bool count_only, uint64_t *n_records_out) {
         if ((rc = ensure_device(r, in.n + in.shard_halo + 16))) return rc;
         if ((rc = run.bind_input())) return rc;
         if ((rc = run.fastq_first_line_phase())) return rc;
-        TraceRange scan_range(r->format == EXG_FMT_FASTQ ? "exg: scan fastq batch" : r->format == EXG_FMT_VCF ? "exg: scan vcf batch" : r->format == EXG_FMT_BED ? "exg: scan bed batch" : "exg: scan fasta batch");
+        TraceRange scan_range(format_desc(r->format).scan_label);
         if ((rc = run.scan())) return rc;
         switch (run.judge()) {  // (the only place that scans the batch again)
             case kAccept: break;

@@ -20,8 +20,6 @@
 
 using namespace exg_rd;
 
-static void flat_schema(const exg_reader *r, exg_schema *out);
-
 extern "C" int exg_open(const exg_open_args *args, exg_reader **out) {
     if (!args || !out || !args->path || !args->file_format) {
         exg::set_error("exg_open: null argument");
@@ -31,17 +29,10 @@ extern "C" int exg_open(const exg_open_args *args, exg_reader **out) {
     std::unique_ptr<exg_reader> r(new exg_reader());
     std::string fmt = args->file_format;
     for (char &ch : fmt) ch = (char)tolower((unsigned char)ch);
-    if (fmt == "fasta")
-        r->format = EXG_FMT_FASTA;
-    else if (fmt == "fastq")
-        r->format = EXG_FMT_FASTQ;
-    else if (fmt == "vcf")
-        r->format = EXG_FMT_VCF;
-    else if (fmt == "bam")
-        r->format = EXG_FMT_BAM;
-    else if (fmt == "bed")
-        r->format = EXG_FMT_BED, r->fused_algo = EXG_ALGO_FUSED_FULL;  // (one single-pass scan: exg_bed.hip)
-    else if (fmt == "sam") {
+    if (const FormatDesc *f = format_named(fmt.c_str())) {
+        r->format = f->format;
+        if (r->format == EXG_FMT_BED) r->fused_algo = EXG_ALGO_FUSED_FULL;  // (one single-pass scan: exg_bed.hip)
+    } else if (fmt == "sam") {
         exg::set_error("file_format sam is not supported: the SAM text tokeniser is not built (read_bam_file_records reads BAM)");
         return EXG_E_UNSUPPORTED;
     } else {
@@ -67,14 +58,8 @@ extern "C" int exg_open(const exg_open_args *args, exg_reader **out) {
     if (const char *e = getenv("EXG_DEVICE_MEM_CAP_MB")) {
         r->mem_cap = strtoull(e, nullptr, 10) << 20;
         r->meter.cap = r->mem_cap;
-        // (per input byte a scan provisions 16 B x columns / 32 (FASTQ) or / 16 (VCF: 9 columns + POS + QUAL) of column
-        // vectors; a compressed input adds up to four segments and two compressed windows)
-        // (24 for FASTQ: with 20 a single-member gzip under a 16 MiB cap peaked between 15.4 and 17.3 MB depending on how far the
-        // decoder thread happened to run ahead of the scan — the first round's symbol buffer is sized for the worst ratio)
-        // (BAM: segments as above, a workspace of ~0.8 B, a side buffer of ~1.25 B and ~2 B of vectors per decoded byte)
-        // (BED: 9 B of vectors + 1.5 B of workspace per byte of an input slot, two slots, and a slot is a batch + 1 MiB of prefetch
-        // slack: measured 17.0 MiB under a 16 MiB cap with batches of 256 KiB — a quarter of VCF's batch stays under it)
-        const uint64_t div = r->format == EXG_FMT_BED ? 256 : r->format == EXG_FMT_VCF ? 64 : r->format == EXG_FMT_FASTA || r->format == EXG_FMT_BAM ? 32 : 24;
+        // (the divisor per format, and what it was measured with: exg_rd_format.hpp)
+        const uint64_t div = format_desc(r->format).mem_cap_div;
         if (r->mem_cap) r->device_batch_bytes = std::max<uint64_t>(64u << 10, std::min<uint64_t>(r->device_batch_bytes, (r->mem_cap / div) & ~15ull));
     }
     r->halo_want = getenv("EXG_SHARD_HALO") ? std::max<uint64_t>(16, strtoull(getenv("EXG_SHARD_HALO"), nullptr, 10)) : kShardHalo;
@@ -116,11 +101,7 @@ extern "C" int exg_open(const exg_open_args *args, exg_reader **out) {
     }
     if (args->filters && *args->filters) {
         // `SELECT * FROM exon_table WHERE <filters>` (arrow_reader.rs:125-141), evaluated on the device
-        exg_schema sch;
-        flat_schema(r.get(), &sch);
-        std::vector<FilterColumn> fcols;  // nested columns ('x') are refused by the parser, like in new_reader
-        for (int c = 0; c < sch.n_columns; c++)
-            fcols.push_back({sch.names[c], sch.types[c] == EXG_TYPE_BIGINT ? 'l' : sch.types[c] == EXG_TYPE_INTEGER ? 'i' : sch.types[c] == EXG_TYPE_FLOAT ? 'f' : sch.types[c] == EXG_TYPE_VARCHAR ? 'u' : 'x'});
+        const std::vector<FilterColumn> fcols = filter_columns(format_desc(r->format));  // nested columns are refused by the parser, like in new_reader
         const std::string text = args->filters;
         FilterParser fp(text, fcols);
         bool parsed = false;
@@ -220,48 +201,14 @@ extern "C" int exg_open(const exg_open_args *args, exg_reader **out) {
     return EXG_OK;
 }
 
-// names / types of the columns; no file is touched (the VCF trees come from nested_schema)
+// names / types of the columns (exg_rd_format.hpp); no file is touched (the VCF trees come from nested_schema)
 static void flat_schema(const exg_reader *r, exg_schema *out) {
-    static const exg_type fastq_t[4] = {{EXG_TYPE_VARCHAR, 0, "name", 0, nullptr}, {EXG_TYPE_VARCHAR, 1, "description", 0, nullptr},
-                                        {EXG_TYPE_VARCHAR, 0, "sequence", 0, nullptr}, {EXG_TYPE_VARCHAR, 0, "quality_scores", 0, nullptr}};
-    static const exg_type fasta_t[3] = {{EXG_TYPE_VARCHAR, 0, "id", 0, nullptr}, {EXG_TYPE_VARCHAR, 1, "description", 0, nullptr},
-                                        {EXG_TYPE_VARCHAR, 0, "sequence", 0, nullptr}};
     memset(out, 0, sizeof *out);
-    if (r->format == EXG_FMT_FASTQ) {
-        // order pinned by test_fastq_scan.test:35-41; names as exon 0.2.6 registers them
-        out->n_columns = 4;
-        for (int i = 0; i < 4; i++) out->names[i] = fastq_t[i].name, out->types[i] = EXG_TYPE_VARCHAR, out->nullable[i] = fastq_t[i].nullable, out->tree[i] = &fastq_t[i];
-    } else if (r->format == EXG_FMT_FASTA) {
-        // `id` pinned by test_fasta_scan.test:34-37, order + NULL description by test_fasta_copy.test:75-80
-        out->n_columns = 3;
-        for (int i = 0; i < 3; i++) out->names[i] = fasta_t[i].name, out->types[i] = EXG_TYPE_VARCHAR, out->nullable[i] = fasta_t[i].nullable, out->tree[i] = &fasta_t[i];
-    } else if (r->format == EXG_FMT_BAM) {
-        // order pinned by test_bam_record_scan.test:5-17, names by test_sam_record_scan.test:6; the types are what exon 0.2.x is
-        // recalled to declare ([RECALLED])
-        static const exg_type bam_t[10] = {{EXG_TYPE_VARCHAR, 0, "name", 0, nullptr},           {EXG_TYPE_INTEGER, 0, "flag", 0, nullptr},
-                                           {EXG_TYPE_VARCHAR, 1, "reference", 0, nullptr},      {EXG_TYPE_INTEGER, 1, "start", 0, nullptr},
-                                           {EXG_TYPE_INTEGER, 1, "end", 0, nullptr},            {EXG_TYPE_VARCHAR, 1, "mapping_quality", 0, nullptr},
-                                           {EXG_TYPE_VARCHAR, 0, "cigar", 0, nullptr},          {EXG_TYPE_VARCHAR, 1, "mate_reference", 0, nullptr},
-                                           {EXG_TYPE_VARCHAR, 0, "sequence", 0, nullptr},       {EXG_TYPE_VARCHAR, 0, "quality_score", 0, nullptr}};
-        out->n_columns = 10;
-        for (int i = 0; i < 10; i++) out->names[i] = bam_t[i].name, out->types[i] = bam_t[i].type, out->nullable[i] = bam_t[i].nullable, out->tree[i] = &bam_t[i];
-    } else if (r->format == EXG_FMT_BED) {
-        // order pinned by test_bed_io.test:4-18; names and types as exon 0.2.6 is recalled to declare them ([RECALLED])
-        static const exg_type bed_t[EXG_BED_COLUMNS] = {
-            {EXG_TYPE_VARCHAR, 0, "reference_sequence_name", 0, nullptr}, {EXG_TYPE_BIGINT, 0, "start", 0, nullptr},
-            {EXG_TYPE_BIGINT, 0, "end", 0, nullptr},                      {EXG_TYPE_VARCHAR, 1, "name", 0, nullptr},
-            {EXG_TYPE_BIGINT, 1, "score", 0, nullptr},                    {EXG_TYPE_VARCHAR, 1, "strand", 0, nullptr},
-            {EXG_TYPE_BIGINT, 1, "thick_start", 0, nullptr},              {EXG_TYPE_BIGINT, 1, "thick_end", 0, nullptr},
-            {EXG_TYPE_VARCHAR, 1, "color", 0, nullptr},                   {EXG_TYPE_BIGINT, 1, "block_count", 0, nullptr},
-            {EXG_TYPE_VARCHAR, 1, "block_sizes", 0, nullptr},             {EXG_TYPE_VARCHAR, 1, "block_starts", 0, nullptr}};
-        out->n_columns = EXG_BED_COLUMNS;
-        for (int i = 0; i < EXG_BED_COLUMNS; i++) out->names[i] = bed_t[i].name, out->types[i] = bed_t[i].type, out->nullable[i] = bed_t[i].nullable, out->tree[i] = &bed_t[i];
-    } else {
-        // test_vcf_record_scan.test:10-19: alt is a LIST, info a STRUCT (module.cpp:126-147 maps exon's Arrow schema)
-        static const char *n[] = {"chrom", "pos", "id", "ref", "alt", "qual", "filter", "info", "formats"};
-        static const int t[] = {EXG_TYPE_VARCHAR, EXG_TYPE_BIGINT, EXG_TYPE_LIST, EXG_TYPE_VARCHAR, EXG_TYPE_LIST, EXG_TYPE_FLOAT, EXG_TYPE_LIST, EXG_TYPE_STRUCT, EXG_TYPE_LIST};
-        out->n_columns = 9;
-        for (int i = 0; i < 9; i++) out->names[i] = n[i], out->types[i] = t[i], out->nullable[i] = !(i == 0 || i == 1 || i == 3);
+    const FormatDesc &f = format_desc(r->format);
+    out->n_columns = f.n_columns;
+    for (int c = 0; c < f.n_columns; c++) {
+        out->names[c] = f.col[c].name, out->types[c] = f.col[c].type, out->nullable[c] = f.col[c].nullable;
+        if (!f.col[c].nested) out->tree[c] = flat_tree(r->format, c);
     }
 }
 

@@ -13,6 +13,7 @@
 
 #include "exg_block_pool.hpp"
 #include "exg_common.hpp"
+#include "exg_rd_format.hpp"
 
 // exg_crc32.hip: bytes (a multiple of 4, both ends 4-byte aligned) of device memory written to pinned host memory by a kernel on
 // `stream` — a decoder's small results, which a copy would queue behind the big copies of its SDMA engine
@@ -462,10 +463,25 @@ struct exg_reader {
     void *d_filter_prog = nullptr, *d_filter_consts = nullptr;  // pooled
     size_t filter_prog_bytes = 0, filter_consts_bytes = 0;
     void *d_row_map = nullptr, *d_gather = nullptr, *d_filter_tmp = nullptr;  // output vectors sized for the densest possible input (after an overflow)
-    void *d_valid[2] = {nullptr, nullptr};
-    void *d_cols[12] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    void *d_bed_valid[12] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // BED: columns 3 .. 11
-    void *d_pos = nullptr, *d_qual = nullptr, *d_payload = nullptr;
+    // per schema column (exg_rd_format.hpp): what the scan writes — a string_t per row, BED's BIGINT columns 8 bytes — and, for the
+    // columns the table marks `validity`, their validity words (FASTQ / FASTA: 1; VCF: 5 and 8; BED: 3 .. 11)
+    void *d_cols[exg_rd::kMaxColumns] = {};
+    void *d_col_valid[exg_rd::kMaxColumns] = {};
+    void *d_valid_spare[2] = {nullptr, nullptr};  // (FormatDesc::spare_validity)
+    void *d_pos = nullptr, *d_qual = nullptr, *d_payload = nullptr;  // VCF: the parsed POS / QUAL; FASTA: the joined sequences
+    // the vector a column's parsed numbers go to, beside the field's text in d_cols (NULL: the column has none)
+    void **parsed_vector(exg_rd::ParsedVector which) { return which == exg_rd::kParsedPos ? &d_pos : which == exg_rd::kParsedQual ? &d_qual : nullptr; }
+    // the typed device data of flat column c and its element size at the chunk boundary (VCF pos / qual: the parsed vectors, not
+    // the field's text in d_cols)
+    struct ColumnData {
+        const void *data;
+        uint32_t elem;
+    };
+    ColumnData column_data(int c) const {
+        const exg_rd::ColumnDesc &d = exg_rd::format_desc(format).col[c];
+        void **parsed = const_cast<exg_reader *>(this)->parsed_vector(d.parsed);
+        return {parsed ? *parsed : d_cols[c], d.elem};
+    }
     uint64_t d_in_cap = 0, ws_bytes = 0, cap_records = 0;
     uint64_t vcf_header_bytes = 0;
     struct FdCloser {

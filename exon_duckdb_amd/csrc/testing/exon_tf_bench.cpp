@@ -585,14 +585,8 @@ extern "C" int exon_tf_drain_arrow_vcf(const char *path, const char *compression
 // parser's message in `out`.
 extern "C" int exon_tf_filter_explain(const char *file_format, const char *filters, char *out, size_t cap) {
     namespace ea = exg::arrow;
-    std::vector<exg_rd::FilterColumn> cols;
     const std::string fmt = file_format ? file_format : "";
-    if (fmt == "fastq")
-        cols = {{"name", 'u'}, {"description", 'u'}, {"sequence", 'u'}, {"quality_scores", 'u'}};
-    else if (fmt == "fasta")
-        cols = {{"id", 'u'}, {"description", 'u'}, {"sequence", 'u'}};
-    else
-        cols = {{"chrom", 'u'}, {"pos", 'l'}, {"id", 'x'}, {"ref", 'u'}, {"alt", 'x'}, {"qual", 'f'}, {"filter", 'x'}, {"info", 'x'}, {"formats", 'x'}};
+    const std::vector<exg_rd::FilterColumn> cols = exg_rd::filter_columns(exg_rd::format_desc(fmt == "fastq" ? EXG_FMT_FASTQ : fmt == "fasta" ? EXG_FMT_FASTA : EXG_FMT_VCF));
     const std::string text = filters ? filters : "";
     exg_rd::FilterParser fp(text, cols);
     std::string res;

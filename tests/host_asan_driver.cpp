@@ -3,7 +3,7 @@
 // reader (exg_rd_bgzf.cpp), the zstd frame / block walk (exg_zstd_index.cpp), the VCF header parser (exg_vcf_header.cpp)
 // and the `filters` parser (exg_filter.hpp) on valid inputs, on truncations of them and on random mutations — every byte
 // these parsers read comes from a user's file or query text.  Also what else of the host path makes no HIP call: next_batch's
-// decisions (exg_rd_stages.hpp), the shard planner, the pinned-block pool, the map guard, the fan-out's run-ahead.
+// decisions (exg_rd_stages.hpp), the format table (exg_rd_format.hpp), the shard planner, the pinned-block pool, the map guard, the fan-out's run-ahead.
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -375,6 +375,66 @@ int main(int argc, char **argv) {
                     if (flen && (f.start + flen > range_hi || flen + 16 > d_in_cap || flen > step)) return 16;
                     runs++;
                 }
+    }
+    // the format table (exg_rd_format.hpp) against every format's columns written out: name, type, nullable, bytes per row at the
+    // chunk boundary (0: a nested column), and the masks and sizing constants the reader's stages take from it
+    {
+        using namespace exg_rd;
+        enum { V = EXG_TYPE_VARCHAR, B = EXG_TYPE_BIGINT, F = EXG_TYPE_FLOAT, I = EXG_TYPE_INTEGER, L = EXG_TYPE_LIST, S = EXG_TYPE_STRUCT };
+        struct Col { const char *name; int type; bool nullable; int elem; };
+        struct Want {
+            int format; const char *name; int n;
+            Col col[12];
+            uint64_t strings, payload, nested, validity, nullable;
+            unsigned mem_cap_div, bytes_per_row, bytes_per_row_worst, tile_bytes, line_index_arrays;
+        };
+        const Want want[] = {
+            {EXG_FMT_FASTQ, "fastq", 4, {{"name", V, false, 16}, {"description", V, true, 16}, {"sequence", V, false, 16}, {"quality_scores", V, false, 16}},
+             0xF, 0xF, 0, 0x2, 0x2, 24, 32, 5, 49152, 1},
+            {EXG_FMT_FASTA, "fasta", 3, {{"id", V, false, 16}, {"description", V, true, 16}, {"sequence", V, false, 16}}, 0x7, 0x3, 0, 0x2, 0x2, 32, 16, 2, 32768, 4},
+            {EXG_FMT_VCF, "vcf", 9,
+             {{"chrom", V, false, 16}, {"pos", B, false, 8}, {"id", L, true, 0}, {"ref", V, false, 16}, {"alt", L, true, 0}, {"qual", F, true, 4},
+              {"filter", L, true, 0}, {"info", S, true, 0}, {"formats", L, true, 0}},
+             0x9, 0x1DD, 0x1D4, 0x120, 0x1F4, 64, 16, 1, 32768, 1},
+            {EXG_FMT_BAM, "bam", 10,
+             {{"name", V, false, 16}, {"flag", I, false, 4}, {"reference", V, true, 16}, {"start", I, true, 4}, {"end", I, true, 4},
+              {"mapping_quality", V, true, 16}, {"cigar", V, false, 16}, {"mate_reference", V, true, 16}, {"sequence", V, false, 16},
+              {"quality_score", V, false, 16}},
+             0x3E5, 0, 0, 0xBC, 0xBC, 32, 1, 1, 1, 1},  // (behind the divisor: not read for BAM, 1 like a format there is none of)
+            {EXG_FMT_BED, "bed", 12,
+             {{"reference_sequence_name", V, false, 16}, {"start", B, false, 8}, {"end", B, false, 8}, {"name", V, true, 16}, {"score", B, true, 8},
+              {"strand", V, true, 16}, {"thick_start", B, true, 8}, {"thick_end", B, true, 8}, {"color", V, true, 16}, {"block_count", B, true, 8},
+              {"block_sizes", V, true, 16}, {"block_starts", V, true, 16}},
+             0xD29, 0xD29, 0, 0xFF8, 0xFF8, 256, 16, 1, 32768, 1},
+        };
+        for (const Want &w : want) {
+            const FormatDesc &f = format_desc(w.format);
+            if (f.format != w.format || strcmp(f.name, w.name) || format_named(w.name) != &f || f.n_columns != w.n) return 17;
+            for (int c = 0; c < w.n; c++) {
+                const ColumnDesc &d = f.col[c];
+                if (strcmp(d.name, w.col[c].name) || d.type != w.col[c].type || d.nullable != w.col[c].nullable || d.elem != w.col[c].elem) return 17;
+                // (the VCF scan writes every field's text, 16 bytes a row, also where the column leaves as a number or nested)
+                if (d.nested != (d.elem == 0) || (d.validity && !d.nullable) || f.scan_elem(c) != (w.format == EXG_FMT_VCF ? 16u : (unsigned)w.col[c].elem)) return 17;
+                const char k = filter_kind(d);
+                if (k != (d.type == V ? 'u' : d.type == B ? 'l' : d.type == I ? 'i' : d.type == F ? 'f' : 'x')) return 17;
+                runs++;
+            }
+            if (f.string_mask() != w.strings || f.payload_mask() != w.payload || f.nested_mask() != w.nested || f.validity_mask() != w.validity ||
+                f.nullable_mask() != w.nullable)
+                return 17;
+            if (f.mem_cap_div != w.mem_cap_div || f.bytes_per_row != w.bytes_per_row || f.bytes_per_row_worst != w.bytes_per_row_worst ||
+                f.tile_bytes != w.tile_bytes || f.line_index_arrays != w.line_index_arrays)
+                return 17;
+            for (int c = 0; c < w.n; c++) {  // the leaf exg_schema_of hands out for a flat column
+                const exg_type *t = flat_tree(w.format, c);
+                if (t->type != w.col[c].type || t->nullable != (int)w.col[c].nullable || strcmp(t->name, w.col[c].name) || t->n_children || t->children) return 17;
+            }
+            const std::vector<FilterColumn> fc = filter_columns(f);
+            if ((int)fc.size() != w.n || fc[0].name != w.col[0].name) return 17;
+        }
+        // a format there is none of: no columns; "sam" and any other spelling are not in the table (exg_open refuses them by name)
+        if (format_desc(0).n_columns != 0 || format_desc(99).n_columns != 0 || format_desc(99).line_index_arrays != 1) return 17;
+        if (format_named("sam") || format_named("") || format_named("FASTQ") || format_named("fastqx")) return 17;
     }
     // host XXH64 (the checksum of big zstd frames): the specification's known answers, and any way of cutting the input
     // into updates gives the one-shot digest

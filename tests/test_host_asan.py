@@ -1,5 +1,5 @@
 """AddressSanitizer + UBSan build of the host-only parsers of libexon_gpu (gzip member index, the BGZF member walk, zstd
-frame / block walk, the VCF header parser, the shard planner, the `filters` grammar, next_batch's HIP-free decisions), driven over valid streams, truncations and random mutations (tests/host_asan_driver.cpp).  GPU
+frame / block walk, the VCF header parser, the shard planner, the `filters` grammar, next_batch's HIP-free decisions, the format table), driven over valid streams, truncations and random mutations (tests/host_asan_driver.cpp).  GPU
 sanitizers do not exist on the pool; everything these parsers read is user input."""
 import gzip
 import os
