@@ -12,11 +12,13 @@
 // Build (out-of-tree extension, like the reference's CMakeLists.txt:131-146, minus Rust/Corrosion):
 //   c++ -std=c++17 -fPIC -shared -DDUCKDB_BUILD_LOADABLE_EXTENSION -I<duckdb>/src/include -I../include
 //       -I../exon_duckdb_amd/csrc exon_extension.cpp -L../exon_duckdb_amd/lib -lexon_gpu -o exon.duckdb_extension
-// tests/test_host_logic.py puts this file through `c++ -fsyntax-only` against declaration-only stand-ins of the ten DuckDB
+// tests/test_host_logic.py puts this file through `c++ -fsyntax-only` against declaration-only stand-ins of the DuckDB
 // headers it includes (tests/duckdb_stub/: signatures as in v0.8.1): every template instantiation of the glue over DuckDB's
 // types is compiled on the build box.
 #define DUCKDB_EXTENSION_MAIN
 #include "duckdb.hpp"
+#include "duckdb/common/exception.hpp"
+#include "duckdb/common/types/vector.hpp"
 #include "duckdb/common/types/vector_buffer.hpp"
 #include "duckdb/function/scalar_function.hpp"
 #include "duckdb/function/table_function.hpp"
@@ -252,11 +254,104 @@ static void QualityScoreStringToList(DataChunk &args, ExpressionState &, Vector 
 	ListVector::SetListSize(result, total);
 }
 
+// sequence_functions/module.cpp:30-121, :168-362: complement, reverse_complement (what the reference computes: A->C, T->G,
+// C->A, G->T, order kept), transcribe, reverse_transcribe, translate_dna_to_aa.  The rules are csrc/exg_seqfn.hpp's; an
+// invalid row throws the reference's InvalidInputException text.  NULL in, NULL out (the reference's
+// GetValue(...).ToString() would read a NULL of a flat vector as the text "NULL").
+static void SequenceMapFunction(uint32_t op, DataChunk &args, Vector &result) {
+	const idx_t count = args.size();
+	UnifiedVectorFormat in;
+	args.data[0].ToUnifiedFormat(count, in);
+	auto strings = reinterpret_cast<const string_t *>(in.data);
+	result.SetVectorType(VectorType::FLAT_VECTOR);
+	auto out = FlatVector::GetData<string_t>(result);
+	std::string buf;
+	for (idx_t i = 0; i < count; i++) {
+		const idx_t k = in.sel->get_index(i);
+		if (!in.validity.RowIsValid(k)) {
+			FlatVector::SetNull(result, i, true);
+			continue;
+		}
+		const idx_t n = strings[k].GetSize();
+		buf.resize(exon_scan::SequenceOutputLength(op, n));
+		const exon_scan::SequenceStatus st = exon_scan::SequenceMap(op, strings[k].GetData(), n, &buf[0]);
+		if (st.code) {
+			throw InvalidInputException(exon_scan::SequenceErrorText(st));
+		}
+		out[i] = StringVector::AddString(result, buf.data(), buf.size());
+	}
+}
+
+// module.cpp:131-158: gc_content(VARCHAR) -> FLOAT.  A flat vector with every row on its own: the reference's early return
+// on an empty string (:145) leaves the rest of its chunk unset, which is not reproduced.
+static void GcContentFunction(DataChunk &args, ExpressionState &, Vector &result) {
+	const idx_t count = args.size();
+	UnifiedVectorFormat in;
+	args.data[0].ToUnifiedFormat(count, in);
+	auto strings = reinterpret_cast<const string_t *>(in.data);
+	result.SetVectorType(VectorType::FLAT_VECTOR);
+	auto out = FlatVector::GetData<float>(result);
+	for (idx_t i = 0; i < count; i++) {
+		const idx_t k = in.sel->get_index(i);
+		if (!in.validity.RowIsValid(k)) {
+			FlatVector::SetNull(result, i, true);
+			out[i] = 0;
+			continue;
+		}
+		out[i] = exon_scan::GcContent(strings[k].GetData(), strings[k].GetSize());
+	}
+}
+
+// sam_functions/module.cpp:143-154: is_segmented .. is_supplementary (INTEGER) -> BOOLEAN, bit `which` of (uint16_t)flag
+static void SamFlagFunction(uint32_t which, DataChunk &args, Vector &result) {
+	const idx_t count = args.size();
+	UnifiedVectorFormat in;
+	args.data[0].ToUnifiedFormat(count, in);
+	auto flags = reinterpret_cast<const int32_t *>(in.data);
+	result.SetVectorType(VectorType::FLAT_VECTOR);
+	auto out = FlatVector::GetData<bool>(result);
+	for (idx_t i = 0; i < count; i++) {
+		const idx_t k = in.sel->get_index(i);
+		if (!in.validity.RowIsValid(k)) {
+			FlatVector::SetNull(result, i, true);
+			out[i] = false;
+			continue;
+		}
+		out[i] = exon_scan::SamFlag(which, flags[k]);
+	}
+}
+
+// exon_extension.cpp:62-73: the sequence scalars and the flag predicates (parse_cigar, extract_from_cigar,
+// gff_parse_attributes and the alignment functions are not registered: INTEGRATION.md)
+static void RegisterScalars(DatabaseInstance &db) {
+	static const struct {
+		const char *name;
+		uint32_t op;
+	} kSequenceMaps[] = {{"complement", EXG_SEQ_COMPLEMENT},
+	                     {"reverse_complement", EXG_SEQ_REVERSE_COMPLEMENT},
+	                     {"transcribe", EXG_SEQ_TRANSCRIBE},
+	                     {"reverse_transcribe", EXG_SEQ_REVERSE_TRANSCRIBE},
+	                     {"translate_dna_to_aa", EXG_SEQ_TRANSLATE}};
+	for (const auto &f : kSequenceMaps) {
+		const uint32_t op = f.op;
+		ExtensionUtil::RegisterFunction(
+		    db, ScalarFunction(f.name, {LogicalType::VARCHAR}, LogicalType::VARCHAR,
+		                       [op](DataChunk &args, ExpressionState &, Vector &result) { SequenceMapFunction(op, args, result); }));
+	}
+	ExtensionUtil::RegisterFunction(db, ScalarFunction("gc_content", {LogicalType::VARCHAR}, LogicalType::FLOAT, GcContentFunction));
+	for (uint32_t which = 0; which < (uint32_t)exg::seqfn::kSamFlagCount; which++) {
+		ExtensionUtil::RegisterFunction(
+		    db, ScalarFunction(exg::seqfn::kSamFlagNames[which], {LogicalType::INTEGER}, LogicalType::BOOLEAN,
+		                       [which](DataChunk &args, ExpressionState &, Vector &result) { SamFlagFunction(which, args, result); }));
+	}
+}
+
 // exon/src/exon_extension.cpp:25-96, restricted to the path
 static void LoadInternal(DatabaseInstance &db) {
 	for (const auto &reg : exon_scan::kRegistrations) {
 		Register(reg.name, reg.file_type, db);
 	}
+	RegisterScalars(db);
 	// exon_extension.cpp:60 (FastqFunctions::GetQualityScoreStringToList)
 	ExtensionUtil::RegisterFunction(db, ScalarFunction("quality_score_string_to_list", {LogicalType::VARCHAR},
 	                                                   LogicalType::LIST(LogicalType::INTEGER), QualityScoreStringToList));

@@ -39,6 +39,9 @@ EXG_PE_BED_SCORE = 25
 EXG_PE_BED_STRAND = 26
 EXG_PE_BED_COLOR = 27
 EXG_PE_BED_BLOCKS = 28
+EXG_PE_SEQ_INVALID_CHARACTER = 30   # (29 is unassigned)
+EXG_PE_SEQ_LENGTH = 31
+EXG_PE_SEQ_CODON = 32
 
 EXG_FMT_FASTA, EXG_FMT_FASTQ, EXG_FMT_VCF, EXG_FMT_BAM, EXG_FMT_BED = 1, 2, 3, 4, 5
 EXG_BAM_COLUMNS = 10
@@ -48,6 +51,9 @@ EXG_RF_NON_ASCII, EXG_RF_HEAD_UNRESOLVED, EXG_RF_FALLBACK, EXG_RF_CAPACITY, EXG_
 EXG_RF_QUAL_RANGE = 32
 EXG_RF_REDO = 64
 EXG_ALGO_AUTO, EXG_ALGO_MULTIPASS, EXG_ALGO_FUSED, EXG_ALGO_FUSED_FULL, EXG_ALGO_FUSED_INDEX = 0, 1, 2, 3, 4
+
+EXG_SEQ_COMPLEMENT, EXG_SEQ_REVERSE_COMPLEMENT, EXG_SEQ_TRANSCRIBE, EXG_SEQ_REVERSE_TRANSCRIBE = 1, 2, 3, 4
+EXG_SEQ_TRANSLATE, EXG_SEQ_GC_CONTENT = 5, 6
 
 EXG_SYNTH_FASTQ_SEED = 0xE0A5EED0001
 EXG_SYNTH_VCF_SEED = 0xE0A5EED0002
@@ -204,6 +210,38 @@ class QualityListArgs(C.Structure):
     ]
 
 
+class SeqResult(C.Structure):
+    _fields_ = [
+        ("total_bytes", C.c_uint64),
+        ("error_row", C.c_uint64),
+        ("error_offset", C.c_uint64),
+        ("error_length", C.c_uint64),
+        ("error_code", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("error_bytes", C.c_uint8 * 4),
+        ("pad", C.c_uint8 * 20),
+    ]
+
+
+class SequenceOpArgs(C.Structure):
+    _fields_ = [
+        ("op", C.c_uint32),
+        ("d_strings", C.c_void_p),
+        ("n_rows", C.c_uint64),
+        ("d_payload", C.c_void_p),
+        ("payload_base", C.c_uint64),
+        ("d_out_strings", C.c_void_p),
+        ("d_out_payload", C.c_void_p),
+        ("out_capacity", C.c_uint64),
+        ("out_base", C.c_uint64),
+        ("d_out_float", C.c_void_p),
+        ("d_workspace", C.c_void_p),
+        ("workspace_bytes", C.c_uint64),
+        ("d_result", C.c_void_p),
+        ("stream", C.c_void_p),
+    ]
+
+
 class OpenArgs(C.Structure):
     _fields_ = [("path", C.c_char_p), ("file_format", C.c_char_p), ("compression", C.c_char_p), ("batch_rows", C.c_uint64),
                 ("device", C.c_int), ("device_batch_bytes", C.c_uint64), ("filters", C.c_char_p),
@@ -240,6 +278,9 @@ SIGNATURES = {
     "exg_count_newlines": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]),
     "exg_quality_list_workspace_bytes": (C.c_uint64, [C.c_uint64]),
     "exg_quality_score_list": (C.c_int, [C.POINTER(QualityListArgs)]),
+    "exg_sequence_workspace_bytes": (C.c_uint64, [C.c_uint32, C.c_uint64]),
+    "exg_sequence_op": (C.c_int, [C.POINTER(SequenceOpArgs)]),
+    "exg_sequence_result": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(SeqResult)]),
     "exg_plan_shards": (C.c_int, [C.POINTER(OpenArgs), C.POINTER(C.c_uint32), C.POINTER(C.c_int), C.c_uint32]),
 }
 
@@ -275,6 +316,8 @@ TEST_SIGNATURES = {
     "exon_tf_expect_vcf_file": (C.c_int, [C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "exon_tf_filter_explain": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_size_t]),
     "exon_tf_vcf_header_explain": (C.c_int, [C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t]),
+    "exon_tf_sequence_fn": (C.c_int, [C.c_uint32, C.c_char_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p, C.c_uint64]),
+    "exon_tf_sam_flag": (C.c_int, [C.c_uint32, C.c_int32]),
     "exon_tf_link_probe": (C.c_int, [C.c_int, C.c_uint64, C.c_int, C.POINTER(C.c_double)]),
     "exon_tf_host_pipeline_probe": (C.c_double, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double]),
     "exon_tf_host_zero_bounce_probe": (C.c_double, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(C.c_double)]),

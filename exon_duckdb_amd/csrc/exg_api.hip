@@ -79,6 +79,9 @@ extern "C" const char *exg_parse_error_string(uint32_t code) {
         case EXG_PE_BED_STRAND: return "invalid strand";
         case EXG_PE_BED_COLOR: return "invalid color";
         case EXG_PE_BED_BLOCKS: return "invalid block sizes or block starts";
+        case EXG_PE_SEQ_INVALID_CHARACTER: return "invalid character in sequence";
+        case EXG_PE_SEQ_LENGTH: return "invalid sequence length";
+        case EXG_PE_SEQ_CODON: return "invalid codon";
         default: return "unknown parse error";
     }
 }

@@ -46,6 +46,7 @@
 #include <vector>
 
 #include "exon_gpu.h"
+#include "exg_seqfn.hpp"
 
 namespace exon_scan {
 
@@ -311,6 +312,62 @@ struct ExonTableFunction {
 static inline void QualityScores(const char *s, size_t n, int32_t *out) {
     for (size_t i = 0; i < n; i++) out[i] = (int32_t)(signed char)s[i] - 33;
 }
+
+// The sequence scalars (exon/src/exon/sequence_functions/module.cpp:30-370) and the SAM flag predicates
+// (sam_functions/module.cpp:143-154): the per-row arithmetic of the SQL scalars the shim registers, on the tables of
+// exg_seqfn.hpp (exg_sequence_op is the same rules on a scan column that is still in HBM).  A status instead of an
+// exception: the caller formats the reference's text with SequenceErrorText.
+struct SequenceStatus {
+    uint32_t code = EXG_PE_NONE;  // EXG_PE_SEQ_*
+    uint64_t offset = 0;          // of the bad byte / codon; 0 for the length error
+    uint64_t length = 0;          // of the row
+    uint8_t bytes[4] = {0, 0, 0, 0};
+};
+static inline size_t SequenceOutputLength(uint32_t op, size_t n) { return (size_t)exg::seqfn::output_length(op, n); }
+// the five VARCHAR -> VARCHAR functions (op = EXG_SEQ_COMPLEMENT .. EXG_SEQ_TRANSLATE); out holds SequenceOutputLength(op, n) bytes
+static inline SequenceStatus SequenceMap(uint32_t op, const char *s, size_t n, char *out) {
+    namespace sf = exg::seqfn;
+    SequenceStatus st;
+    st.length = n;
+    const uint8_t *u = reinterpret_cast<const uint8_t *>(s);
+    if (op == EXG_SEQ_TRANSLATE) {
+        if (n % 3) {
+            st.code = EXG_PE_SEQ_LENGTH;
+            return st;
+        }
+        for (size_t i = 0; i < n / 3; i++) {
+            const uint8_t *c = u + 3 * i;
+            if (!sf::codon_ok(c[0], c[1], c[2])) {
+                st.code = EXG_PE_SEQ_CODON, st.offset = 3 * i;
+                memcpy(st.bytes, c, 3);
+                return st;
+            }
+            out[i] = sf::codon_aa(sf::codon_index(c[0], c[1], c[2]));
+        }
+        return st;
+    }
+    const sf::ByteMap m = sf::byte_map(op);
+    for (size_t i = 0; i < n; i++) {
+        if (!sf::base_ok(m.from, u[i])) {
+            st.code = EXG_PE_SEQ_INVALID_CHARACTER, st.offset = i, st.bytes[0] = u[i];
+            return st;
+        }
+        out[i] = (char)sf::base_to(m.to, u[i]);
+    }
+    return st;
+}
+static inline float GcContent(const char *s, size_t n) {
+    uint32_t count = 0;
+    for (size_t i = 0; i < n; i++) count += exg::seqfn::is_gc((uint8_t)s[i]) ? 1u : 0u;
+    return exg::seqfn::gc_ratio(count, (uint32_t)n);
+}
+static inline std::string SequenceErrorText(const SequenceStatus &st) {
+    char buf[96];
+    const size_t k = exg::seqfn::format_error(st.code, st.bytes, st.length, buf, sizeof buf);
+    return std::string(buf, k);
+}
+// is_segmented .. is_supplementary: `which` indexes exg::seqfn::kSamFlagNames
+static inline bool SamFlag(uint32_t which, int32_t flag) { return exg::seqfn::sam_flag(which, flag); }
 
 // exon/src/exon_extension.cpp:47-58: the registrations of the path (+ the read_vcf alias the north star names)
 struct Registration {

@@ -211,6 +211,37 @@ extern "C" uint64_t exon_tf_cardinality(exon_tf_handle *h) {
 }
 // the arithmetic of the SQL scalar quality_score_string_to_list as the shim registers it (fastq_functions/module.cpp:28-54)
 extern "C" void exon_tf_quality_scores(const char *s, uint64_t n, int32_t *out) { exon_scan::QualityScores(s, (size_t)n, out); }
+// the arithmetic of the sequence scalars as the shim registers them (sequence_functions/module.cpp:30-370).  op = EXG_SEQ_*:
+// the string ops write their output (*out_len bytes) to out, gc_content writes one float there.  0, or EXG_E_PARSE with the
+// reference's exception text in err (*out_len = its length); EXG_E_CAPACITY when out is too small (*out_len = what it takes)
+extern "C" int exon_tf_sequence_fn(uint32_t op, const char *s, uint64_t n, char *out, uint64_t out_cap, uint64_t *out_len, char *err,
+                                   uint64_t err_cap) {
+    if (err_cap) err[0] = 0;
+    if (op == EXG_SEQ_GC_CONTENT) {
+        *out_len = sizeof(float);
+        if (out_cap < sizeof(float)) return EXG_E_CAPACITY;
+        const float f = exon_scan::GcContent(s, (size_t)n);
+        memcpy(out, &f, sizeof f);
+        return EXG_OK;
+    }
+    if (!exg::seqfn::is_string_op(op)) return EXG_E_INVALID_ARG;
+    *out_len = exon_scan::SequenceOutputLength(op, (size_t)n);
+    if (out_cap < *out_len) return EXG_E_CAPACITY;
+    const exon_scan::SequenceStatus st = exon_scan::SequenceMap(op, s, (size_t)n, out);
+    if (!st.code) return EXG_OK;
+    const std::string text = exon_scan::SequenceErrorText(st);
+    if (err_cap) {
+        const size_t k = text.size() < err_cap - 1 ? text.size() : (size_t)err_cap - 1;
+        memcpy(err, text.data(), k);
+        err[k] = 0;
+        *out_len = k;  // (the text may hold a NUL: the offending byte goes in raw)
+    }
+    return EXG_E_PARSE;
+}
+// is_segmented .. is_supplementary (which = 0 .. 11) of an INTEGER flag; -1 for an unknown predicate
+extern "C" int exon_tf_sam_flag(uint32_t which, int32_t flag) {
+    return which < (uint32_t)exg::seqfn::kSamFlagCount ? (exon_scan::SamFlag(which, flag) ? 1 : 0) : -1;
+}
 
 extern "C" int exon_tf_schema(exon_tf_handle *h, exg_schema *out) {
     memset(out, 0, sizeof *out);

@@ -149,6 +149,49 @@ def quality_score_string_to_list(strings, n_rows, d_payload, payload_base, value
     return entries[:n_rows], values[:min(t, cap)], t
 
 
+SEQ_OUT_BASE = 1 << 46   # string_t.ptr of sequence_op's out-of-line rows = SEQ_OUT_BASE + offset in out_payload
+
+
+def sequence_op(op, strings, n_rows, d_payload, payload_base, out_capacity=None):
+    """The sequence scalars (reference sequence_functions/module.cpp:30-370; op = abi.EXG_SEQ_*) on a VARCHAR column that
+    is still in HBM: `strings` is a [cap, 2] int64 tensor of string_t (e.g. FastqScan.cols[2]), `d_payload` the buffer its
+    pointers address.  String ops return (out_strings [n_rows, 2] int64, out_payload uint8, result): out-of-line rows
+    point at SEQ_OUT_BASE + offset in out_payload; result.flags & EXG_RF_CAPACITY means out_capacity (default: the bytes of
+    d_payload) was too small and nothing was written.  EXG_SEQ_GC_CONTENT returns (floats [n_rows] float32, result).
+    An invalid row raises ExgError with the reference's text."""
+    torch = _torch()
+    lib = load_library()
+    dev = strings.device
+    gc = op == abi.EXG_SEQ_GC_CONTENT
+    a = abi.SequenceOpArgs()
+    a.op = op
+    a.d_strings = strings.data_ptr()
+    a.n_rows = n_rows
+    a.d_payload = d_payload.data_ptr() if d_payload is not None else None
+    a.payload_base = payload_base
+    if gc:
+        floats = torch.empty(max(n_rows, 1), dtype=torch.float32, device=dev)
+        a.d_out_float = floats.data_ptr()
+    else:
+        cap = int(out_capacity if out_capacity is not None else (d_payload.numel() if d_payload is not None else 0))
+        out_strings = torch.empty((max(n_rows, 1), 2), dtype=torch.int64, device=dev)
+        out_payload = torch.empty(max(cap, 16), dtype=torch.uint8, device=dev)
+        a.d_out_strings, a.d_out_payload = out_strings.data_ptr(), out_payload.data_ptr()
+        a.out_capacity, a.out_base = cap, SEQ_OUT_BASE
+    ws_bytes = int(lib.exg_sequence_workspace_bytes(op, n_rows))
+    ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.int64, device=dev)
+    result = torch.empty(8, dtype=torch.int64, device=dev)
+    a.d_workspace, a.workspace_bytes = ws.data_ptr(), ws_bytes
+    a.d_result = result.data_ptr()
+    a.stream = stream_ptr().value
+    check(lib.exg_sequence_op(C.byref(a)))
+    r = abi.SeqResult()
+    check(lib.exg_sequence_result(C.c_void_p(result.data_ptr()), stream_ptr(), C.byref(r)))
+    if gc:
+        return floats[:n_rows], r
+    return out_strings[:n_rows], out_payload[:min(int(r.total_bytes), cap)], r
+
+
 class VcfScan:
     """Reusable output + workspace buffers for exg_vcf_scan."""
 

@@ -358,3 +358,61 @@ def quality_score_string_to_list(s: bytes):
     out = (C.c_int32 * max(1, len(s)))()
     _lib().exon_tf_quality_scores(s, len(s), out)
     return list(out[:len(s)])
+
+
+def _sequence_fn(op, s):
+    """one row through the host arithmetic of a sequence scalar as the DuckDB shim registers it (reference
+    sequence_functions/module.cpp:30-370): NULL in, NULL out; an invalid row raises ExgError with the reference's text"""
+    if s is None:
+        return None
+    l = _lib()
+    gc = op == abi.EXG_SEQ_GC_CONTENT
+    out = C.create_string_buffer(max(4, len(s)))
+    n_out, err = C.c_uint64(0), C.create_string_buffer(128)
+    rc = l.exon_tf_sequence_fn(op, s, len(s), out, len(out), C.byref(n_out), err, len(err))
+    if rc != 0:
+        raise ExgError(rc, (err.raw[:n_out.value] if rc == abi.EXG_E_PARSE else err.value).decode("latin-1"))
+    return C.c_float.from_buffer(out).value if gc else out.raw[:n_out.value]
+
+
+def complement(s):
+    return _sequence_fn(abi.EXG_SEQ_COMPLEMENT, s)
+
+
+def reverse_complement(s):
+    """what the reference computes (A->C, T->G, C->A, G->T, order kept: test_scalar_functions.test:43-46), not the name"""
+    return _sequence_fn(abi.EXG_SEQ_REVERSE_COMPLEMENT, s)
+
+
+def transcribe(s):
+    return _sequence_fn(abi.EXG_SEQ_TRANSCRIBE, s)
+
+
+def reverse_transcribe(s):
+    return _sequence_fn(abi.EXG_SEQ_REVERSE_TRANSCRIBE, s)
+
+
+def translate_dna_to_aa(s):
+    return _sequence_fn(abi.EXG_SEQ_TRANSLATE, s)
+
+
+def gc_content(s):
+    return _sequence_fn(abi.EXG_SEQ_GC_CONTENT, s)
+
+
+#: the SAM flag predicates in the reference's order (sam_functions/module.cpp:143-154): bit k of (uint16_t)flag
+SAM_FLAG_FUNCTIONS = ("is_segmented", "is_properly_aligned", "is_unmapped", "is_mate_unmapped", "is_reverse_complemented",
+                      "is_mate_reverse_complemented", "is_first_segment", "is_last_segment", "is_secondary",
+                      "is_quality_control_failed", "is_duplicate", "is_supplementary")
+
+
+def _sam_flag_fn(which, name):
+    def fn(flag):
+        return None if flag is None else bool(_lib().exon_tf_sam_flag(which, flag))
+    fn.__name__ = fn.__qualname__ = name
+    fn.__doc__ = f"the SQL scalar {name}(INTEGER) -> BOOLEAN as the shim registers it: bit {which} of (uint16_t)flag"
+    return fn
+
+
+for _k, _name in enumerate(SAM_FLAG_FUNCTIONS):
+    globals()[_name] = _sam_flag_fn(_k, _name)

@@ -43,8 +43,8 @@
 extern "C" {
 #endif
 
-/* 9 still: read_bed_file (EXG_FMT_BED, exg_bed_scan, EXG_PE_BED_*) is a pure addition — no existing struct, constant or
- * entry point changed. */
+/* 9 still: read_bed_file (EXG_FMT_BED, exg_bed_scan, EXG_PE_BED_*) and the sequence scalars (exg_sequence_op,
+ * EXG_SEQ_*, EXG_PE_SEQ_*) are pure additions — no existing struct, constant or entry point changed. */
 #define EXG_ABI_VERSION 9
 
 /* DuckDB v0.8.1 STANDARD_VECTOR_SIZE; the reference asks the Rust side for
@@ -94,6 +94,10 @@ extern "C" {
 #define EXG_PE_BED_STRAND 26          /* BED: strand is not `+`, `-` or `.` */
 #define EXG_PE_BED_COLOR 27           /* BED: color is neither `0` nor r,g,b with three decimals in 0..255 */
 #define EXG_PE_BED_BLOCKS 28          /* BED: block_sizes / block_starts hold fewer than block_count integers */
+/* (29 stays unassigned: it is what callers probe to see "unknown parse error") */
+#define EXG_PE_SEQ_INVALID_CHARACTER 30 /* sequence scalars: a byte outside the function's alphabet */
+#define EXG_PE_SEQ_LENGTH 31          /* translate_dna_to_aa: the length is not a multiple of 3 */
+#define EXG_PE_SEQ_CODON 32           /* translate_dna_to_aa: three bytes that are not a codon over A, C, G, T */
 
 /* ---- duckdb::string_t, bit-for-bit (v0.8.1 duckdb/common/types/string_type.hpp)
  * length <= 12: bytes inlined, zero padded.  Otherwise 4-byte prefix + pointer.
@@ -384,6 +388,63 @@ typedef struct exg_quality_list_args {
 uint64_t exg_quality_list_workspace_bytes(uint64_t n_rows);
 /* Enqueue on args->stream; asynchronous. */
 int exg_quality_score_list(const exg_quality_list_args *args);
+
+/* ---- sequence scalars on device-resident columns --------------------------------------------------------
+ * The scalar functions of exon/src/exon/sequence_functions/module.cpp:30-370 for a VARCHAR column that is still in HBM
+ * (the sequence column a scan just wrote).  The rules are stated once, in exon_duckdb_amd/csrc/exg_seqfn.hpp
+ * ("Sequence and SAM-flag scalars"); reverse_complement is what the reference COMPUTES (A->C, T->G, C->A,
+ * G->T, order kept), not what its name says.
+ *
+ * Input: exg_string_t[n_rows] as the scans leave it (up to 12 bytes inlined, longer strings at payload_base + offset in
+ * d_payload at any alignment, a NULL row = 16 zero bytes); the output column's validity is the input's.  n_rows < 2^32 - 1.
+ * String ops: one string_t per row in d_out_strings — up to 12 bytes inlined and zero padded, longer rows as
+ * {length, 4-byte prefix, out_base + offset} with the out-of-line rows packed into d_out_payload in row order without
+ * gaps: offset(i) = the sum of the output lengths of the rows j < i whose output is longer than 12, total_bytes = that sum
+ * over all rows (a translate_dna_to_aa row counts length / 3, whatever else is wrong with it).  total_bytes > out_capacity:
+ * EXG_RF_CAPACITY, neither output buffer is touched and no row is validated.  GC_CONTENT: one float per row, 0 for a NULL
+ * or empty row, (float)count / (float)length in one IEEE division otherwise.
+ * Errors: the lowest failing row wins, in it the length error of translate_dna_to_aa, else the leftmost bad byte / codon.
+ * With an error the result block is exact and the output buffers are unspecified.  Deterministic: byte-identical outputs for
+ * identical inputs.  No host round trip between the passes. */
+#define EXG_SEQ_COMPLEMENT 1
+#define EXG_SEQ_REVERSE_COMPLEMENT 2
+#define EXG_SEQ_TRANSCRIBE 3
+#define EXG_SEQ_REVERSE_TRANSCRIBE 4
+#define EXG_SEQ_TRANSLATE 5
+#define EXG_SEQ_GC_CONTENT 6
+typedef struct exg_seq_result { /* 64 bytes, written by the device */
+    uint64_t total_bytes;   /* bytes of d_out_payload the rows need (string ops); 0 for GC_CONTENT */
+    uint64_t error_row;     /* lowest failing row */
+    uint64_t error_offset;  /* byte offset in that row of the bad byte / codon (0 for the length error) */
+    uint64_t error_length;  /* that row's length */
+    uint32_t error_code;    /* 0, EXG_PE_SEQ_INVALID_CHARACTER, EXG_PE_SEQ_LENGTH or EXG_PE_SEQ_CODON */
+    uint32_t flags;         /* EXG_RF_CAPACITY: total_bytes > out_capacity, no output was written */
+    uint8_t error_bytes[4]; /* the byte, or the three bytes of the codon */
+    uint8_t pad[20];
+} exg_seq_result;
+typedef struct exg_sequence_op_args {
+    uint32_t op;                   /* EXG_SEQ_* */
+    const exg_string_t *d_strings; /* device, 16-byte aligned, n_rows entries */
+    uint64_t n_rows;
+    const void *d_payload;         /* device bytes the non-inlined strings point into */
+    uint64_t payload_base;         /* string_t.ptr - payload_base = byte offset in d_payload */
+    exg_string_t *d_out_strings;   /* string ops, out: device, 16-byte aligned, n_rows entries */
+    uint8_t *d_out_payload;        /* string ops, out: device, 16-byte aligned, out_capacity bytes */
+    uint64_t out_capacity;
+    uint64_t out_base;             /* out string_t.ptr = out_base + offset in d_out_payload */
+    float *d_out_float;            /* GC_CONTENT, out: device, n_rows entries */
+    void *d_workspace;             /* device, 8-byte aligned, exg_sequence_workspace_bytes(op, n_rows) */
+    uint64_t workspace_bytes;
+    exg_seq_result *d_result;      /* device, 64 bytes, 8-byte aligned */
+    void *stream;
+} exg_sequence_op_args;
+uint64_t exg_sequence_workspace_bytes(uint32_t op, uint64_t n_rows);
+/* Enqueue on args->stream; asynchronous. */
+int exg_sequence_op(const exg_sequence_op_args *args);
+/* Synchronising copy of the 64-byte result to the host.  error_code != 0: EXG_E_PARSE, and the thread's last error message
+ * is the reference's text (`Invalid character in sequence: X`, `Invalid sequence length: N`, `Invalid codon: XYZ`)
+ * followed by ` in row <r>`; *out is filled either way. */
+int exg_sequence_result(const exg_seq_result *d_result, void *stream, exg_seq_result *out);
 
 /* ---- device inflate (gzip / BGZF members; replaces flate2 behind rust/src/arrow_reader.rs:60-91) ---- */
 typedef struct exg_inflate_member {
