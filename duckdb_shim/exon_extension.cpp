@@ -17,9 +17,11 @@
 // types is compiled on the build box.
 #define DUCKDB_EXTENSION_MAIN
 #include "duckdb.hpp"
+#include "duckdb/catalog/catalog.hpp"
 #include "duckdb/common/exception.hpp"
 #include "duckdb/common/types/vector.hpp"
 #include "duckdb/common/types/vector_buffer.hpp"
+#include "duckdb/function/function_set.hpp"
 #include "duckdb/function/scalar_function.hpp"
 #include "duckdb/function/table_function.hpp"
 #include "duckdb/main/extension_util.hpp"
@@ -321,9 +323,73 @@ static void SamFlagFunction(uint32_t which, DataChunk &args, Vector &result) {
 	}
 }
 
-// exon_extension.cpp:62-73: the sequence scalars and the flag predicates (parse_cigar, extract_from_cigar,
-// gff_parse_attributes and the alignment functions are not registered: INTEGRATION.md)
+// alignment_functions/module.cpp:264-329: alignment_score / alignment_score_wfa_gap_affine -> FLOAT in the two-, six- and
+// seven-argument forms (n_args), on the host scalar exon_scan::AlignmentScore over the rules of csrc/exg_alignfn.hpp.  The
+// arguments are taken by position as the signatures name them: (text, pattern[, match], mismatch, gap_opening, gap_extension,
+// memory_model); module.cpp:68-72 reads argument 4 for both gap values, which is not reproduced.  The parameter checks
+// (AlignmentBindError: the reference's texts) run here, on every row's own values, before the row is scored: the reference makes
+// them in a bind callback on constant arguments, which the declaration-only stand-in of ScalarFunction does not carry — so a
+// call over zero rows raises nothing, and the parameters may differ from row to row.  NULL in any argument, NULL out.
+static void AlignmentScoreFunction(idx_t n_args, DataChunk &args, Vector &result) {
+	const idx_t count = args.size();
+	UnifiedVectorFormat in[7];
+	for (idx_t c = 0; c < n_args; c++) {
+		args.data[c].ToUnifiedFormat(count, in[c]);
+	}
+	result.SetVectorType(VectorType::FLAT_VECTOR);
+	auto out = FlatVector::GetData<float>(result);
+	const idx_t first = n_args == 7 ? 3 : 2; // the column of `mismatch`
+	for (idx_t i = 0; i < count; i++) {
+		bool valid = true;
+		idx_t k[7];
+		for (idx_t c = 0; c < n_args; c++) {
+			k[c] = in[c].sel->get_index(i);
+			valid = valid && in[c].validity.RowIsValid(k[c]);
+		}
+		out[i] = 0;
+		if (!valid) {
+			FlatVector::SetNull(result, i, true);
+			continue;
+		}
+		exon_scan::AlignmentParams prm;
+		if (n_args > 2) {
+			auto integer = [&](idx_t c) { return (int64_t) reinterpret_cast<const int32_t *>(in[c].data)[k[c]]; };
+			const string_t &model = reinterpret_cast<const string_t *>(in[n_args - 1].data)[k[n_args - 1]];
+			const std::string msg = exon_scan::AlignmentBindError(n_args == 7, n_args == 7 ? integer(2) : 0, integer(first), integer(first + 1),
+			                                                      integer(first + 2), model.GetData(), model.GetSize());
+			if (!msg.empty()) {
+				throw InvalidInputException(msg);
+			}
+			prm.mismatch = (int32_t)integer(first), prm.gap_opening = (int32_t)integer(first + 1), prm.gap_extension = (int32_t)integer(first + 2);
+		}
+		const string_t &text = reinterpret_cast<const string_t *>(in[0].data)[k[0]];
+		const string_t &pattern = reinterpret_cast<const string_t *>(in[1].data)[k[1]];
+		if (exon_scan::AlignmentScore(text.GetData(), text.GetSize(), pattern.GetData(), pattern.GetSize(), prm, &out[i]) != EXG_OK) {
+			throw InvalidInputException("alignment_score: the pair is longer than 2^21 bytes");
+		}
+	}
+}
+
+// exon_extension.cpp:81-93: both names, each a set of three signatures (module.cpp:308-329).  A set goes into the system
+// catalog the way ExtensionUtil::RegisterFunction puts a single function there.
+static void RegisterAlignmentScore(DatabaseInstance &db, const char *name) {
+	ScalarFunctionSet set(name);
+	const LogicalType V = LogicalType::VARCHAR, I = LogicalType::INTEGER;
+	const vector<LogicalType> forms[] = {{V, V}, {V, V, I, I, I, V}, {V, V, I, I, I, I, V}};
+	for (const auto &arguments : forms) {
+		const idx_t n_args = arguments.size();
+		set.AddFunction(ScalarFunction(name, arguments, LogicalType::FLOAT,
+		                               [n_args](DataChunk &args, ExpressionState &, Vector &result) { AlignmentScoreFunction(n_args, args, result); }));
+	}
+	CreateScalarFunctionInfo info(std::move(set));
+	Catalog::GetSystemCatalog(db).CreateFunction(CatalogTransaction::GetSystemTransaction(db), info);
+}
+
+// exon_extension.cpp:62-73, :81-93: the sequence scalars, the flag predicates and the alignment scores (parse_cigar,
+// extract_from_cigar, gff_parse_attributes and alignment_string* are not registered: INTEGRATION.md)
 static void RegisterScalars(DatabaseInstance &db) {
+	RegisterAlignmentScore(db, "alignment_score");
+	RegisterAlignmentScore(db, "alignment_score_wfa_gap_affine");
 	static const struct {
 		const char *name;
 		uint32_t op;

@@ -42,6 +42,7 @@ EXG_PE_BED_BLOCKS = 28
 EXG_PE_SEQ_INVALID_CHARACTER = 30   # (29 is unassigned)
 EXG_PE_SEQ_LENGTH = 31
 EXG_PE_SEQ_CODON = 32
+EXG_PE_ALIGN_TOO_LONG = 33
 
 EXG_FMT_FASTA, EXG_FMT_FASTQ, EXG_FMT_VCF, EXG_FMT_BAM, EXG_FMT_BED = 1, 2, 3, 4, 5
 EXG_BAM_COLUMNS = 10
@@ -242,6 +243,44 @@ class SequenceOpArgs(C.Structure):
     ]
 
 
+class AlignScoreResult(C.Structure):
+    _fields_ = [
+        ("n_capped", C.c_uint64),
+        ("error_row", C.c_uint64),
+        ("error_length", C.c_uint64),
+        ("error_limit", C.c_uint64),
+        ("n_global", C.c_uint64),
+        ("error_code", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("pad", C.c_uint8 * 16),
+    ]
+
+
+class AlignScoreArgs(C.Structure):
+    _fields_ = [
+        ("d_text", C.c_void_p),
+        ("d_text_payload", C.c_void_p),
+        ("text_payload_base", C.c_uint64),
+        ("d_pattern", C.c_void_p),
+        ("d_pattern_payload", C.c_void_p),
+        ("pattern_payload_base", C.c_uint64),
+        ("n_rows", C.c_uint64),
+        ("mismatch", C.c_uint32),
+        ("gap_opening", C.c_uint32),
+        ("gap_extension", C.c_uint32),
+        ("max_penalty", C.c_uint32),
+        ("max_pair_bytes", C.c_uint64),
+        ("d_out_float", C.c_void_p),
+        ("d_out_valid", C.c_void_p),
+        ("d_workspace", C.c_void_p),
+        ("workspace_bytes", C.c_uint64),
+        ("d_result", C.c_void_p),
+        ("stream", C.c_void_p),
+        ("lanes", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
 class OpenArgs(C.Structure):
     _fields_ = [("path", C.c_char_p), ("file_format", C.c_char_p), ("compression", C.c_char_p), ("batch_rows", C.c_uint64),
                 ("device", C.c_int), ("device_batch_bytes", C.c_uint64), ("filters", C.c_char_p),
@@ -281,6 +320,9 @@ SIGNATURES = {
     "exg_sequence_workspace_bytes": (C.c_uint64, [C.c_uint32, C.c_uint64]),
     "exg_sequence_op": (C.c_int, [C.POINTER(SequenceOpArgs)]),
     "exg_sequence_result": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(SeqResult)]),
+    "exg_align_workspace_bytes": (C.c_uint64, [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32]),
+    "exg_align_score": (C.c_int, [C.POINTER(AlignScoreArgs)]),
+    "exg_align_result": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(AlignScoreResult)]),
     "exg_plan_shards": (C.c_int, [C.POINTER(OpenArgs), C.POINTER(C.c_uint32), C.POINTER(C.c_int), C.c_uint32]),
 }
 
@@ -318,6 +360,9 @@ TEST_SIGNATURES = {
     "exon_tf_vcf_header_explain": (C.c_int, [C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t]),
     "exon_tf_sequence_fn": (C.c_int, [C.c_uint32, C.c_char_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p, C.c_uint64]),
     "exon_tf_sam_flag": (C.c_int, [C.c_uint32, C.c_int32]),
+    "exon_tf_alignment_score_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "exon_tf_alignment_score": (C.c_int, [C.c_int, C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                                          C.c_char_p, C.c_uint64, C.POINTER(C.c_float), C.c_char_p, C.c_uint64]),
     "exon_tf_link_probe": (C.c_int, [C.c_int, C.c_uint64, C.c_int, C.POINTER(C.c_double)]),
     "exon_tf_host_pipeline_probe": (C.c_double, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double]),
     "exon_tf_host_zero_bounce_probe": (C.c_double, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(C.c_double)]),

@@ -82,6 +82,7 @@ extern "C" const char *exg_parse_error_string(uint32_t code) {
         case EXG_PE_SEQ_INVALID_CHARACTER: return "invalid character in sequence";
         case EXG_PE_SEQ_LENGTH: return "invalid sequence length";
         case EXG_PE_SEQ_CODON: return "invalid codon";
+        case EXG_PE_ALIGN_TOO_LONG: return "alignment pair too long";
         default: return "unknown parse error";
     }
 }

@@ -46,6 +46,7 @@
 #include <vector>
 
 #include "exon_gpu.h"
+#include "exg_alignfn.hpp"
 #include "exg_seqfn.hpp"
 
 namespace exon_scan {
@@ -368,6 +369,81 @@ static inline std::string SequenceErrorText(const SequenceStatus &st) {
 }
 // is_segmented .. is_supplementary: `which` indexes exg::seqfn::kSamFlagNames
 static inline bool SamFlag(uint32_t which, int32_t flag) { return exg::seqfn::sam_flag(which, flag); }
+
+// alignment_score / alignment_score_wfa_gap_affine (exon/src/exon/alignment_functions/module.cpp:264-329): the score of the
+// optimal global gap-affine alignment, on the rules and the recurrences of exg_alignfn.hpp (exg_align_score is the same on two
+// scan columns that are still in HBM).  The exact wavefront algorithm with whole wavefronts of the last max(x, o + e) + 1
+// scores: O((n + m) * depth) memory, O(penalty * width) time.
+struct AlignmentParams {
+    int32_t mismatch = exg::alignfn::kDefaultMismatch;
+    int32_t gap_opening = exg::alignfn::kDefaultGapOpening;
+    int32_t gap_extension = exg::alignfn::kDefaultGapExtension;
+};
+// The bind-time checks of the SQL forms, by position as the signatures name them (module.cpp:68-72 reads argument 4 for both
+// gap values; that slip is not reproduced).  has_match: the seven-argument form.  "" or the exception's text.
+static inline std::string AlignmentBindError(bool has_match, int64_t match, int64_t mismatch, int64_t gap_opening, int64_t gap_extension,
+                                             const char *memory_model, size_t memory_model_len) {
+    namespace af = exg::alignfn;
+    if (has_match && match > 0) return af::kMatchPositiveText;
+    if (has_match && match < 0) return af::kMatchNegativeText;
+    if (!af::params_ok(mismatch, gap_opening, gap_extension)) return af::kParamRangeText;
+    if (!af::memory_model_ok(memory_model, memory_model_len)) return std::string(af::kMemoryModelPrefix) + std::string(memory_model, memory_model_len);
+    return std::string();
+}
+// EXG_OK and *score; EXG_E_INVALID_ARG for parameters outside their limits, EXG_E_CAPACITY for a pair longer than
+// exg::alignfn::kMaxPairBytes (2^21)
+static inline int AlignmentScore(const char *text, size_t n_, const char *pattern, size_t m_, const AlignmentParams &prm, float *score) {
+    namespace af = exg::alignfn;
+    if (!af::params_ok(prm.mismatch, prm.gap_opening, prm.gap_extension)) return EXG_E_INVALID_ARG;
+    if ((uint64_t)n_ + (uint64_t)m_ > af::kMaxPairBytes) return EXG_E_CAPACITY;
+    const int32_t n = (int32_t)n_, m = (int32_t)m_;
+    const int32_t x = prm.mismatch, o = prm.gap_opening, e = prm.gap_extension;
+    const int32_t rm = (int32_t)af::m_ring_depth(x, o, e), rg = (int32_t)af::gap_ring_depth(e);
+    const int32_t nd = n + m + 1;  // diagonal k = h - v lives at index d = k + m
+    const int32_t bound = (int32_t)af::penalty_bound(o, e, n, m);
+    std::vector<int32_t> M((size_t)rm * nd, af::kNone), I((size_t)rg * nd, af::kNone), D((size_t)rg * nd, af::kNone);
+    auto extend = [&](int32_t h, int32_t k) {
+        int32_t v = h - k;
+        while (h < n && v < m) {
+            if (n - h >= 8 && m - v >= 8) {
+                uint64_t a, b;
+                memcpy(&a, text + h, 8), memcpy(&b, pattern + v, 8);
+                const int32_t c = (int32_t)af::equal_prefix8(a, b);
+                h += c, v += c;
+                if (c < 8) break;
+            } else {
+                if (text[h] != pattern[v]) break;
+                h++, v++;
+            }
+        }
+        return h;
+    };
+    int32_t lo = m, hi = m;  // the diagonals any wavefront has reached so far
+    for (int32_t s = 0; s <= bound; s++) {
+        const int32_t from = s ? (lo > 0 ? lo - 1 : 0) : m, to = s ? (hi < nd - 1 ? hi + 1 : nd - 1) : m;
+        const int32_t *m_sub = s >= x ? &M[(size_t)((s - x) % rm) * nd] : nullptr;
+        const int32_t *m_open = s >= o + e ? &M[(size_t)((s - o - e) % rm) * nd] : nullptr;
+        const int32_t *i_prev = s >= e ? &I[(size_t)((s - e) % rg) * nd] : nullptr, *d_prev = s >= e ? &D[(size_t)((s - e) % rg) * nd] : nullptr;
+        int32_t *m_now = &M[(size_t)(s % rm) * nd], *i_now = &I[(size_t)(s % rg) * nd], *d_now = &D[(size_t)(s % rg) * nd];
+        for (int32_t d = from; d <= to; d++) {
+            const int32_t k = d - m;
+            af::Cell c = af::cell(m_open && d > 0 ? m_open[d - 1] : af::kNone, i_prev && d > 0 ? i_prev[d - 1] : af::kNone,
+                                  m_open && d < nd - 1 ? m_open[d + 1] : af::kNone, d_prev && d < nd - 1 ? d_prev[d + 1] : af::kNone,
+                                  m_sub ? m_sub[d] : af::kNone, k, n, m);
+            if (!s) c.m = 0;
+            if (c.m >= 0) {
+                c.m = extend(c.m, k);
+                lo = d < lo ? d : lo, hi = d > hi ? d : hi;
+            }
+            i_now[d] = c.i, d_now[d] = c.d, m_now[d] = c.m;
+        }
+        if (m_now[n] >= n) {
+            *score = af::score_of((uint32_t)s);
+            return EXG_OK;
+        }
+    }
+    return EXG_E_INVALID_ARG;  // (unreachable: the bound is an alignment's penalty)
+}
 
 // exon/src/exon_extension.cpp:47-58: the registrations of the path (+ the read_vcf alias the north star names)
 struct Registration {

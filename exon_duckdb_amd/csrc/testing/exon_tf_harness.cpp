@@ -238,6 +238,43 @@ extern "C" int exon_tf_sequence_fn(uint32_t op, const char *s, uint64_t n, char 
     }
     return EXG_E_PARSE;
 }
+// alignment_score / alignment_score_wfa_gap_affine as the shim registers them (alignment_functions/module.cpp:264-329).
+// n_args = 2, 6 or 7: the SQL form, whose bind-time checks run first (match is read by the seven-argument form only,
+// memory_model by the six- and seven-argument forms).  0 and *score; EXG_E_INVALID_ARG with the exception's text in err
+extern "C" int exon_tf_alignment_score(int n_args, const char *text, uint64_t n, const char *pattern, uint64_t m, int64_t match,
+                                       int64_t mismatch, int64_t gap_opening, int64_t gap_extension, const char *memory_model,
+                                       uint64_t memory_model_len, float *score, char *err, uint64_t err_cap) {
+    if (err_cap) err[0] = 0;
+    auto fail = [&](const std::string &msg) {
+        if (err_cap) snprintf(err, (size_t)err_cap, "%s", msg.c_str());
+        return EXG_E_INVALID_ARG;
+    };
+    exon_scan::AlignmentParams prm;
+    if (n_args == 6 || n_args == 7) {
+        const std::string msg = exon_scan::AlignmentBindError(n_args == 7, match, mismatch, gap_opening, gap_extension, memory_model,
+                                                              (size_t)memory_model_len);
+        if (!msg.empty()) return fail(msg);
+        prm.mismatch = (int32_t)mismatch, prm.gap_opening = (int32_t)gap_opening, prm.gap_extension = (int32_t)gap_extension;
+    } else if (n_args != 2) {
+        return fail("Invalid number of arguments for align function");
+    }
+    const int rc = exon_scan::AlignmentScore(text, (size_t)n, pattern, (size_t)m, prm, score);
+    if (rc == EXG_E_CAPACITY) return fail("alignment_score: the pair is longer than 2^21 bytes");
+    return rc;
+}
+// the same host scalar over n pairs in one call (tools/align_bench.py times it: one core, no per-row call overhead): pair i is
+// texts[t_off[i] .. t_off[i + 1]) against patterns[p_off[i] .. p_off[i + 1])
+extern "C" int exon_tf_alignment_score_batch(const char *texts, const uint64_t *t_off, const char *patterns, const uint64_t *p_off, uint64_t n,
+                                             int32_t mismatch, int32_t gap_opening, int32_t gap_extension, float *scores) {
+    exon_scan::AlignmentParams prm;
+    prm.mismatch = mismatch, prm.gap_opening = gap_opening, prm.gap_extension = gap_extension;
+    for (uint64_t i = 0; i < n; i++) {
+        const int rc = exon_scan::AlignmentScore(texts + t_off[i], (size_t)(t_off[i + 1] - t_off[i]), patterns + p_off[i],
+                                                 (size_t)(p_off[i + 1] - p_off[i]), prm, &scores[i]);
+        if (rc != EXG_OK) return rc;
+    }
+    return EXG_OK;
+}
 // is_segmented .. is_supplementary (which = 0 .. 11) of an INTEGER flag; -1 for an unknown predicate
 extern "C" int exon_tf_sam_flag(uint32_t which, int32_t flag) {
     return which < (uint32_t)exg::seqfn::kSamFlagCount ? (exon_scan::SamFlag(which, flag) ? 1 : 0) : -1;

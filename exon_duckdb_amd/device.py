@@ -192,6 +192,40 @@ def sequence_op(op, strings, n_rows, d_payload, payload_base, out_capacity=None)
     return out_strings[:n_rows], out_payload[:min(int(r.total_bytes), cap)], r
 
 
+def align_score(text, text_payload, text_payload_base, pattern, pattern_payload, pattern_payload_base, n_rows, max_pair_bytes,
+                mismatch=4, gap_opening=6, gap_extension=2, max_penalty=0, valid=None, lanes=0):
+    """alignment_score / alignment_score_wfa_gap_affine (reference alignment_functions/module.cpp:264-329) on two VARCHAR
+    columns that are still in HBM: `text` and `pattern` are [cap, 2] int64 tensors of string_t (e.g. FastqScan.cols[2] of two
+    scans), each with the buffer its pointers address.  Returns (scores [n_rows] float32, result): the exact optimum of the
+    global gap-affine alignment as (float)(-penalty).  A row whose optimum exceeds a non-zero max_penalty gets -inf, its bit is
+    cleared in `valid` (an int64 tensor of validity words, when given) and result.n_capped counts it.  A row with
+    |text| + |pattern| > max_pair_bytes raises ExgError naming the lowest such row."""
+    torch = _torch()
+    lib = load_library()
+    dev = text.device
+    a = abi.AlignScoreArgs()
+    a.d_text, a.d_pattern = text.data_ptr(), pattern.data_ptr()
+    a.d_text_payload = text_payload.data_ptr() if text_payload is not None else None
+    a.d_pattern_payload = pattern_payload.data_ptr() if pattern_payload is not None else None
+    a.text_payload_base, a.pattern_payload_base = text_payload_base, pattern_payload_base
+    a.n_rows = n_rows
+    a.mismatch, a.gap_opening, a.gap_extension = mismatch, gap_opening, gap_extension
+    a.max_penalty, a.max_pair_bytes, a.lanes = max_penalty, max_pair_bytes, lanes
+    scores = torch.empty(max(n_rows, 1), dtype=torch.float32, device=dev)
+    a.d_out_float = scores.data_ptr()
+    a.d_out_valid = valid.data_ptr() if valid is not None else None
+    ws_bytes = int(lib.exg_align_workspace_bytes(n_rows, max_pair_bytes, mismatch, gap_opening, gap_extension))
+    ws = torch.empty(max(ws_bytes, 64) // 8 + 2, dtype=torch.int64, device=dev)
+    result = torch.empty(8, dtype=torch.int64, device=dev)
+    a.d_workspace, a.workspace_bytes = ws.data_ptr(), ws_bytes
+    a.d_result = result.data_ptr()
+    a.stream = stream_ptr().value
+    check(lib.exg_align_score(C.byref(a)))
+    r = abi.AlignScoreResult()
+    check(lib.exg_align_result(C.c_void_p(result.data_ptr()), stream_ptr(), C.byref(r)))
+    return scores[:n_rows], r
+
+
 class VcfScan:
     """Reusable output + workspace buffers for exg_vcf_scan."""
 

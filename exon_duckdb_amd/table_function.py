@@ -360,6 +360,31 @@ def quality_score_string_to_list(s: bytes):
     return list(out[:len(s)])
 
 
+def alignment_score(text, pattern, *args):
+    """the SQL scalar alignment_score as the DuckDB shim registers it (reference alignment_functions/module.cpp:264-329), in
+    its three forms: (text, pattern), (text, pattern, mismatch, gap_opening, gap_extension, memory_model) and
+    (text, pattern, match, mismatch, gap_opening, gap_extension, memory_model).  The exact optimum of the global gap-affine
+    alignment as a float32: -penalty.  NULL in, NULL out; a bind-time error raises ExgError with the exception's text."""
+    if len(args) not in (0, 4, 5):
+        raise ExgError(abi.EXG_E_INVALID_ARG, "Invalid number of arguments for align function")
+    match, (x, o, e), model = 0, (0, 0, 0), b""
+    if args:
+        match = args[0] if len(args) == 5 else 0
+        x, o, e = args[-4:-1]
+        model = args[-1].encode() if isinstance(args[-1], str) else bytes(args[-1])
+    score, err = C.c_float(0), C.create_string_buffer(256)
+    null = text is None or pattern is None
+    t, p = (b"", b"") if null else (text, pattern)
+    rc = _lib().exon_tf_alignment_score(2 + len(args), t, len(t), p, len(p), match, x, o, e, model, len(model), C.byref(score), err, len(err))
+    if rc != 0:
+        raise ExgError(rc, err.value.decode("latin-1"))
+    return None if null else score.value
+
+
+#: the reference registers the same function under a second name (exon_extension.cpp:81-93)
+alignment_score_wfa_gap_affine = alignment_score
+
+
 def _sequence_fn(op, s):
     """one row through the host arithmetic of a sequence scalar as the DuckDB shim registers it (reference
     sequence_functions/module.cpp:30-370): NULL in, NULL out; an invalid row raises ExgError with the reference's text"""

@@ -43,8 +43,9 @@
 extern "C" {
 #endif
 
-/* 9 still: read_bed_file (EXG_FMT_BED, exg_bed_scan, EXG_PE_BED_*) and the sequence scalars (exg_sequence_op,
- * EXG_SEQ_*, EXG_PE_SEQ_*) are pure additions — no existing struct, constant or entry point changed. */
+/* 9 still: read_bed_file (EXG_FMT_BED, exg_bed_scan, EXG_PE_BED_*), the sequence scalars (exg_sequence_op,
+ * EXG_SEQ_*, EXG_PE_SEQ_*) and the alignment scores (exg_align_score, EXG_PE_ALIGN_TOO_LONG) are pure additions — no
+ * existing struct, constant or entry point changed. */
 #define EXG_ABI_VERSION 9
 
 /* DuckDB v0.8.1 STANDARD_VECTOR_SIZE; the reference asks the Rust side for
@@ -98,6 +99,7 @@ extern "C" {
 #define EXG_PE_SEQ_INVALID_CHARACTER 30 /* sequence scalars: a byte outside the function's alphabet */
 #define EXG_PE_SEQ_LENGTH 31          /* translate_dna_to_aa: the length is not a multiple of 3 */
 #define EXG_PE_SEQ_CODON 32           /* translate_dna_to_aa: three bytes that are not a codon over A, C, G, T */
+#define EXG_PE_ALIGN_TOO_LONG 33      /* exg_align_score: |text| + |pattern| of a row exceeds max_pair_bytes */
 
 /* ---- duckdb::string_t, bit-for-bit (v0.8.1 duckdb/common/types/string_type.hpp)
  * length <= 12: bytes inlined, zero padded.  Otherwise 4-byte prefix + pointer.
@@ -445,6 +447,58 @@ int exg_sequence_op(const exg_sequence_op_args *args);
  * is the reference's text (`Invalid character in sequence: X`, `Invalid sequence length: N`, `Invalid codon: XYZ`)
  * followed by ` in row <r>`; *out is filled either way. */
 int exg_sequence_result(const exg_seq_result *d_result, void *stream, exg_seq_result *out);
+
+/* ---- gap-affine alignment scores on device-resident columns ---------------------------------------------
+ * alignment_score / alignment_score_wfa_gap_affine of exon/src/exon/alignment_functions/module.cpp:264-329 for two VARCHAR
+ * columns that are still in HBM.  The rules are stated once, in exon_duckdb_amd/csrc/exg_alignfn.hpp (INTEGRATION.md,
+ * "Alignment scores"): score = (float)(-(int32_t)penalty), penalty = the exact optimum over global alignments of 0 per equal
+ * byte pair, mismatch per unequal pair, gap_opening + L * gap_extension per gap of L bytes (match = 0).  No heuristic.
+ *
+ * Input: two exg_string_t[n_rows] columns as the scans leave them, each with its own payload; a NULL row (16 zero bytes) is
+ * an empty string.  n_rows < 2^32 - 1.  1 <= mismatch <= 1023, 0 <= gap_opening <= 1023, 1 <= gap_extension <= 1023,
+ * max_pair_bytes <= 2^21: anything else is EXG_E_INVALID_ARG.
+ * A row with |text| + |pattern| > max_pair_bytes is an error (EXG_PE_ALIGN_TOO_LONG): the lowest such row wins, the result
+ * block is exact and the outputs are unspecified.  A row whose optimum exceeds a non-zero max_penalty gets -INFINITY, its
+ * bit is cleared in d_out_valid (when given; the op clears bits only — the column's validity, the AND of the inputs', is
+ * the caller's to put there) and it is counted in n_capped: the safety valve for dissimilar long pairs.
+ * Deterministic; no host round trip between the passes; n_rows = 0 is valid. */
+typedef struct exg_align_score_result { /* 64 bytes, written by the device */
+    uint64_t n_capped;      /* rows whose optimum exceeds max_penalty */
+    uint64_t error_row;     /* lowest row that is too long */
+    uint64_t error_length;  /* its |text| + |pattern| */
+    uint64_t error_limit;   /* max_pair_bytes of the call */
+    uint64_t n_global;      /* rows whose wavefronts did not fit LDS and ran out of the workspace */
+    uint32_t error_code;    /* 0 or EXG_PE_ALIGN_TOO_LONG */
+    uint32_t flags;         /* 0 (bit 0: a score loop ran into its hard bound — a defect, never expected) */
+    uint8_t pad[16];
+} exg_align_score_result;
+typedef struct exg_align_score_args {
+    const exg_string_t *d_text;    /* device, 16-byte aligned, n_rows entries */
+    const void *d_text_payload;    /* device bytes the non-inlined texts point into */
+    uint64_t text_payload_base;    /* string_t.ptr - text_payload_base = byte offset in d_text_payload */
+    const exg_string_t *d_pattern; /* likewise */
+    const void *d_pattern_payload;
+    uint64_t pattern_payload_base;
+    uint64_t n_rows;
+    uint32_t mismatch, gap_opening, gap_extension;
+    uint32_t max_penalty;          /* 0 = none */
+    uint64_t max_pair_bytes;       /* the longest |text| + |pattern| the workspace is sized for */
+    float *d_out_float;            /* out: device, n_rows entries */
+    uint64_t *d_out_valid;         /* optional: device validity words, bit (row & 63) of word row >> 6; may be NULL */
+    void *d_workspace;             /* device, 16-byte aligned, exg_align_workspace_bytes(...) */
+    uint64_t workspace_bytes;
+    exg_align_score_result *d_result;    /* device, 64 bytes, 8-byte aligned */
+    void *stream;
+    uint32_t lanes;                /* lanes of a wave a pair gets while its wavefronts fit LDS: 0 = default, 16, 32 or 64 */
+    uint32_t reserved;             /* 0 */
+} exg_align_score_args;
+uint64_t exg_align_workspace_bytes(uint64_t n_rows, uint64_t max_pair_bytes, uint32_t mismatch, uint32_t gap_opening,
+                                   uint32_t gap_extension);
+/* Enqueue on args->stream; asynchronous. */
+int exg_align_score(const exg_align_score_args *args);
+/* Synchronising copy of the 64-byte result to the host.  error_code != 0: EXG_E_PARSE, and the thread's last error message is
+ * `Alignment pair too long: <n> bytes (at most <max_pair_bytes>) in row <r>`; *out is filled either way. */
+int exg_align_result(const exg_align_score_result *d_result, void *stream, exg_align_score_result *out);
 
 /* ---- device inflate (gzip / BGZF members; replaces flate2 behind rust/src/arrow_reader.rs:60-91) ---- */
 typedef struct exg_inflate_member {
