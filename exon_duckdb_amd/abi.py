@@ -43,10 +43,19 @@ EXG_PE_SEQ_INVALID_CHARACTER = 30   # (29 is unassigned)
 EXG_PE_SEQ_LENGTH = 31
 EXG_PE_SEQ_CODON = 32
 EXG_PE_ALIGN_TOO_LONG = 33
+EXG_PE_SAM_FIELD_COUNT = 35   # (34 is unassigned)
+EXG_PE_SAM_EMPTY_FIELD = 36
+EXG_PE_SAM_HEADER_LINE = 37
+EXG_PE_SAM_FLAG = 38
+EXG_PE_SAM_POSITION = 39
+EXG_PE_SAM_MAPQ = 40
+EXG_PE_SAM_CIGAR = 41
+EXG_PE_SAM_LENGTHS = 42
 
-EXG_FMT_FASTA, EXG_FMT_FASTQ, EXG_FMT_VCF, EXG_FMT_BAM, EXG_FMT_BED = 1, 2, 3, 4, 5
+EXG_FMT_FASTA, EXG_FMT_FASTQ, EXG_FMT_VCF, EXG_FMT_BAM, EXG_FMT_BED, EXG_FMT_SAM = 1, 2, 3, 4, 5, 6
 EXG_BAM_COLUMNS = 10
 EXG_BED_COLUMNS = 12
+EXG_SAM_COLUMNS = 10
 EXG_F_BOF, EXG_F_EOF, EXG_F_NO_STORE = 1, 2, 4
 EXG_RF_NON_ASCII, EXG_RF_HEAD_UNRESOLVED, EXG_RF_FALLBACK, EXG_RF_CAPACITY, EXG_RF_INDEX_OVERFLOW = 1, 2, 4, 8, 16
 EXG_RF_QUAL_RANGE = 32
@@ -195,6 +204,24 @@ class BedScanArgs(C.Structure):
     ]
 
 
+class SamScanArgs(C.Structure):
+    _fields_ = [
+        ("d_input", C.c_void_p),
+        ("n_bytes", C.c_uint64),
+        ("lead", C.c_uint64),
+        ("payload_base", C.c_uint64),
+        ("flags", C.c_uint32),
+        ("algo", C.c_uint32),
+        ("d_columns", C.c_void_p * 10),
+        ("d_validity", C.c_void_p * 10),
+        ("capacity_records", C.c_uint64),
+        ("d_workspace", C.c_void_p),
+        ("workspace_bytes", C.c_uint64),
+        ("d_result", C.c_void_p),
+        ("stream", C.c_void_p),
+    ]
+
+
 class QualityListArgs(C.Structure):
     _fields_ = [
         ("d_strings", C.c_void_p),
@@ -308,6 +335,7 @@ SIGNATURES = {
     "exg_fasta_scan": (C.c_int, [C.POINTER(FastaScanArgs)]),
     "exg_bam_scan": (C.c_int, [C.POINTER(BamScanArgs)]),
     "exg_bed_scan": (C.c_int, [C.POINTER(BedScanArgs)]),
+    "exg_sam_scan": (C.c_int, [C.POINTER(SamScanArgs)]),
     "exg_gzip_index": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),
                                  C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
     "exg_inflate_members": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),

@@ -83,6 +83,14 @@ extern "C" const char *exg_parse_error_string(uint32_t code) {
         case EXG_PE_SEQ_LENGTH: return "invalid sequence length";
         case EXG_PE_SEQ_CODON: return "invalid codon";
         case EXG_PE_ALIGN_TOO_LONG: return "alignment pair too long";
+        case EXG_PE_SAM_FIELD_COUNT: return "fewer than 11 SAM fields";
+        case EXG_PE_SAM_EMPTY_FIELD: return "empty SAM field";
+        case EXG_PE_SAM_HEADER_LINE: return "header line behind the SAM header";
+        case EXG_PE_SAM_FLAG: return "invalid SAM flag";
+        case EXG_PE_SAM_POSITION: return "invalid SAM position";
+        case EXG_PE_SAM_MAPQ: return "invalid SAM mapping quality";
+        case EXG_PE_SAM_CIGAR: return "invalid SAM CIGAR";
+        case EXG_PE_SAM_LENGTHS: return "sequence and quality scores differ in length";
         default: return "unknown parse error";
     }
 }
@@ -96,6 +104,15 @@ extern "C" uint64_t exg_scan_workspace_bytes(int format, uint64_t n_bytes) {
         const FastqWsLayout l = fastq_ws_layout(n_bytes, 0);
         const uint64_t small = n_bytes < (1ull << 20) ? n_bytes : (1ull << 20);
         const uint64_t lines = (n_bytes / 16 > small ? n_bytes / 16 : small) + 8;
+        return l.off_nl_pos + (lines + 2) * 8;
+    }
+    if (format == EXG_FMT_SAM) {
+        // as for BED: the per-tile arrays, and a line index for one line per 22 bytes — the densest valid line is eleven
+        // one-byte fields, 21 bytes ("q\t0\t*\t0\t0\t*\t*\t0\t0\t*\t*"), + LF —, never less than min(n, 1 Mi) lines.  A denser
+        // input holds a line that is in error; when the index overflows in front of it, EXG_RF_INDEX_OVERFLOW says so
+        const FastqWsLayout l = fastq_ws_layout(n_bytes, 0);
+        const uint64_t small = n_bytes < (1ull << 20) ? n_bytes : (1ull << 20);
+        const uint64_t lines = (n_bytes / 22 > small ? n_bytes / 22 : small) + 8;
         return l.off_nl_pos + (lines + 2) * 8;
     }
     return fastq_ws_layout(n_bytes, 0, exg_rd::format_desc(format).line_index_arrays).total_bytes;  // (FASTA keeps four arrays)

@@ -25,6 +25,7 @@
 #include "exg_rd_bam.hpp"
 #include "exg_rd_source.hpp"
 #include "exg_rd_stages.hpp"
+#include "exg_sam_header.hpp"
 
 namespace exg_rd {
 
@@ -53,9 +54,13 @@ const Switches &switches() {
 // room every segment leaves in front of its bytes for the tail the scan carries over (a longer tail moves into a block of its own)
 static uint64_t source_reserve(const exg_reader *r) { return std::min<uint64_t>(std::max<uint64_t>(r->device_batch_bytes / 8, 64u << 10), 8u << 20); }
 
-// The leading '#' lines of a decoded VCF come back to the host for the header parse (blk->p holds a prefix of the decoded
-// stream; the DataChunk payload travels per batch): `src` is read from its first byte until a line that does not start with
-// '#' begins inside the prefix, or the stream ends.
+// the formats whose text begins with a header, and the byte its lines begin with (VCF: parsed; SAM: only skipped)
+static bool has_text_header(const exg_reader *r) { return r->format == EXG_FMT_VCF || r->format == EXG_FMT_SAM; }
+static char header_marker(const exg_reader *r) { return r->format == EXG_FMT_SAM ? '@' : '#'; }
+
+// The leading '#' lines of a decoded VCF ('@' lines of a SAM) come back to the host for the header parse (blk->p holds a prefix
+// of the decoded stream; the DataChunk payload travels per batch): `src` is read from its first byte until a line that does
+// not start with the marker begins inside the prefix, or the stream ends.
 static int source_header_prefix(exg_reader *r, DecodedSource *src, PinnedBlock &b) {
     // (not more than a device batch at first: what is acquired here is the first batch's size, which sizes the scan's buffers)
     for (uint64_t want = std::min<uint64_t>(4u << 20, r->device_batch_bytes);; want *= 8) {
@@ -74,12 +79,7 @@ static int source_header_prefix(exg_reader *r, DecodedSource *src, PinnedBlock &
         b.pooled = true;
         if (len) RD_HIP(r, hipMemcpyAsync(b.p, d_at, len, hipMemcpyDeviceToHost, r->stream));
         RD_HIP(r, hipStreamSynchronize(r->stream));
-        const char *d = (const char *)b.p;
-        size_t pos = 0;
-        while (pos < len && d[pos] == '#') {
-            const void *nl = memchr(d + pos, '\n', len - pos);
-            pos = nl ? (size_t)((const char *)nl - d) + 1 : len;
-        }
+        const size_t pos = leading_lines_end((const char *)b.p, len, header_marker(r));
         if (pos < len || (eof && len == avail)) {
             r->gz_header_prefix = len;
             return EXG_OK;
@@ -228,17 +228,11 @@ static int open_source(exg_reader *r, std::shared_ptr<PinnedBlock> &blk, const s
         // VCF: every rank needs the header (schema, and where the data begins): read from the start of the file by a
         // source of its own, kept on the host like in the unsharded case
         uint64_t header_bytes = 0;
-        if (r->format == EXG_FMT_VCF) {
+        if (has_text_header(r)) {
             std::unique_ptr<DecodedSource> head = make(0, n, r->compression == kGzip, nullptr);
             int rc = source_header_prefix(r, head.get(), *out_blk);
             if (rc) return rc;
-            const char *d = (const char *)out_blk->p;
-            size_t pos = 0;
-            while (pos < r->gz_header_prefix && d[pos] == '#') {
-                const void *nl = memchr(d + pos, '\n', (size_t)r->gz_header_prefix - pos);
-                pos = nl ? (size_t)((const char *)nl - d) + 1 : (size_t)r->gz_header_prefix;
-            }
-            header_bytes = pos;
+            header_bytes = leading_lines_end((const char *)out_blk->p, (size_t)r->gz_header_prefix, header_marker(r));
         }
         const bool fasta = r->format == EXG_FMT_FASTA;
         uint64_t c_begin = 0, c_end = n, marks[2] = {~0ull, ~0ull};
@@ -317,7 +311,7 @@ static int open_source(exg_reader *r, std::shared_ptr<PinnedBlock> &blk, const s
         }
     } else {
         r->src = make(0, n, false, nullptr);
-        if (r->format == EXG_FMT_VCF) {
+        if (has_text_header(r)) {
             int rc = source_header_prefix(r, r->src.get(), *out_blk);
             if (rc) return rc;
         }
@@ -503,6 +497,10 @@ int open_next_file(exg_reader *r) {
         if (!chrom) return fail(r, EXG_E_PARSE, std::string(exg_parse_error_string(EXG_PE_VCF_NO_HEADER)) + " in '" + p + "'");
         r->vcf_header_bytes = pos;
         r->file_pos = pos;
+    } else if (r->format == EXG_FMT_SAM) {
+        // header = the leading '@' lines, skipped unread (a header-only or empty file has no rows); a decoded stream has the
+        // prefix that holds them on the host, however long they are (source_header_prefix)
+        r->file_pos = sam_header_end((const char *)blk->p, r->compression != kNone ? (size_t)r->gz_header_prefix : blk->n);
     }
     // byte-range shard of this file: [lo, hi) of the bytes behind the header; records / lines belong to the shard they END in
     r->range_hi = r->src ? ~0ull : blk->n;  // (a decoded stream ends where its source says so)
@@ -1001,6 +999,19 @@ struct BatchRun {
         }
         return scan_rc(exg_bed_scan(&a));
     }
+    int launch_sam(uint32_t algo) {
+        exg_sam_scan_args a;
+        fill_common(&a);
+        a.lead = in.lead;
+        a.algo = algo;
+        // (the projection reaches the kernel, as for BED)
+        for (int c = 0; c < EXG_SAM_COLUMNS; c++) {
+            if (!r->want(c) && !((r->filter_cols >> c) & 1ull)) continue;
+            a.d_columns[c] = r->d_cols[c];
+            a.d_validity[c] = (uint64_t *)r->d_col_valid[c];
+        }
+        return scan_rc(exg_sam_scan(&a));
+    }
     int launch_fasta() {
         in.b = std::make_shared<Batch>();
         if (!count_only) {
@@ -1019,7 +1030,13 @@ struct BatchRun {
     }
     int scan_rc(int rc) { return rc ? fail(r, rc, exg_last_error_message()) : EXG_OK; }
     int launch_scan(uint32_t algo) {
-        return r->format == EXG_FMT_FASTQ ? launch_fastq(algo) : r->format == EXG_FMT_VCF ? launch_vcf(algo) : r->format == EXG_FMT_BED ? launch_bed(algo) : launch_fasta();
+        switch (r->format) {
+            case EXG_FMT_FASTQ: return launch_fastq(algo);
+            case EXG_FMT_VCF: return launch_vcf(algo);
+            case EXG_FMT_BED: return launch_bed(algo);
+            case EXG_FMT_SAM: return launch_sam(algo);
+            default: return launch_fasta();
+        }
     }
     int scan() {
         int rc = launch_scan(r->fused_algo);

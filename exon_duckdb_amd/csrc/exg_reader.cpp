@@ -31,10 +31,9 @@ extern "C" int exg_open(const exg_open_args *args, exg_reader **out) {
     for (char &ch : fmt) ch = (char)tolower((unsigned char)ch);
     if (const FormatDesc *f = format_named(fmt.c_str())) {
         r->format = f->format;
-        if (r->format == EXG_FMT_BED) r->fused_algo = EXG_ALGO_FUSED_FULL;  // (one single-pass scan: exg_bed.hip)
-    } else if (fmt == "sam") {
-        exg::set_error("file_format sam is not supported: the SAM text tokeniser is not built (read_bam_file_records reads BAM)");
-        return EXG_E_UNSUPPORTED;
+        if (r->format == EXG_FMT_BED) r->fused_algo = EXG_ALGO_FUSED_FULL;  // (one single-pass scan: exg_bed.hip; SAM below: exg_sam.hip)
+    } else if (fmt == "sam") {  // (not in format_named's answers: see there)
+        r->format = EXG_FMT_SAM, r->fused_algo = EXG_ALGO_FUSED_FULL;
     } else {
         // rust/src/arrow_reader.rs:93-102
         exg::set_error("could not parse file_format %s", args->file_format);
@@ -86,6 +85,22 @@ extern "C" int exg_open(const exg_open_args *args, exg_reader **out) {
     if (r->compression == kBzip2 && r->shard_count > 1) {  // (one bzip2 file is one shard: blocks are not split among readers)
         exg::set_error("exg_open: shards of a bzip2 input are not supported (shard_count %u): one file is one shard", r->shard_count);
         return EXG_E_UNSUPPORTED;
+    }
+    if (r->format == EXG_FMT_SAM && r->compression == kNone) {
+        // SAM is text.  A file that begins with the gzip magic and is to be read as it is cannot be: it is a BAM file (BGZF) or a
+        // compressed SAM whose name does not say so — refused here, by name, before a device is asked for, not as a field-count
+        // error at byte 0
+        for (const std::string &f : r->files) {
+            unsigned char magic[2] = {0, 0};
+            FILE *fp = fopen(f.c_str(), "rb");
+            const size_t got = fp ? fread(magic, 1, 2, fp) : 0;
+            if (fp) fclose(fp);
+            if (got == 2 && magic[0] == 0x1f && magic[1] == 0x8b) {
+                exg::set_error("file_format sam is not supported for '%s': it holds gzip members, not SAM text (a BAM file: file_format bam / "
+                               "read_bam_file_records; a gzip-compressed SAM: compression gzip)", f.c_str());
+                return EXG_E_UNSUPPORTED;
+            }
+        }
     }
     const int n_dev = exg_device_count();
     if (n_dev < 1) return EXG_E_NO_DEVICE;

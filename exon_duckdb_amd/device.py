@@ -419,6 +419,8 @@ class BedScan:
              "block_count", "block_sizes", "block_starts"]
     INT_COLS, NULLABLE = (1, 2, 4, 6, 7, 9), tuple(range(3, 12))
     PAYLOAD_BASE = 1 << 44
+    # what SamScan overrides: the column count, the integer columns' width, the format, the args struct and the entry point
+    N_COLS, INT_DTYPE, FMT, ARGS, ENTRY = abi.EXG_BED_COLUMNS, "int64", abi.EXG_FMT_BED, abi.BedScanArgs, "exg_bed_scan"
 
     def __init__(self, n_bytes, capacity_records=None, device="cuda"):
         torch = _torch()
@@ -426,13 +428,13 @@ class BedScan:
         self.n_bytes = n_bytes
         self.capacity = int(capacity_records if capacity_records is not None else n_bytes // 2 + 16)
         cap = max(self.capacity, 1)
-        self.cols = [torch.empty((cap,), dtype=torch.int64, device=device) if c in self.INT_COLS else
-                     torch.empty((cap, 2), dtype=torch.int64, device=device) for c in range(abi.EXG_BED_COLUMNS)]
+        self.cols = [torch.empty((cap,), dtype=getattr(torch, self.INT_DTYPE), device=device) if c in self.INT_COLS else
+                     torch.empty((cap, 2), dtype=torch.int64, device=device) for c in range(self.N_COLS)]
         self.validity = {c: torch.empty(((cap + 63) // 64,), dtype=torch.int64, device=device) for c in self.NULLABLE}
-        self.ws_bytes = int(self.lib.exg_scan_workspace_bytes(abi.EXG_FMT_BED, n_bytes))
+        self.ws_bytes = int(self.lib.exg_scan_workspace_bytes(self.FMT, n_bytes))
         self.ws = torch.empty((self.ws_bytes + 255) // 8, dtype=torch.int64, device=device)
         self.result = torch.zeros(8, dtype=torch.int64, device=device)
-        self.args = abi.BedScanArgs()
+        self.args = self.ARGS()
 
     def launch(self, d_input, n_bytes=None, lead=0, payload_base=None, flags=abi.EXG_F_BOF | abi.EXG_F_EOF,
                algo=abi.EXG_ALGO_AUTO, project=None):
@@ -442,7 +444,7 @@ class BedScan:
         a.lead = lead
         a.payload_base = self.PAYLOAD_BASE if payload_base is None else payload_base
         a.flags, a.algo = flags, algo
-        for c in range(abi.EXG_BED_COLUMNS):
+        for c in range(self.N_COLS):
             on = project is None or c in project
             a.d_columns[c] = self.cols[c].data_ptr() if on else None
             a.d_validity[c] = self.validity[c].data_ptr() if on and c in self.validity else None
@@ -450,7 +452,7 @@ class BedScan:
         a.d_workspace, a.workspace_bytes = self.ws.data_ptr(), self.ws_bytes
         a.d_result = self.result.data_ptr()
         a.stream = stream_ptr().value
-        check(self.lib.exg_bed_scan(C.byref(a)))
+        check(getattr(self.lib, self.ENTRY)(C.byref(a)))
 
     def fetch(self):
         r = abi.ScanResult()
@@ -461,7 +463,7 @@ class BedScan:
         """raw columns ([n,16] uint8 string_t / int64) and validity words of the first n rows"""
         nw = (n + 63) // 64
         cols = [self.cols[c][:n].cpu().numpy() if c in self.INT_COLS else self.cols[c][:n].cpu().numpy().view(np.uint8).reshape(n, 16)
-                for c in range(abi.EXG_BED_COLUMNS)]
+                for c in range(self.N_COLS)]
         return cols, {c: v[:nw].cpu().numpy().view(np.uint64) for c, v in self.validity.items()}
 
     def rows(self, n, data: bytes, columns=None, payload_base=None):
@@ -469,7 +471,7 @@ class BedScan:
         base = self.PAYLOAD_BASE if payload_base is None else payload_base
         cols, words = self.host(n)
         out = []
-        for c in (range(abi.EXG_BED_COLUMNS) if columns is None else columns):
+        for c in (range(self.N_COLS) if columns is None else columns):
             valid = np.unpackbits(words[c].view(np.uint8), bitorder="little")[:n] if c in words else None
             if c in self.INT_COLS:
                 vals = cols[c].tolist()
@@ -495,3 +497,11 @@ class BedScan:
                         vals[i] = None
             out.append(vals)
         return list(zip(*out))
+
+
+class SamScan(BedScan):
+    """exg_sam_scan on SAM alignment lines (no header) resident in HBM: BedScan's buffers and decoding with BAM's ten columns,
+    the three INTEGER ones 4 bytes wide."""
+    NAMES = ["name", "flag", "reference", "start", "end", "mapping_quality", "cigar", "mate_reference", "sequence", "quality_score"]
+    INT_COLS, NULLABLE = (1, 3, 4), (2, 3, 4, 5, 7)
+    N_COLS, INT_DTYPE, FMT, ARGS, ENTRY = abi.EXG_SAM_COLUMNS, "int32", abi.EXG_FMT_SAM, abi.SamScanArgs, "exg_sam_scan"

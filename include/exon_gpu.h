@@ -44,8 +44,8 @@ extern "C" {
 #endif
 
 /* 9 still: read_bed_file (EXG_FMT_BED, exg_bed_scan, EXG_PE_BED_*), the sequence scalars (exg_sequence_op,
- * EXG_SEQ_*, EXG_PE_SEQ_*) and the alignment scores (exg_align_score, EXG_PE_ALIGN_TOO_LONG) are pure additions — no
- * existing struct, constant or entry point changed. */
+ * EXG_SEQ_*, EXG_PE_SEQ_*), the alignment scores (exg_align_score, EXG_PE_ALIGN_TOO_LONG) and read_sam_file_records
+ * (EXG_FMT_SAM, exg_sam_scan, EXG_PE_SAM_*) are pure additions — no existing struct, constant or entry point changed. */
 #define EXG_ABI_VERSION 9
 
 /* DuckDB v0.8.1 STANDARD_VECTOR_SIZE; the reference asks the Rust side for
@@ -100,6 +100,15 @@ extern "C" {
 #define EXG_PE_SEQ_LENGTH 31          /* translate_dna_to_aa: the length is not a multiple of 3 */
 #define EXG_PE_SEQ_CODON 32           /* translate_dna_to_aa: three bytes that are not a codon over A, C, G, T */
 #define EXG_PE_ALIGN_TOO_LONG 33      /* exg_align_score: |text| + |pattern| of a row exceeds max_pair_bytes */
+/* (34 stays unassigned, like 29: callers probe it to see "unknown parse error") */
+#define EXG_PE_SAM_FIELD_COUNT 35     /* SAM: a line with fewer than 11 tab-separated fields (an empty line among them) */
+#define EXG_PE_SAM_EMPTY_FIELD 36     /* SAM: one of the eleven mandatory fields is empty */
+#define EXG_PE_SAM_HEADER_LINE 37     /* SAM: a line that starts with '@' behind the header */
+#define EXG_PE_SAM_FLAG 38            /* SAM: FLAG is not made of digits only, or above 65535 */
+#define EXG_PE_SAM_POSITION 39        /* SAM: POS is not made of digits only, or above 2^31 - 1 */
+#define EXG_PE_SAM_MAPQ 40            /* SAM: MAPQ is not made of digits only, or above 255 */
+#define EXG_PE_SAM_CIGAR 41           /* SAM: CIGAR is neither `*` nor [digits, one of MIDNSHP=X]+ with lengths <= 2^28 - 1 */
+#define EXG_PE_SAM_LENGTHS 42         /* SAM: SEQ and QUAL are both present and differ in length */
 
 /* ---- duckdb::string_t, bit-for-bit (v0.8.1 duckdb/common/types/string_type.hpp)
  * length <= 12: bytes inlined, zero padded.  Otherwise 4-byte prefix + pointer.
@@ -124,6 +133,7 @@ typedef union exg_string_t {
 #define EXG_FMT_VCF 3
 #define EXG_FMT_BAM 4 /* reader level + exg_bam_scan; the chunk boundary only (new_reader refuses it) */
 #define EXG_FMT_BED 5 /* reader level + exg_bed_scan; the chunk boundary only (new_reader refuses it) */
+#define EXG_FMT_SAM 6 /* reader level + exg_sam_scan; the chunk boundary only (new_reader refuses it) */
 
 /* ---- scan flags ------------------------------------------------------------ */
 #define EXG_F_BOF 1u /* a line starts at d_input[0] (start of file, or a record-aligned batch) */
@@ -326,6 +336,35 @@ typedef struct exg_bed_scan_args {
     void *stream;
 } exg_bed_scan_args;
 
+/* SAM (read_sam_file_records): one row per alignment line, the ten columns of read_bam_file_records in the same order, with
+ * the same names, types and nullability (test_sam_record_scan.test:6-17; the value rules are INTEGRATION.md's):
+ *   0 name VARCHAR, 1 flag INTEGER, 2 reference VARCHAR?, 3 start INTEGER?, 4 end INTEGER?, 5 mapping_quality VARCHAR?,
+ *   6 cigar VARCHAR, 7 mate_reference VARCHAR?, 8 sequence VARCHAR, 9 quality_score VARCHAR
+ * The input holds alignment lines only: the header (the leading '@' lines) is skipped by the caller (the reader does it at
+ * open).  A line has 11 or more tab-separated fields; fields 12 and up are not read.  Every string is a zero-copy slice of
+ * the input (payload_base + offset; up to 12 bytes inlined): there is no side buffer.  mate_reference `=` is a string_t on
+ * RNAME's bytes; mapping_quality points behind the field's leading zeros.  A NULL value holds zeros (16 bytes / 4 bytes).
+ * lead, flags, algo and the result block are exg_bed_scan's: EXG_ALGO_MULTIPASS is the general path, EXG_ALGO_AUTO /
+ * EXG_ALGO_FUSED / EXG_ALGO_FUSED_FULL all run the single-pass any-shape scan (there is no lean instance),
+ * EXG_ALGO_FUSED_INDEX is EXG_E_INVALID_ARG. */
+#define EXG_SAM_COLUMNS 10
+typedef struct exg_sam_scan_args {
+    const void *d_input; /* device pointer, 16-byte aligned, readable up to round_up(n_bytes,16) */
+    uint64_t n_bytes;
+    uint64_t lead;
+    uint64_t payload_base;
+    uint32_t flags;
+    uint32_t algo;
+    void *d_columns[EXG_SAM_COLUMNS];      /* device: exg_string_t[capacity_records] for columns 0, 2, 5, 6, 7, 8, 9; int32_t[] for 1, 3, 4.
+                                            * NULL = not produced, still validated */
+    uint64_t *d_validity[EXG_SAM_COLUMNS]; /* device: ceil(capacity / 64) words for columns 2, 3, 4, 5, 7 (when produced) */
+    uint64_t capacity_records;
+    void *d_workspace; /* device, exg_scan_workspace_bytes(EXG_FMT_SAM, n_bytes), 256-byte aligned */
+    uint64_t workspace_bytes;
+    exg_scan_result *d_result; /* device, 64 bytes */
+    void *stream;
+} exg_sam_scan_args;
+
 /* ---- library / device ------------------------------------------------------ */
 int exg_abi_version(void);
 /* Number of visible HIP devices, or EXG_E_NO_DEVICE. Does not initialise a context. */
@@ -344,6 +383,8 @@ int exg_fasta_scan(const exg_fasta_scan_args *args);
 int exg_bam_scan(const exg_bam_scan_args *args);
 /* Enqueue on args->stream; asynchronous (the result through exg_fetch_result). */
 int exg_bed_scan(const exg_bed_scan_args *args);
+/* Enqueue on args->stream; asynchronous (the result through exg_fetch_result). */
+int exg_sam_scan(const exg_sam_scan_args *args);
 /* Synchronising copy of the 64-byte result to the host. */
 int exg_fetch_result(const exg_scan_result *d_result, void *stream, exg_scan_result *out);
 /* '\n' count of d_input[begin,end) into *d_count (device u64); used for the shard phase exchange. */
@@ -605,10 +646,11 @@ typedef struct exg_reader exg_reader;
 
 typedef struct exg_open_args {
     const char *path;        /* local file or directory (the reference lists directories: test_fasta_scan.test:55-59) */
-    const char *file_format; /* "fasta" | "fastq" | "vcf" | "bam" | "bed" (the reference's file_type strings, exon_extension.cpp:47-58;
-                              * any case).  A BAM file is always read as gzip members (BGZF), whatever `compression` says, and as
-                              * ONE shard (shard_count > 1: EXG_E_UNSUPPORTED); "sam" is refused.  "bed": text without a header,
-                              * every line a record; batches, decoders, shards and fan-out as for VCF */
+    const char *file_format; /* "fasta" | "fastq" | "vcf" | "bam" | "bed" | "sam" (the reference's file_type strings,
+                              * exon_extension.cpp:47-58; any case).  A BAM file is always read as gzip members (BGZF), whatever
+                              * `compression` says, and as ONE shard (shard_count > 1: EXG_E_UNSUPPORTED).  "bed": text without a
+                              * header, every line a record; "sam": the leading '@' lines are skipped at open, every line behind
+                              * them is a record; both: batches, decoders, shards and fan-out as for VCF */
     const char *compression; /* NULL = infer from extension like arrow_reader.rs:60-75; "gzip","zstd","uncompressed",... */
     uint64_t batch_rows;     /* rows per chunk; 0 => EXG_VECTOR_SIZE */
     int device;              /* HIP device ordinal */
@@ -807,7 +849,7 @@ typedef struct ReaderResult {
  * the `filters` predicate and the Arrow buffers themselves (offsets, values, validity) are produced
  * on the device; the host only copies them back and wires the ArrowArray structs.
  *   compression: NULL = by extension (:60-75), else DataFusion's FileCompressionType names (:77-91)
- *   file_format: "fasta" | "fastq" | "vcf" ("bam" and "bed" are refused: they are served at the chunk boundary, exg_open, only)
+ *   file_format: "fasta" | "fastq" | "vcf" ("bam", "bed" and "sam" are refused: they are served at the chunk boundary, exg_open, only)
  *   filters:     NULL / "" or the predicate text FilterToString renders (module.cpp:158-214):
  *                <column> (= | != | <> | < | <= | > | >=) <literal>, <column> IS [NOT] NULL, AND, OR
  *                with SQL precedence; it is applied as `SELECT * FROM exon_table WHERE <filters>` (:125-141). */
