@@ -191,6 +191,65 @@ int launch_line_index(const uint8_t *d_in, uint64_t n_bytes, uint64_t lead, uint
     return EXG_OK;
 }
 
+// ---- the result block of the line-row scans (exg_line_rows.hpp: BED, SAM) ------------------
+// n_bytes, lead, capacity, flags: the scan's.  fused != 0: positions come from tile_qend; else from nl_pos.
+__global__ __launch_bounds__(256) void k_line_rows_finalize(uint64_t n_bytes, uint64_t lead, uint64_t capacity, uint32_t flags, ScanWsHeader *hdr,
+                                                            const unsigned long long *__restrict__ tile_qend, uint32_t n_tiles,
+                                                            const uint64_t *__restrict__ nl_pos, int fused, exg_scan_result *res) {
+    __shared__ unsigned long long s_qend;
+    __shared__ int s_found;
+    if (threadIdx.x == 0) {
+        s_qend = 0;
+        s_found = 0;
+    }
+    __syncthreads();
+    if (fused) {
+        for (int64_t base = (int64_t)n_tiles - 1; base >= 0; base -= 256) {
+            const int64_t t = base - threadIdx.x;
+            const unsigned long long q = t >= 0 ? tile_qend[t] & ~kFarBit : 0;
+            if (q) atomicMax(&s_qend, q);
+            if (q) s_found = 1;
+            __syncthreads();
+            if (s_found) break;
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x) return;
+    const uint64_t T = hdr->total_lines, halo = hdr->halo_nl;
+    const uint64_t n_owned = T > halo ? T - halo : 0;
+    uint64_t last_end = s_qend;
+    if (!fused) {
+        const uint64_t Tc = T < hdr->lines_cap ? T : hdr->lines_cap;
+        last_end = Tc ? nl_pos[Tc - 1] + 1 : 0;
+        if (last_end > n_bytes) last_end = n_bytes;
+    }
+    exg_scan_result r;
+    r.n_lines = n_owned;
+    r.flags = hdr->flags;
+    if (!fused && T > hdr->lines_cap) r.flags |= EXG_RF_INDEX_OVERFLOW;
+    r.payload_bytes = 0;
+    r.redo_tiles = 0;
+    r.error_code = 0;
+    r.error_offset = ~0ull;
+    r.error_record = ~0ull;
+    uint64_t n_rec = (n_owned < capacity || (flags & EXG_F_NO_STORE)) ? n_owned : capacity;
+    uint64_t consumed = last_end > lead ? last_end : lead;
+    const unsigned long long err = hdr->err_word;
+    if (err != kNoError) {
+        const uint64_t rec = err >> 8;
+        r.error_code = (uint32_t)(err & 0xFF);
+        r.error_record = rec;
+        r.error_offset = hdr->err_off;
+        if (rec < n_rec) {
+            n_rec = rec;
+            consumed = hdr->err_off > lead ? hdr->err_off : lead;
+        }
+    }
+    r.n_records = n_rec;
+    r.consumed_bytes = n_rec ? consumed : lead;
+    *res = r;
+}
+
 // ---- exg_count_newlines ------------------------------------------------------------------
 
 __global__ __launch_bounds__(256) void k_count_range(const uint8_t *__restrict__ d_in, uint64_t begin, uint64_t end,

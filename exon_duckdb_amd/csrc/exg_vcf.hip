@@ -18,9 +18,7 @@
 // `lead` are not rows.
 #include <stdlib.h>
 
-#include "exg_fused_core.hpp"
-#include "exg_line_src.hpp"
-#include "exg_lines.hpp"
+#include "exg_line_rows.hpp"
 
 #include "exg_parse.hpp"
 #include "exg_float_slow.hpp"
@@ -191,10 +189,6 @@ __device__ __forceinline__ VcfRowInfo vcf_line(const Src &src, int s, int e, con
     return r;
 }
 
-__device__ __forceinline__ void vcf_report(ScanWsHeader *hdr, uint32_t code, unsigned long long out, uint64_t line_off) {
-    atomicMin(&hdr->err_word, (out << 8) | (code & 0x7Fu));
-    atomicMin(&hdr->err_off, (unsigned long long)line_off);
-}
 // a QUAL literal for the exact parser (k_vcf_finalize).  The list holds one literal per 32 bytes of input, at most 4096 per
 // launch (such a literal has more than 19 digits and sits astride a float rounding boundary: one in 10^11 by chance); more
 // than that is an error (EXG_RF_QUAL_RANGE)
@@ -207,7 +201,7 @@ __device__ __forceinline__ void vcf_slow_qual(ScanWsHeader *hdr, const VcfDev &a
         a.d_slow[k].row = (unsigned int)out;
     } else {
         atomicOr(&hdr->flags, EXG_RF_QUAL_RANGE);
-        vcf_report(hdr, EXG_PE_VCF_BAD_QUAL, out, line_off);
+        row_report(hdr, EXG_PE_VCF_BAD_QUAL, out, line_off);
     }
 }
 
@@ -257,17 +251,7 @@ struct VcfFormat {
         const uint32_t rot_w = 0;  // (measured, A/B in one box: rotating is 2-4 % SLOWER on wide and on short lines alike — kept as a switch)
 #endif
         const uint32_t t_rot = (threadIdx.x - rot_w * 64u) & (uint32_t)(kThreads - 1);  // this thread's line of a pass of 256
-        unsigned long long qend_word = 0;  // (thread t_rot == 0: what it stored into tile_qend)
-        if (t_rot == 0 && (c.pass_base == 0 || c.n_lines)) {  // offset just past the last line that ends in this half (0: none)
-            long long e = 0;
-            if (c.n_lines) {
-                e = (long long)c.tile_off + (int)s.nlist[4 + c.n_lines - 1] - kWin + 1;
-                if ((unsigned long long)e > a.n_bytes) e = (long long)a.n_bytes;
-            }
-            if (c.pass_base) e |= (long long)(tile_qend[tile_index] & kFarBit);  // (a later pass keeps the first pass's mark)
-            qend_word = (unsigned long long)e;
-            tile_qend[tile_index] = qend_word;
-        }
+        const unsigned long long qend_word = half_qend(s, c, a.n_bytes, t_rot == 0, tile_qend, tile_index);
         if (dev_mode == 3 || dev_mode == 4) return;
         if constexpr (kMode == kFullIndex) {
             // EXG_ALGO_FUSED_INDEX (round 5).  A half of a cohort VCF holds 1-40 lines: thread = line leaves ONE wave running each
@@ -311,16 +295,7 @@ struct VcfFormat {
                         hdr->any_redo = 1u;
                     } else {
                         // any-shape scan: its row is k_vcf_far's
-                        FarRec f;
-                        f.pos[0] = s.prev32[3];
-                        f.pos[1] = c.half * kTile + e1 - kWin;
-                        f.pos[2] = f.pos[3] = f.pos[4] = 0;
-                        f.flags = c.is_eof_tile ? 1u : 0u;
-                        f.out = out;
-                        far_rec_of<false>(tile_qend, a.n_bytes)[tile_index] = f;
-                        hdr->any_far = 1u;
-                        tile_qend[tile_index] = qend_word | kFarBit;  // (this thread stored the word above: no load — a load behind
-                                                                       // the store cost a memory round trip per half of a cohort VCF)
+                        mark_far_line(s, c, a.n_bytes, e1, out, qend_word, hdr, tile_qend, tile_index);
                     }
                 } else {
                     int s0 = (int)q0 + 1;
@@ -332,7 +307,7 @@ struct VcfFormat {
                     if constexpr (kMode != kLean) {  // noodles builds str fields: the line must be UTF-8
                         if (!r.code && c.non_ascii && !utf8_valid_lds(s, s0, e1)) r.code = EXG_PE_INVALID_UTF8;
                     }
-                    if (r.code) vcf_report(hdr, r.code, (unsigned long long)out, c.tile_off + s0 - kWin);
+                    if (r.code) row_report(hdr, r.code, (unsigned long long)out, c.tile_off + s0 - kWin);
                     else if (r.slow_len) vcf_slow_qual(hdr, a, c.tile_off + r.slow_s - kWin, (uint32_t)r.slow_len, (unsigned long long)out, c.tile_off + s0 - kWin);
                     qv = r.qual_valid;
                     rv = r.rest_valid;
@@ -368,29 +343,21 @@ __global__ __launch_bounds__(256) void k_vcf_lines(VcfDev a, const uint64_t *__r
         }
         bool qv = false, rv = false;
         if (act) {
-            uint64_t e1 = nl_pos[j];
-            bool resolved = j > 0 || (a.flags & EXG_F_BOF);
-            uint64_t s0 = j > 0 ? nl_pos[j - 1] + 1 : 0;
-            if (!resolved) {
-                atomicAdd(&hdr->n_unresolved, 1ull);
-                atomicOr(&hdr->flags, EXG_RF_HEAD_UNRESOLVED);
-            } else if (e1 - s0 > 0x7FFFFFF0ull) {
-                vcf_report(hdr, EXG_PE_FIELD_TOO_LONG, out, s0);
-            } else {
-                if (s0 > e1) s0 = e1;
-                bool virt = e1 >= a.n_bytes;
-                if (!virt && e1 > s0 && a.d_in[e1 - 1] == '\r') e1--;
-                const GlobalSrc src{a.d_in, s0, a.payload_base, (a.n_bytes + 15) & ~15ull};
+            const uint64_t e1 = nl_pos[j];
+            const bool resolved = j > 0 || (a.flags & EXG_F_BOF);
+            const uint64_t s0 = j > 0 ? nl_pos[j - 1] + 1 : 0;
+            if (!resolved) head_unresolved(hdr);
+            else global_line(a, hdr, out, s0, e1, [&](const GlobalSrc &src, uint64_t s0, uint64_t e1) {
                 VcfRowInfo r = vcf_line(src, 0, (int)(e1 - s0), a, out, !no_store);
                 if (!r.code && (hdr->flags & EXG_RF_NON_ASCII)) {
                     // noodles builds str fields: the line must be UTF-8
                     if (!utf8_valid_global(a.d_in, s0, e1)) r.code = EXG_PE_INVALID_UTF8;
                 }
-                if (r.code) vcf_report(hdr, r.code, out, s0);
+                if (r.code) row_report(hdr, r.code, out, s0);
                 else if (r.slow_len) vcf_slow_qual(hdr, a, s0 + (uint64_t)r.slow_s, (uint32_t)r.slow_len, out, s0);
                 qv = r.qual_valid;
                 rv = r.rest_valid;
-            }
+            });
         }
         if (!no_store) {
             long long out_base = (long long)(it * 64) - (long long)halo;
@@ -493,7 +460,7 @@ __global__ __launch_bounds__(256) void k_vcf_rows(VcfDev a, const uint64_t *__re
                 atomicAdd(&hdr->n_unresolved, 1ull);
                 atomicOr(&hdr->flags, EXG_RF_HEAD_UNRESOLVED);
             } else if (e1 - s0 > 0x7FFFFFF0ull) {
-                vcf_report(hdr, EXG_PE_FIELD_TOO_LONG, out, s0);
+                row_report(hdr, EXG_PE_FIELD_TOO_LONG, out, s0);
             } else {
                 if (s0 > e1) s0 = e1;
                 // the line's head: the 16-byte blocks from the one that holds its first byte (a block that begins below `limit`
@@ -527,7 +494,7 @@ __global__ __launch_bounds__(256) void k_vcf_rows(VcfDev a, const uint64_t *__re
                     // noodles builds str fields: the line must be UTF-8
                     if (!utf8_valid_global(a.d_in, s0, e1)) r.code = EXG_PE_INVALID_UTF8;
                 }
-                if (r.code) vcf_report(hdr, r.code, out, s0);
+                if (r.code) row_report(hdr, r.code, out, s0);
                 else if (r.slow_len) vcf_slow_qual(hdr, a, s0 + (uint64_t)r.slow_s, (uint32_t)r.slow_len, out, s0);
                 qv = r.qual_valid;
                 rv = r.rest_valid;
@@ -557,27 +524,19 @@ __global__ __launch_bounds__(256) void k_vcf_far(VcfDev a, const unsigned int *_
         int64_t p[2];
         const unsigned long long out = (unsigned long long)f.out;
         if (!far_positions<2>(f, (uint32_t)(x / kHalves), kSuper, tileA, tileL, (a.flags & EXG_F_BOF) != 0, p)) {
-            atomicAdd(&hdr->n_unresolved, 1ull);  // the line begins in front of d_input[0]: the caller widens the halo
-            atomicOr(&hdr->flags, EXG_RF_HEAD_UNRESOLVED);
+            head_unresolved(hdr);
             continue;
         }
-        uint64_t s0 = (uint64_t)(p[0] + 1), e1 = (uint64_t)p[1];
-        if (e1 - s0 > 0x7FFFFFF0ull) {
-            vcf_report(hdr, EXG_PE_FIELD_TOO_LONG, out, s0);
-            continue;
-        }
-        if (s0 > e1) s0 = e1;
-        const bool virt = e1 >= a.n_bytes;
-        if (!virt && e1 > s0 && a.d_in[e1 - 1] == '\r') e1--;
-        const GlobalSrc src{a.d_in, s0, a.payload_base, (a.n_bytes + 15) & ~15ull};
-        VcfRowInfo r = vcf_line(src, 0, (int)(e1 - s0), a, out, !no_store);
-        if (!r.code && tiles_non_ascii(tileA, kSuper, (int64_t)s0, (int64_t)e1) && !utf8_valid_global(a.d_in, s0, e1)) r.code = EXG_PE_INVALID_UTF8;
-        if (r.code) vcf_report(hdr, r.code, out, s0);
-        else if (r.slow_len) vcf_slow_qual(hdr, a, s0 + (uint64_t)r.slow_s, (uint32_t)r.slow_len, out, s0);
-        if (!no_store) {
-            if (r.qual_valid && a.d_qual_valid) atomicOr((unsigned long long *)&a.d_qual_valid[out >> 6], 1ull << (out & 63));
-            if (r.rest_valid && a.d_formats_valid) atomicOr((unsigned long long *)&a.d_formats_valid[out >> 6], 1ull << (out & 63));
-        }
+        global_line(a, hdr, out, (uint64_t)(p[0] + 1), (uint64_t)p[1], [&](const GlobalSrc &src, uint64_t s0, uint64_t e1) {
+            VcfRowInfo r = vcf_line(src, 0, (int)(e1 - s0), a, out, !no_store);
+            if (!r.code && tiles_non_ascii(tileA, kSuper, (int64_t)s0, (int64_t)e1) && !utf8_valid_global(a.d_in, s0, e1)) r.code = EXG_PE_INVALID_UTF8;
+            if (r.code) row_report(hdr, r.code, out, s0);
+            else if (r.slow_len) vcf_slow_qual(hdr, a, s0 + (uint64_t)r.slow_s, (uint32_t)r.slow_len, out, s0);
+            if (!no_store) {
+                if (r.qual_valid && a.d_qual_valid) atomicOr((unsigned long long *)&a.d_qual_valid[out >> 6], 1ull << (out & 63));
+                if (r.rest_valid && a.d_formats_valid) atomicOr((unsigned long long *)&a.d_formats_valid[out >> 6], 1ull << (out & 63));
+            }
+        });
     }
 }
 
@@ -604,7 +563,7 @@ __global__ __launch_bounds__(256) void k_vcf_finalize(VcfDev a, ScanWsHeader *hd
             if (rc || v < 0.0f) {
                 unsigned long long line = lit.off;  // the record's offset = the start of its line
                 while (line > 0 && a.d_in[line - 1] != '\n') line--;
-                vcf_report(hdr, EXG_PE_VCF_BAD_QUAL, lit.row, line);
+                row_report(hdr, EXG_PE_VCF_BAD_QUAL, lit.row, line);
             }
             else if (a.d_qual && !(a.flags & EXG_F_NO_STORE) && lit.row < a.capacity)
                 a.d_qual[lit.row] = v;

@@ -115,7 +115,7 @@ def seam_bytes():
 
 
 def far_bytes():
-    """lines for k_sam_far: a 5 kB read that begins in front of a half's window and ends inside the half, a 5 kB name the same way,
+    """lines for k_line_far: a 5 kB read that begins in front of a half's window and ends inside the half, a 5 kB name the same way,
     a 40 kB read over two whole halves and a super-tile seam — all with aux fields behind QUAL or without"""
     rng = S.rng(13)
     data = S.fill_to(rng, b"", 3 * HALF - 2600)

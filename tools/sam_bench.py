@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Rates of read_sam_file_records on one GPU, for two generated shapes: 150 bp pairs (the records of
-bam_files.illumina_pairs as text, ~400-byte lines) and 15 kb long reads (~30 kB lines, every one of them k_sam_far's).
+bam_files.illumina_pairs as text, ~400-byte lines) and 15 kb long reads (~30 kB lines, every one of them k_line_far's).
 
   scan   exg_sam_scan alone (EXG_ALGO_FUSED_FULL, the single-pass scan) on text resident in HBM, timed with device events:
          all ten columns, `name, flag, start` only, and EXG_F_NO_STORE (tokenise + validate: COUNT(*)'s share); the general path
