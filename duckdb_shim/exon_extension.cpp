@@ -385,8 +385,79 @@ static void RegisterAlignmentScore(DatabaseInstance &db, const char *name) {
 	Catalog::GetSystemCatalog(db).CreateFunction(CatalogTransaction::GetSystemTransaction(db), info);
 }
 
-// exon_extension.cpp:62-73, :81-93: the sequence scalars, the flag predicates and the alignment scores (parse_cigar,
-// extract_from_cigar, gff_parse_attributes and alignment_string* are not registered: INTEGRATION.md)
+// sam_functions/module.cpp:32-77: parse_cigar(VARCHAR) -> LIST(STRUCT(op VARCHAR, len INTEGER)) on the host scalar
+// exon_scan::ParseCigar over the rules of csrc/exg_cigarfn.hpp.  The list entries, the two STRUCT children and the one-letter
+// strings are written directly, as QualityScoreStringToList writes its list.  The empty string and `*` give an empty list
+// (the reference rejects the empty string; the scans hand `*` over as one).  NULL in, NULL out.
+static void ParseCigarFunction(DataChunk &args, ExpressionState &, Vector &result) {
+	const idx_t count = args.size();
+	UnifiedVectorFormat in;
+	args.data[0].ToUnifiedFormat(count, in);
+	auto strings = reinterpret_cast<const string_t *>(in.data);
+	result.SetVectorType(VectorType::FLAT_VECTOR);
+	auto entries = FlatVector::GetData<list_entry_t>(result);
+	std::vector<exon_scan::CigarOp> all, row;
+	for (idx_t i = 0; i < count; i++) {
+		const idx_t k = in.sel->get_index(i);
+		entries[i].offset = all.size();
+		entries[i].length = 0;
+		if (!in.validity.RowIsValid(k)) {
+			FlatVector::SetNull(result, i, true);
+			continue;
+		}
+		if (exon_scan::ParseCigar(strings[k].GetData(), strings[k].GetSize(), &row).code) {
+			throw InvalidInputException(exon_scan::ParseCigarErrorText(strings[k].GetData(), strings[k].GetSize()));
+		}
+		entries[i].length = row.size();
+		all.insert(all.end(), row.begin(), row.end());
+	}
+	ListVector::Reserve(result, all.size());
+	auto &fields = StructVector::GetEntries(ListVector::GetEntry(result));
+	auto ops = FlatVector::GetData<string_t>(*fields[0]);
+	auto lens = FlatVector::GetData<int32_t>(*fields[1]);
+	for (idx_t j = 0; j < all.size(); j++) {
+		ops[j] = StringVector::AddString(*fields[0], &all[j].op, 1);
+		lens[j] = all[j].len;
+	}
+	ListVector::SetListSize(result, all.size());
+}
+
+// sam_functions/module.cpp:79-131: extract_from_cigar(VARCHAR, VARCHAR) -> STRUCT(sequence_start INTEGER, sequence_end
+// INTEGER, sequence VARCHAR) on exon_scan::ExtractFromCigar: the sequence without a leading and a trailing insertion.  An
+// absent CIGAR gives the whole sequence (the reference panics on it), insertions that exceed the sequence are an error (the
+// reference panics in the slice).  NULL in either argument, NULL out.
+static void ExtractFromCigarFunction(DataChunk &args, ExpressionState &, Vector &result) {
+	const idx_t count = args.size();
+	UnifiedVectorFormat in[2];
+	args.data[0].ToUnifiedFormat(count, in[0]);
+	args.data[1].ToUnifiedFormat(count, in[1]);
+	result.SetVectorType(VectorType::FLAT_VECTOR);
+	auto &fields = StructVector::GetEntries(result);
+	auto starts = FlatVector::GetData<int32_t>(*fields[0]);
+	auto ends = FlatVector::GetData<int32_t>(*fields[1]);
+	auto slices = FlatVector::GetData<string_t>(*fields[2]);
+	for (idx_t i = 0; i < count; i++) {
+		const idx_t ks = in[0].sel->get_index(i), kc = in[1].sel->get_index(i);
+		if (!in[0].validity.RowIsValid(ks) || !in[1].validity.RowIsValid(kc)) {
+			FlatVector::SetNull(result, i, true);
+			for (auto &field : fields) {
+				FlatVector::SetNull(*field, i, true);
+			}
+			starts[i] = ends[i] = 0;
+			continue;
+		}
+		const string_t &sequence = reinterpret_cast<const string_t *>(in[0].data)[ks];
+		const string_t &cigar = reinterpret_cast<const string_t *>(in[1].data)[kc];
+		const exon_scan::CigarStatus st = exon_scan::ExtractFromCigar(sequence.GetSize(), cigar.GetData(), cigar.GetSize(), &starts[i], &ends[i]);
+		if (st.code) {
+			throw InvalidInputException(exon_scan::ExtractFromCigarErrorText(st));
+		}
+		slices[i] = StringVector::AddString(*fields[2], sequence.GetData() + starts[i], (idx_t)(ends[i] - starts[i]));
+	}
+}
+
+// exon_extension.cpp:62-73, :81-93: the sequence scalars, the flag predicates, the alignment scores and the two CIGAR scalars
+// (gff_parse_attributes and alignment_string* are not registered: INTEGRATION.md)
 static void RegisterScalars(DatabaseInstance &db) {
 	RegisterAlignmentScore(db, "alignment_score");
 	RegisterAlignmentScore(db, "alignment_score_wfa_gap_affine");
@@ -405,6 +476,13 @@ static void RegisterScalars(DatabaseInstance &db) {
 		                       [op](DataChunk &args, ExpressionState &, Vector &result) { SequenceMapFunction(op, args, result); }));
 	}
 	ExtensionUtil::RegisterFunction(db, ScalarFunction("gc_content", {LogicalType::VARCHAR}, LogicalType::FLOAT, GcContentFunction));
+	ExtensionUtil::RegisterFunction(
+	    db, ScalarFunction("parse_cigar", {LogicalType::VARCHAR},
+	                       LogicalType::LIST(LogicalType::STRUCT({{"op", LogicalType::VARCHAR}, {"len", LogicalType::INTEGER}})), ParseCigarFunction));
+	ExtensionUtil::RegisterFunction(
+	    db, ScalarFunction("extract_from_cigar", {LogicalType::VARCHAR, LogicalType::VARCHAR},
+	                       LogicalType::STRUCT({{"sequence_start", LogicalType::INTEGER}, {"sequence_end", LogicalType::INTEGER}, {"sequence", LogicalType::VARCHAR}}),
+	                       ExtractFromCigarFunction));
 	for (uint32_t which = 0; which < (uint32_t)exg::seqfn::kSamFlagCount; which++) {
 		ExtensionUtil::RegisterFunction(
 		    db, ScalarFunction(exg::seqfn::kSamFlagNames[which], {LogicalType::INTEGER}, LogicalType::BOOLEAN,

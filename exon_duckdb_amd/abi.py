@@ -51,6 +51,8 @@ EXG_PE_SAM_POSITION = 39
 EXG_PE_SAM_MAPQ = 40
 EXG_PE_SAM_CIGAR = 41
 EXG_PE_SAM_LENGTHS = 42
+EXG_PE_CIGAR_INVALID = 44   # (43 is unassigned)
+EXG_PE_CIGAR_RANGE = 45
 
 EXG_FMT_FASTA, EXG_FMT_FASTQ, EXG_FMT_VCF, EXG_FMT_BAM, EXG_FMT_BED, EXG_FMT_SAM = 1, 2, 3, 4, 5, 6
 EXG_BAM_COLUMNS = 10
@@ -64,6 +66,7 @@ EXG_ALGO_AUTO, EXG_ALGO_MULTIPASS, EXG_ALGO_FUSED, EXG_ALGO_FUSED_FULL, EXG_ALGO
 
 EXG_SEQ_COMPLEMENT, EXG_SEQ_REVERSE_COMPLEMENT, EXG_SEQ_TRANSCRIBE, EXG_SEQ_REVERSE_TRANSCRIBE = 1, 2, 3, 4
 EXG_SEQ_TRANSLATE, EXG_SEQ_GC_CONTENT = 5, 6
+EXG_CIGAR_PARSE, EXG_CIGAR_EXTRACT = 1, 2
 
 EXG_SYNTH_FASTQ_SEED = 0xE0A5EED0001
 EXG_SYNTH_VCF_SEED = 0xE0A5EED0002
@@ -308,6 +311,43 @@ class AlignScoreArgs(C.Structure):
     ]
 
 
+class CigarResult(C.Structure):
+    _fields_ = [
+        ("total_ops", C.c_uint64),
+        ("error_row", C.c_uint64),
+        ("error_offset", C.c_uint64),
+        ("n_rows", C.c_uint64),
+        ("error_code", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("error_byte", C.c_uint8),
+        ("pad", C.c_uint8 * 23),
+    ]
+
+
+class CigarOpArgs(C.Structure):
+    _fields_ = [
+        ("op", C.c_uint32),
+        ("d_cigar", C.c_void_p),
+        ("d_cigar_payload", C.c_void_p),
+        ("cigar_payload_base", C.c_uint64),
+        ("d_sequence", C.c_void_p),
+        ("d_sequence_payload", C.c_void_p),
+        ("sequence_payload_base", C.c_uint64),
+        ("n_rows", C.c_uint64),
+        ("d_out_entries", C.c_void_p),
+        ("d_out_op", C.c_void_p),
+        ("d_out_len", C.c_void_p),
+        ("ops_capacity", C.c_uint64),
+        ("d_out_start", C.c_void_p),
+        ("d_out_end", C.c_void_p),
+        ("d_out_sequence", C.c_void_p),
+        ("d_workspace", C.c_void_p),
+        ("workspace_bytes", C.c_uint64),
+        ("d_result", C.c_void_p),
+        ("stream", C.c_void_p),
+    ]
+
+
 class OpenArgs(C.Structure):
     _fields_ = [("path", C.c_char_p), ("file_format", C.c_char_p), ("compression", C.c_char_p), ("batch_rows", C.c_uint64),
                 ("device", C.c_int), ("device_batch_bytes", C.c_uint64), ("filters", C.c_char_p),
@@ -351,6 +391,9 @@ SIGNATURES = {
     "exg_align_workspace_bytes": (C.c_uint64, [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32]),
     "exg_align_score": (C.c_int, [C.POINTER(AlignScoreArgs)]),
     "exg_align_result": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(AlignScoreResult)]),
+    "exg_cigar_workspace_bytes": (C.c_uint64, [C.c_uint32, C.c_uint64, C.c_uint64]),
+    "exg_cigar_op": (C.c_int, [C.POINTER(CigarOpArgs)]),
+    "exg_cigar_result": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(CigarResult)]),
     "exg_plan_shards": (C.c_int, [C.POINTER(OpenArgs), C.POINTER(C.c_uint32), C.POINTER(C.c_int), C.c_uint32]),
 }
 
@@ -391,6 +434,11 @@ TEST_SIGNATURES = {
     "exon_tf_alignment_score_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "exon_tf_alignment_score": (C.c_int, [C.c_int, C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
                                           C.c_char_p, C.c_uint64, C.POINTER(C.c_float), C.c_char_p, C.c_uint64]),
+    "exon_tf_parse_cigar": (C.c_int, [C.c_char_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32),
+                                      C.POINTER(C.c_uint64), C.c_char_p, C.c_uint64]),
+    "exon_tf_extract_from_cigar": (C.c_int, [C.c_uint64, C.c_char_p, C.c_uint64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_uint32),
+                                             C.POINTER(C.c_uint64), C.c_char_p, C.c_uint64]),
+    "exon_tf_parse_cigar_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "exon_tf_link_probe": (C.c_int, [C.c_int, C.c_uint64, C.c_int, C.POINTER(C.c_double)]),
     "exon_tf_host_pipeline_probe": (C.c_double, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double]),
     "exon_tf_host_zero_bounce_probe": (C.c_double, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(C.c_double)]),

@@ -91,6 +91,8 @@ extern "C" const char *exg_parse_error_string(uint32_t code) {
         case EXG_PE_SAM_MAPQ: return "invalid SAM mapping quality";
         case EXG_PE_SAM_CIGAR: return "invalid SAM CIGAR";
         case EXG_PE_SAM_LENGTHS: return "sequence and quality scores differ in length";
+        case EXG_PE_CIGAR_INVALID: return "invalid CIGAR string";
+        case EXG_PE_CIGAR_RANGE: return "CIGAR insertions exceed the sequence";
         default: return "unknown parse error";
     }
 }

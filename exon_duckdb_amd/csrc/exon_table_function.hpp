@@ -47,6 +47,7 @@
 
 #include "exon_gpu.h"
 #include "exg_alignfn.hpp"
+#include "exg_cigarfn.hpp"
 #include "exg_seqfn.hpp"
 
 namespace exon_scan {
@@ -443,6 +444,61 @@ static inline int AlignmentScore(const char *text, size_t n_, const char *patter
         }
     }
     return EXG_E_INVALID_ARG;  // (unreachable: the bound is an alignment's penalty)
+}
+
+// parse_cigar / extract_from_cigar (exon/src/exon/sam_functions/module.cpp:32-131, rust/src/sam_functions.rs:114-200): the
+// per-row arithmetic of the SQL scalars the shim registers, on the rules of exg_cigarfn.hpp (exg_cigar_op is the same on scan
+// columns that are still in HBM).  A status instead of an exception, like SequenceMap.
+struct CigarStatus {
+    uint32_t code = EXG_PE_NONE;  // EXG_PE_CIGAR_*
+    uint64_t offset = 0;          // EXG_PE_CIGAR_INVALID: where a left-to-right parser stops
+};
+struct CigarOp {
+    char op;
+    int32_t len;
+};
+// the operations of s[0, n) into *out (emptied first); the empty string and `*` have none
+static inline CigarStatus ParseCigar(const char *s, size_t n, std::vector<CigarOp> *out) {
+    namespace cf = exg::cigarfn;
+    const uint8_t *u = reinterpret_cast<const uint8_t *>(s);
+    CigarStatus st;
+    out->clear();
+    if (cf::is_absent(u, n)) return st;
+    for (uint64_t i = 0; i < n;) {
+        const cf::Step step = cf::next_op(u, n, i);
+        if (!step.ok) {
+            st.code = EXG_PE_CIGAR_INVALID, st.offset = step.next;
+            return st;
+        }
+        out->push_back(CigarOp{(char)step.op, (int32_t)step.len});
+        i = step.next;
+    }
+    return st;
+}
+// the slice of the sequence is its bytes [*start, *end)
+static inline CigarStatus ExtractFromCigar(size_t sequence_length, const char *cigar, size_t n, int32_t *start, int32_t *end) {
+    namespace cf = exg::cigarfn;
+    const uint8_t *u = reinterpret_cast<const uint8_t *>(cigar);
+    CigarStatus st;
+    const bool absent = cf::is_absent(u, n);
+    cf::Step first{0, 0, 0, true}, last{0, 0, 0, true};
+    for (uint64_t i = 0; !absent && i < n;) {  // the whole CIGAR is validated
+        last = cf::next_op(u, n, i);
+        if (!last.ok) {
+            st.code = EXG_PE_CIGAR_INVALID, st.offset = last.next;
+            return st;
+        }
+        if (i == 0) first = last;
+        i = last.next;
+    }
+    if (!cf::extract_range(absent, first.op, first.len, last.op, last.len, sequence_length, start, end)) st.code = EXG_PE_CIGAR_RANGE;
+    return st;
+}
+// the exception texts of the two SQL scalars: parse_cigar names the string (test_scalar_functions.test:97), extract_from_cigar
+// does not
+static inline std::string ParseCigarErrorText(const char *s, size_t n) { return std::string(exg::cigarfn::kInvalidText) + ": " + std::string(s, n); }
+static inline std::string ExtractFromCigarErrorText(const CigarStatus &st) {
+    return st.code == EXG_PE_CIGAR_RANGE ? exg::cigarfn::kRangeText : exg::cigarfn::kInvalidText;
 }
 
 // exon/src/exon_extension.cpp:47-58: the registrations of the path (+ the read_vcf alias the north star names)

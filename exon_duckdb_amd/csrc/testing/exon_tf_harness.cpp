@@ -275,6 +275,48 @@ extern "C" int exon_tf_alignment_score_batch(const char *texts, const uint64_t *
     }
     return EXG_OK;
 }
+static int cigar_failure(const exon_scan::CigarStatus &st, const std::string &text, uint32_t *code, uint64_t *offset, char *err, uint64_t err_cap) {
+    *code = st.code, *offset = st.offset;
+    if (err_cap) snprintf(err, (size_t)err_cap, "%s", text.c_str());
+    return EXG_E_PARSE;
+}
+// parse_cigar as the shim registers it (sam_functions/module.cpp:32-77): the operations' letters to ops and their lengths to
+// lens, *n_ops of them.  0; EXG_E_CAPACITY when cap is too small (*n_ops = what it takes); EXG_E_PARSE with *code, *offset and
+// the exception's text in err
+extern "C" int exon_tf_parse_cigar(const char *s, uint64_t n, char *ops, int32_t *lens, uint64_t cap, uint64_t *n_ops, uint32_t *code,
+                                   uint64_t *offset, char *err, uint64_t err_cap) {
+    if (err_cap) err[0] = 0;
+    *code = 0, *offset = 0, *n_ops = 0;
+    std::vector<exon_scan::CigarOp> list;
+    const exon_scan::CigarStatus st = exon_scan::ParseCigar(s, (size_t)n, &list);
+    if (st.code) return cigar_failure(st, exon_scan::ParseCigarErrorText(s, (size_t)n), code, offset, err, err_cap);
+    *n_ops = list.size();
+    if (list.size() > cap) return EXG_E_CAPACITY;
+    for (size_t k = 0; k < list.size(); k++) ops[k] = list[k].op, lens[k] = list[k].len;
+    return EXG_OK;
+}
+// extract_from_cigar as the shim registers it (sam_functions/module.cpp:79-131): the slice is sequence bytes [*start, *end)
+extern "C" int exon_tf_extract_from_cigar(uint64_t sequence_length, const char *cigar, uint64_t n, int32_t *start, int32_t *end,
+                                          uint32_t *code, uint64_t *offset, char *err, uint64_t err_cap) {
+    if (err_cap) err[0] = 0;
+    *code = 0, *offset = 0;
+    const exon_scan::CigarStatus st = exon_scan::ExtractFromCigar((size_t)sequence_length, cigar, (size_t)n, start, end);
+    if (st.code) return cigar_failure(st, exon_scan::ExtractFromCigarErrorText(st), code, offset, err, err_cap);
+    return EXG_OK;
+}
+// parse_cigar over n rows in one call (tools/cigar_bench.py times it: one core, no per-row call overhead): row i is
+// bytes[off[i] .. off[i + 1]); *total_ops = the operations of all rows, *len_sum = the sum of their lengths (keeps the work alive)
+extern "C" int exon_tf_parse_cigar_batch(const char *bytes, const uint64_t *off, uint64_t n, uint64_t *total_ops, uint64_t *len_sum) {
+    std::vector<exon_scan::CigarOp> list;
+    uint64_t total = 0, sum = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        if (exon_scan::ParseCigar(bytes + off[i], (size_t)(off[i + 1] - off[i]), &list).code) return EXG_E_PARSE;
+        total += list.size();
+        for (const exon_scan::CigarOp &o : list) sum += (uint64_t)o.len;
+    }
+    *total_ops = total, *len_sum = sum;
+    return EXG_OK;
+}
 // is_segmented .. is_supplementary (which = 0 .. 11) of an INTEGER flag; -1 for an unknown predicate
 extern "C" int exon_tf_sam_flag(uint32_t which, int32_t flag) {
     return which < (uint32_t)exg::seqfn::kSamFlagCount ? (exon_scan::SamFlag(which, flag) ? 1 : 0) : -1;

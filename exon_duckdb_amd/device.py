@@ -226,6 +226,72 @@ def align_score(text, text_payload, text_payload_base, pattern, pattern_payload,
     return scores[:n_rows], r
 
 
+def _cigar_call(a, n_rows, cigar, cigar_payload, cigar_payload_base, cigar_payload_bytes):
+    """the common half of a exg_cigar_op call: the cigar column, workspace and result block; runs it and fetches the result"""
+    torch = _torch()
+    lib = load_library()
+    dev = cigar.device
+    a.d_cigar, a.n_rows = cigar.data_ptr(), n_rows
+    a.d_cigar_payload = cigar_payload.data_ptr() if cigar_payload is not None else None
+    a.cigar_payload_base = cigar_payload_base
+    if cigar_payload_bytes is None:
+        cigar_payload_bytes = cigar_payload.numel() if cigar_payload is not None else 0
+    ws_bytes = int(lib.exg_cigar_workspace_bytes(a.op, n_rows, cigar_payload_bytes))
+    ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.int64, device=dev)
+    result = torch.empty(8, dtype=torch.int64, device=dev)
+    a.d_workspace, a.workspace_bytes = ws.data_ptr(), ws_bytes
+    a.d_result = result.data_ptr()
+    a.stream = stream_ptr().value
+    check(lib.exg_cigar_op(C.byref(a)))
+    r = abi.CigarResult()
+    check(lib.exg_cigar_result(C.c_void_p(result.data_ptr()), stream_ptr(), C.byref(r)))
+    return r
+
+
+def parse_cigar(cigar, n_rows, cigar_payload, cigar_payload_base, ops_capacity=None, cigar_payload_bytes=None):
+    """parse_cigar (reference sam_functions/module.cpp:32-77) on a cigar column that is still in HBM: `cigar` is a [cap, 2] int64
+    tensor of string_t (BamScan.cols[6] / SamScan.cols[6]), `cigar_payload` the buffer its pointers address.  Returns (entries
+    [n_rows, 2] int64 = DuckDB list_entry_t {offset, length}, op [total, 2] int64 = string_t of one letter, len [total] int32,
+    result).  ops_capacity=None is the two-call form: a counting call, then the exact capacity; with a capacity given,
+    result.flags & EXG_RF_CAPACITY means it was too small and the children were not written.  `cigar_payload_bytes`: an upper
+    bound of the bytes of the rows longer than 12 (default: the payload tensor's size).  An invalid row raises ExgError."""
+    torch = _torch()
+    dev = cigar.device
+    a = abi.CigarOpArgs()
+    a.op = abi.EXG_CIGAR_PARSE
+    if ops_capacity is None:
+        ops_capacity = int(_cigar_call(a, n_rows, cigar, cigar_payload, cigar_payload_base, cigar_payload_bytes).total_ops)
+    cap = int(ops_capacity)
+    entries = torch.empty((max(n_rows, 1), 2), dtype=torch.int64, device=dev)
+    op = torch.empty((max(cap, 1), 2), dtype=torch.int64, device=dev)
+    length = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
+    a.d_out_entries, a.d_out_op, a.d_out_len, a.ops_capacity = entries.data_ptr(), op.data_ptr(), length.data_ptr(), cap
+    r = _cigar_call(a, n_rows, cigar, cigar_payload, cigar_payload_base, cigar_payload_bytes)
+    k = min(int(r.total_ops), cap)
+    return entries[:n_rows], op[:k], length[:k], r
+
+
+def extract_from_cigar(sequence, sequence_payload, sequence_payload_base, cigar, cigar_payload, cigar_payload_base, n_rows,
+                       cigar_payload_bytes=None):
+    """extract_from_cigar (reference sam_functions/module.cpp:79-131) on the sequence and cigar columns of a scan that are still
+    in HBM ([cap, 2] int64 tensors of string_t, each with the buffer its pointers address).  Returns (start [n_rows] int32, end
+    [n_rows] int32, slices [n_rows, 2] int64 = string_t, result): a slice of up to 12 bytes is inlined, a longer one points into
+    the caller's sequence payload (sequence_payload_base + offset).  An invalid row raises ExgError."""
+    torch = _torch()
+    dev = cigar.device
+    a = abi.CigarOpArgs()
+    a.op = abi.EXG_CIGAR_EXTRACT
+    a.d_sequence = sequence.data_ptr()
+    a.d_sequence_payload = sequence_payload.data_ptr() if sequence_payload is not None else None
+    a.sequence_payload_base = sequence_payload_base
+    start = torch.empty(max(n_rows, 1), dtype=torch.int32, device=dev)
+    end = torch.empty(max(n_rows, 1), dtype=torch.int32, device=dev)
+    slices = torch.empty((max(n_rows, 1), 2), dtype=torch.int64, device=dev)
+    a.d_out_start, a.d_out_end, a.d_out_sequence = start.data_ptr(), end.data_ptr(), slices.data_ptr()
+    r = _cigar_call(a, n_rows, cigar, cigar_payload, cigar_payload_base, cigar_payload_bytes)
+    return start[:n_rows], end[:n_rows], slices[:n_rows], r
+
+
 class VcfScan:
     """Reusable output + workspace buffers for exg_vcf_scan."""
 

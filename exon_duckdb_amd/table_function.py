@@ -425,6 +425,43 @@ def gc_content(s):
     return _sequence_fn(abi.EXG_SEQ_GC_CONTENT, s)
 
 
+def _cigar_error(rc, code, offset, err):
+    e = ExgError(rc, err.value.decode("latin-1"))
+    e.parse_code, e.offset = code.value, offset.value    # abi.EXG_PE_CIGAR_*, and where a left-to-right parser stops
+    return e
+
+
+def parse_cigar(s):
+    """the SQL scalar parse_cigar(VARCHAR) -> LIST(STRUCT(op VARCHAR, len INTEGER)) as the DuckDB shim registers it (reference
+    sam_functions/module.cpp:32-77) -> list of {"op", "len"}; the empty string and `*` give []; NULL in, NULL out; an invalid
+    row raises ExgError with `Invalid CIGAR string: <text>` (.parse_code, .offset: the rule of csrc/exg_cigarfn.hpp)"""
+    if s is None:
+        return None
+    cap = max(1, len(s) // 2)
+    ops, lens = C.create_string_buffer(cap), (C.c_int32 * cap)()
+    n_ops, code, offset, err = C.c_uint64(0), C.c_uint32(0), C.c_uint64(0), C.create_string_buffer(len(s) + 64)
+    rc = _lib().exon_tf_parse_cigar(s, len(s), ops, lens, cap, C.byref(n_ops), C.byref(code), C.byref(offset), err, len(err))
+    if rc != 0:
+        raise _cigar_error(rc, code, offset, err)
+    return [{"op": ops.raw[k:k + 1].decode("latin-1"), "len": lens[k]} for k in range(n_ops.value)]
+
+
+def extract_from_cigar(sequence, cigar):
+    """the SQL scalar extract_from_cigar(VARCHAR, VARCHAR) -> STRUCT(sequence_start INTEGER, sequence_end INTEGER, sequence
+    VARCHAR) as the shim registers it (reference sam_functions/module.cpp:79-131): the sequence without a leading and a
+    trailing insertion.  NULL in either argument, NULL out; an invalid CIGAR raises ExgError (`Invalid CIGAR string`), so do
+    insertions that exceed the sequence"""
+    if sequence is None or cigar is None:
+        return None
+    start, end = C.c_int32(0), C.c_int32(0)
+    code, offset, err = C.c_uint32(0), C.c_uint64(0), C.create_string_buffer(128)
+    rc = _lib().exon_tf_extract_from_cigar(len(sequence), cigar, len(cigar), C.byref(start), C.byref(end), C.byref(code), C.byref(offset),
+                                           err, len(err))
+    if rc != 0:
+        raise _cigar_error(rc, code, offset, err)
+    return {"sequence_start": start.value, "sequence_end": end.value, "sequence": sequence[start.value:end.value]}
+
+
 #: the SAM flag predicates in the reference's order (sam_functions/module.cpp:143-154): bit k of (uint16_t)flag
 SAM_FLAG_FUNCTIONS = ("is_segmented", "is_properly_aligned", "is_unmapped", "is_mate_unmapped", "is_reverse_complemented",
                       "is_mate_reverse_complemented", "is_first_segment", "is_last_segment", "is_secondary",

@@ -45,7 +45,8 @@ extern "C" {
 
 /* 9 still: read_bed_file (EXG_FMT_BED, exg_bed_scan, EXG_PE_BED_*), the sequence scalars (exg_sequence_op,
  * EXG_SEQ_*, EXG_PE_SEQ_*), the alignment scores (exg_align_score, EXG_PE_ALIGN_TOO_LONG) and read_sam_file_records
- * (EXG_FMT_SAM, exg_sam_scan, EXG_PE_SAM_*) are pure additions — no existing struct, constant or entry point changed. */
+ * (EXG_FMT_SAM, exg_sam_scan, EXG_PE_SAM_*) and the CIGAR scalars (exg_cigar_op, EXG_CIGAR_*, EXG_PE_CIGAR_*) are pure additions — no
+ * existing struct, constant or entry point changed. */
 #define EXG_ABI_VERSION 9
 
 /* DuckDB v0.8.1 STANDARD_VECTOR_SIZE; the reference asks the Rust side for
@@ -109,6 +110,9 @@ extern "C" {
 #define EXG_PE_SAM_MAPQ 40            /* SAM: MAPQ is not made of digits only, or above 255 */
 #define EXG_PE_SAM_CIGAR 41           /* SAM: CIGAR is neither `*` nor [digits, one of MIDNSHP=X]+ with lengths <= 2^28 - 1 */
 #define EXG_PE_SAM_LENGTHS 42         /* SAM: SEQ and QUAL are both present and differ in length */
+/* (43 stays unassigned, like 29 and 34: callers probe it to see "unknown parse error") */
+#define EXG_PE_CIGAR_INVALID 44       /* CIGAR scalars: a row is not [digits, one of MIDNSHP=X]+ with lengths <= 2^28 - 1 */
+#define EXG_PE_CIGAR_RANGE 45         /* extract_from_cigar: the leading and trailing insertions exceed the sequence */
 
 /* ---- duckdb::string_t, bit-for-bit (v0.8.1 duckdb/common/types/string_type.hpp)
  * length <= 12: bytes inlined, zero padded.  Otherwise 4-byte prefix + pointer.
@@ -540,6 +544,74 @@ int exg_align_score(const exg_align_score_args *args);
 /* Synchronising copy of the 64-byte result to the host.  error_code != 0: EXG_E_PARSE, and the thread's last error message is
  * `Alignment pair too long: <n> bytes (at most <max_pair_bytes>) in row <r>`; *out is filled either way. */
 int exg_align_result(const exg_align_score_result *d_result, void *stream, exg_align_score_result *out);
+
+/* ---- CIGAR scalars on device-resident columns -------------------------------------------------------------
+ * parse_cigar(VARCHAR) -> LIST(STRUCT(op VARCHAR, len INTEGER)) and extract_from_cigar(VARCHAR, VARCHAR) ->
+ * STRUCT(sequence_start INTEGER, sequence_end INTEGER, sequence VARCHAR) of exon/src/exon/sam_functions/module.cpp:32-131 for
+ * the cigar (and sequence) column a BAM or SAM scan just wrote.  The rules are stated once, in
+ * exon_duckdb_amd/csrc/exg_cigarfn.hpp ("CIGAR scalars"): a row is [digits, one of MIDNSHP=X]+ with every
+ * length <= 2^28 - 1 in value; the empty string and `*` are the CIGAR without operations.
+ *
+ * Input: exg_string_t[n_rows] columns as the scans leave them (up to 12 bytes inlined, longer strings at payload_base + offset
+ * in their payload at any alignment); a NULL row = 16 zero bytes = the empty string.  n_rows < 2^32 - 1.
+ * PARSE: the two children hold the operations of all rows in row order without gaps: d_out_op[k] is an inlined string_t of
+ * length 1 (the letter, eleven zero bytes behind it), d_out_len[k] the length; d_out_entries[r] = {operations in front of row
+ * r, operations of row r}, also for a row without any.  total_ops > ops_capacity: EXG_RF_CAPACITY, neither child is touched,
+ * total_ops is exact and the rows are validated all the same; ops_capacity = 0 with NULL children is the counting call of a
+ * two-call protocol.  total_ops counts every operation letter, those of a failing row too.
+ * EXTRACT: start = the first operation's length if it is I, else 0; end = |sequence| - the last operation's length if it is
+ * I, else |sequence| ({0, |sequence|} for the CIGAR without operations); d_out_sequence[r] is the slice [start, end): up to
+ * 12 bytes inlined and zero padded, a longer one {length, its first four bytes, the input's ptr + start} — a zero-copy slice
+ * of the caller's sequence payload under the same sequence_payload_base.  No output payload.
+ * Errors: the lowest failing row wins; in it the leftmost offset at which a left-to-right parser stops (a bad byte or an
+ * operation letter without digits: its offset; digits up to the end of the row: the row's length; a length above the bound:
+ * the digit at which the value first exceeds it), then — EXTRACT — the range error (start > end, or |sequence| > 2^31 - 1).
+ * With an error the result block is exact and the outputs are unspecified.  Deterministic: byte-identical outputs for
+ * identical inputs.  No host round trip between the passes; n_rows = 0 is valid.
+ * (`exg_cigar_result` names the struct as a tag and the function: write `struct exg_cigar_result`.) */
+#define EXG_CIGAR_PARSE 1
+#define EXG_CIGAR_EXTRACT 2
+struct exg_cigar_result { /* 64 bytes, written by the device */
+    uint64_t total_ops;    /* PARSE: operations of all rows; 0 for EXTRACT */
+    uint64_t error_row;    /* lowest failing row */
+    uint64_t error_offset; /* EXG_PE_CIGAR_INVALID: the byte offset in that row's CIGAR (the row's length: digits up to its end) */
+    uint64_t n_rows;
+    uint32_t error_code;   /* 0, EXG_PE_CIGAR_INVALID or EXG_PE_CIGAR_RANGE */
+    uint32_t flags;        /* EXG_RF_CAPACITY: total_ops > ops_capacity, no child was written; EXG_RF_INDEX_OVERFLOW: the rows
+                            * longer than 12 bytes hold more bytes than the workspace was sized for — nothing was done */
+    uint8_t error_byte;    /* the byte at error_offset (0 when that is the row's length) */
+    uint8_t pad[23];
+};
+typedef struct exg_cigar_op_args {
+    uint32_t op;                      /* EXG_CIGAR_* */
+    const exg_string_t *d_cigar;      /* device, 16-byte aligned, n_rows entries */
+    const void *d_cigar_payload;      /* device bytes the non-inlined CIGARs point into */
+    uint64_t cigar_payload_base;      /* string_t.ptr - cigar_payload_base = byte offset in d_cigar_payload */
+    const exg_string_t *d_sequence;   /* EXTRACT: device, 16-byte aligned, n_rows entries */
+    const void *d_sequence_payload;   /* EXTRACT: device bytes the non-inlined sequences point into */
+    uint64_t sequence_payload_base;
+    uint64_t n_rows;
+    exg_list_entry_t *d_out_entries;  /* PARSE, out: device, 8-byte aligned, n_rows entries (may be NULL in the counting call) */
+    exg_string_t *d_out_op;           /* PARSE, out: device, 16-byte aligned, ops_capacity entries */
+    int32_t *d_out_len;               /* PARSE, out: device, 4-byte aligned, ops_capacity entries */
+    uint64_t ops_capacity;
+    int32_t *d_out_start;             /* EXTRACT, out: device, n_rows entries */
+    int32_t *d_out_end;               /* EXTRACT, out: device, n_rows entries */
+    exg_string_t *d_out_sequence;     /* EXTRACT, out: device, 16-byte aligned, n_rows entries */
+    void *d_workspace;                /* device, 8-byte aligned, exg_cigar_workspace_bytes(...) */
+    uint64_t workspace_bytes;
+    struct exg_cigar_result *d_result; /* device, 64 bytes, 8-byte aligned */
+    void *stream;
+} exg_cigar_op_args;
+/* cigar_payload_bytes: an upper bound of the summed lengths of the rows longer than 12 bytes — the size of the buffer
+ * d_cigar_payload points into, unless rows share bytes (PARSE keeps one counter per 4 KiB of them; EXTRACT ignores it). */
+uint64_t exg_cigar_workspace_bytes(uint32_t op, uint64_t n_rows, uint64_t cigar_payload_bytes);
+/* Enqueue on args->stream; asynchronous. */
+int exg_cigar_op(const exg_cigar_op_args *args);
+/* Synchronising copy of the 64-byte result to the host.  error_code != 0: EXG_E_PARSE, and the thread's last error message
+ * is `Invalid CIGAR string in row <r> at byte <k>` or `CIGAR insertions exceed the sequence in row <r>`; *out is filled
+ * either way. */
+int exg_cigar_result(const struct exg_cigar_result *d_result, void *stream, struct exg_cigar_result *out);
 
 /* ---- device inflate (gzip / BGZF members; replaces flate2 behind rust/src/arrow_reader.rs:60-91) ---- */
 typedef struct exg_inflate_member {
