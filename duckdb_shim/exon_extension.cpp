@@ -385,6 +385,68 @@ static void RegisterAlignmentScore(DatabaseInstance &db, const char *name) {
 	Catalog::GetSystemCatalog(db).CreateFunction(CatalogTransaction::GetSystemTransaction(db), info);
 }
 
+// alignment_functions/module.cpp:150-247: alignment_string / alignment_string_wfa_gap_affine -> VARCHAR in the same three
+// forms, on the host scalar exon_scan::AlignmentString: the run-length CIGAR of the optimum that the backtrace rule of
+// csrc/exg_alignfn.hpp picks.  The checks (AlignmentStringBindError: the reference's texts; a match score below 0 is folded into
+// the penalties) run per row, exactly as AlignmentScoreFunction makes them.  NULL in any argument, NULL out.
+static void AlignmentStringFunction(idx_t n_args, DataChunk &args, Vector &result) {
+	const idx_t count = args.size();
+	UnifiedVectorFormat in[7];
+	for (idx_t c = 0; c < n_args; c++) {
+		args.data[c].ToUnifiedFormat(count, in[c]);
+	}
+	result.SetVectorType(VectorType::FLAT_VECTOR);
+	auto out = FlatVector::GetData<string_t>(result);
+	const idx_t first = n_args == 7 ? 3 : 2; // the column of `mismatch`
+	std::string cigar;
+	for (idx_t i = 0; i < count; i++) {
+		bool valid = true;
+		idx_t k[7];
+		for (idx_t c = 0; c < n_args; c++) {
+			k[c] = in[c].sel->get_index(i);
+			valid = valid && in[c].validity.RowIsValid(k[c]);
+		}
+		if (!valid) {
+			FlatVector::SetNull(result, i, true);
+			continue;
+		}
+		exon_scan::AlignmentParams prm;
+		if (n_args > 2) {
+			auto integer = [&](idx_t c) { return (int64_t) reinterpret_cast<const int32_t *>(in[c].data)[k[c]]; };
+			const string_t &model = reinterpret_cast<const string_t *>(in[n_args - 1].data)[k[n_args - 1]];
+			const std::string msg = exon_scan::AlignmentStringBindError(n_args == 7, n_args == 7 ? integer(2) : 0, integer(first), integer(first + 1),
+			                                                            integer(first + 2), model.GetData(), model.GetSize(), &prm);
+			if (!msg.empty()) {
+				throw InvalidInputException(msg);
+			}
+		}
+		const string_t &text = reinterpret_cast<const string_t *>(in[0].data)[k[0]];
+		const string_t &pattern = reinterpret_cast<const string_t *>(in[1].data)[k[1]];
+		const int rc = exon_scan::AlignmentString(text.GetData(), text.GetSize(), pattern.GetData(), pattern.GetSize(), prm, &cigar);
+		if (rc == EXG_E_NOMEM) {
+			throw InvalidInputException(exg::alignfn::kHistoryLimitText);
+		}
+		if (rc != EXG_OK) {
+			throw InvalidInputException("alignment_string: the pair is longer than 2^21 bytes");
+		}
+		out[i] = StringVector::AddString(result, cigar.data(), cigar.size());
+	}
+}
+
+// exon_extension.cpp:82-91: both names, each a set of the three signatures of the score, returning VARCHAR
+static void RegisterAlignmentString(DatabaseInstance &db, const char *name) {
+	ScalarFunctionSet set(name);
+	const LogicalType V = LogicalType::VARCHAR, I = LogicalType::INTEGER;
+	const vector<LogicalType> forms[] = {{V, V}, {V, V, I, I, I, V}, {V, V, I, I, I, I, V}};
+	for (const auto &arguments : forms) {
+		const idx_t n_args = arguments.size();
+		set.AddFunction(ScalarFunction(name, arguments, LogicalType::VARCHAR,
+		                               [n_args](DataChunk &args, ExpressionState &, Vector &result) { AlignmentStringFunction(n_args, args, result); }));
+	}
+	CreateScalarFunctionInfo info(std::move(set));
+	Catalog::GetSystemCatalog(db).CreateFunction(CatalogTransaction::GetSystemTransaction(db), info);
+}
+
 // sam_functions/module.cpp:32-77: parse_cigar(VARCHAR) -> LIST(STRUCT(op VARCHAR, len INTEGER)) on the host scalar
 // exon_scan::ParseCigar over the rules of csrc/exg_cigarfn.hpp.  The list entries, the two STRUCT children and the one-letter
 // strings are written directly, as QualityScoreStringToList writes its list.  The empty string and `*` give an empty list
@@ -456,11 +518,13 @@ static void ExtractFromCigarFunction(DataChunk &args, ExpressionState &, Vector 
 	}
 }
 
-// exon_extension.cpp:62-73, :81-93: the sequence scalars, the flag predicates, the alignment scores and the two CIGAR scalars
-// (gff_parse_attributes and alignment_string* are not registered: INTEGRATION.md)
+// exon_extension.cpp:62-73, :81-93: the sequence scalars, the flag predicates, the alignment scores and strings and the two
+// CIGAR scalars (gff_parse_attributes is not registered: INTEGRATION.md)
 static void RegisterScalars(DatabaseInstance &db) {
 	RegisterAlignmentScore(db, "alignment_score");
 	RegisterAlignmentScore(db, "alignment_score_wfa_gap_affine");
+	RegisterAlignmentString(db, "alignment_string");
+	RegisterAlignmentString(db, "alignment_string_wfa_gap_affine");
 	static const struct {
 		const char *name;
 		uint32_t op;

@@ -311,6 +311,49 @@ class AlignScoreArgs(C.Structure):
     ]
 
 
+class AlignStringResult(C.Structure):
+    _fields_ = [
+        ("n_capped", C.c_uint64),
+        ("error_row", C.c_uint64),
+        ("error_length", C.c_uint64),
+        ("error_limit", C.c_uint64),
+        ("n_global", C.c_uint64),
+        ("out_bytes", C.c_uint64),
+        ("error_code", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("out_capacity", C.c_uint64),
+    ]
+
+
+class AlignStringArgs(C.Structure):
+    _fields_ = [
+        ("d_text", C.c_void_p),
+        ("d_text_payload", C.c_void_p),
+        ("text_payload_base", C.c_uint64),
+        ("d_pattern", C.c_void_p),
+        ("d_pattern_payload", C.c_void_p),
+        ("pattern_payload_base", C.c_uint64),
+        ("n_rows", C.c_uint64),
+        ("mismatch", C.c_uint32),
+        ("gap_opening", C.c_uint32),
+        ("gap_extension", C.c_uint32),
+        ("max_penalty", C.c_uint32),
+        ("max_pair_bytes", C.c_uint64),
+        ("d_out_strings", C.c_void_p),
+        ("d_out_payload", C.c_void_p),
+        ("out_capacity", C.c_uint64),
+        ("out_payload_base", C.c_uint64),
+        ("d_out_score", C.c_void_p),
+        ("d_out_valid", C.c_void_p),
+        ("d_workspace", C.c_void_p),
+        ("workspace_bytes", C.c_uint64),
+        ("d_result", C.c_void_p),
+        ("stream", C.c_void_p),
+        ("lanes", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
 class CigarResult(C.Structure):
     _fields_ = [
         ("total_ops", C.c_uint64),
@@ -391,6 +434,9 @@ SIGNATURES = {
     "exg_align_workspace_bytes": (C.c_uint64, [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32]),
     "exg_align_score": (C.c_int, [C.POINTER(AlignScoreArgs)]),
     "exg_align_result": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(AlignScoreResult)]),
+    "exg_align_string_workspace_bytes": (C.c_uint64, [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64]),
+    "exg_align_string": (C.c_int, [C.POINTER(AlignStringArgs)]),
+    "exg_align_string_result": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(AlignStringResult)]),
     "exg_cigar_workspace_bytes": (C.c_uint64, [C.c_uint32, C.c_uint64, C.c_uint64]),
     "exg_cigar_op": (C.c_int, [C.POINTER(CigarOpArgs)]),
     "exg_cigar_result": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(CigarResult)]),
@@ -434,6 +480,10 @@ TEST_SIGNATURES = {
     "exon_tf_alignment_score_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "exon_tf_alignment_score": (C.c_int, [C.c_int, C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
                                           C.c_char_p, C.c_uint64, C.POINTER(C.c_float), C.c_char_p, C.c_uint64]),
+    "exon_tf_alignment_string": (C.c_int, [C.c_int, C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                                           C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_char_p, C.c_uint64]),
+    "exon_tf_alignment_string_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_int32, C.c_int32,
+                                                 C.c_void_p, C.c_uint64, C.c_void_p]),
     "exon_tf_parse_cigar": (C.c_int, [C.c_char_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32),
                                       C.POINTER(C.c_uint64), C.c_char_p, C.c_uint64]),
     "exon_tf_extract_from_cigar": (C.c_int, [C.c_uint64, C.c_char_p, C.c_uint64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_uint32),

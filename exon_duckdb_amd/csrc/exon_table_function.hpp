@@ -446,6 +446,94 @@ static inline int AlignmentScore(const char *text, size_t n_, const char *patter
     return EXG_E_INVALID_ARG;  // (unreachable: the bound is an alignment's penalty)
 }
 
+// alignment_string / alignment_string_wfa_gap_affine (exon/src/exon/alignment_functions/module.cpp:150-247): the run-length
+// CIGAR of ONE optimal global gap-affine alignment, chosen by the backtrace rule of exg_alignfn.hpp (exg_align_string is the
+// same on two scan columns that are still in HBM).  The bind-time checks of the SQL forms; unlike the score, a match score
+// below 0 is folded into the penalties, and *prm gets the penalties the rule runs on.  "" or the exception's text.
+static inline std::string AlignmentStringBindError(bool has_match, int64_t match, int64_t mismatch, int64_t gap_opening, int64_t gap_extension,
+                                                   const char *memory_model, size_t memory_model_len, AlignmentParams *prm) {
+    namespace af = exg::alignfn;
+    if (has_match && match > 0) return af::kMatchPositiveText;
+    if (!af::params_ok(mismatch, gap_opening, gap_extension)) return af::kStringParamRangeText;
+    if (has_match && match < -af::kMaxParam) return af::kStringParamRangeText;  // no folded gap_extension passes; the products below stay small
+    const int64_t a = has_match ? match : 0;
+    const int64_t x = a ? af::fold_mismatch(a, mismatch) : mismatch, o = a ? af::fold_gap_opening(a, gap_opening) : gap_opening,
+                  e = a ? af::fold_gap_extension(a, gap_extension) : gap_extension;
+    if (!af::params_ok(x, o, e)) return af::kStringParamRangeText;
+    if (!af::memory_model_ok(memory_model, memory_model_len)) return std::string(af::kMemoryModelPrefix) + std::string(memory_model, memory_model_len);
+    prm->mismatch = (int32_t)x, prm->gap_opening = (int32_t)o, prm->gap_extension = (int32_t)e;
+    return std::string();
+}
+// EXG_OK and *out (emptied first); EXG_E_INVALID_ARG for parameters outside their limits, EXG_E_CAPACITY for a pair longer than
+// exg::alignfn::kMaxPairBytes, EXG_E_NOMEM when the kept wavefronts would pass 1 GiB (kHistoryLimitText).  The forward loop is
+// AlignmentScore's with every step's visited diagonals kept: M after extend, I and D, as the reference's memory_high keeps them.
+static inline int AlignmentString(const char *text, size_t n_, const char *pattern, size_t m_, const AlignmentParams &prm, std::string *out) {
+    namespace af = exg::alignfn;
+    out->clear();
+    if (!af::params_ok(prm.mismatch, prm.gap_opening, prm.gap_extension)) return EXG_E_INVALID_ARG;
+    if ((uint64_t)n_ + (uint64_t)m_ > af::kMaxPairBytes) return EXG_E_CAPACITY;
+    const int32_t n = (int32_t)n_, m = (int32_t)m_;
+    const int32_t x = prm.mismatch, o = prm.gap_opening, e = prm.gap_extension;
+    const int32_t nd = n + m + 1;
+    const int32_t bound = (int32_t)af::penalty_bound(o, e, n, m);
+    struct Step {
+        int32_t from, width;
+        std::vector<int32_t> v;  // M | I | D, `width` entries each
+    };
+    struct History {
+        std::vector<Step> steps;
+        int32_t m;
+        int32_t at(int32_t s, int32_t k, int32_t plane) const {
+            if (s < 0) return af::kNone;
+            const Step &st = steps[(size_t)s];
+            const int32_t d = k + m - st.from;
+            return d < 0 || d >= st.width ? af::kNone : st.v[(size_t)plane * st.width + d];
+        }
+    } hist;
+    struct View {
+        const History *h;
+        int32_t m(int32_t s, int32_t k) const { return h->at(s, k, 0); }
+        int32_t i(int32_t s, int32_t k) const { return h->at(s, k, 1); }
+        int32_t d(int32_t s, int32_t k) const { return h->at(s, k, 2); }
+    };
+    hist.m = m;
+    auto extend = [&](int32_t h, int32_t k) {
+        int32_t v = h - k;
+        while (h < n && v < m && text[h] == pattern[v]) h++, v++;
+        return h;
+    };
+    const View w{&hist};
+    uint64_t kept = 0;
+    int32_t lo = m, hi = m, penalty = -1;
+    for (int32_t s = 0; s <= bound && penalty < 0; s++) {
+        const int32_t from = s ? (lo > 0 ? lo - 1 : 0) : m, to = s ? (hi < nd - 1 ? hi + 1 : nd - 1) : m;
+        Step st;
+        st.from = from, st.width = to - from + 1;
+        kept += 12ull * st.width + sizeof(Step);
+        if (kept > af::kHostHistoryBytes) return EXG_E_NOMEM;
+        st.v.assign((size_t)3 * st.width, af::kNone);
+        for (int32_t d = from; d <= to; d++) {
+            const int32_t k = d - m;
+            af::Cell c = af::cell(w.m(s - o - e, k - 1), w.i(s - e, k - 1), w.m(s - o - e, k + 1), w.d(s - e, k + 1), w.m(s - x, k), k, n, m);
+            if (!s) c.m = 0;
+            if (c.m >= 0) {
+                c.m = extend(c.m, k);
+                lo = d < lo ? d : lo, hi = d > hi ? d : hi;
+            }
+            st.v[(size_t)(d - from)] = c.m, st.v[(size_t)st.width + (d - from)] = c.i, st.v[(size_t)2 * st.width + (d - from)] = c.d;
+        }
+        hist.steps.push_back(std::move(st));
+        if (w.m(s, n - m) >= n) penalty = s;
+    }
+    if (penalty < 0) return EXG_E_INVALID_ARG;  // (unreachable: the bound is an alignment's penalty)
+    std::vector<uint8_t> buf(2 * ((size_t)n + m) + 16);
+    af::RunWriter rw{buf.data() + buf.size(), buf.data(), 0, 0, false};
+    if (!af::backtrace(w, penalty, x, o, e, n, m, &rw)) return EXG_E_INVALID_ARG;  // (unreachable: the history is the forward pass's)
+    const uint8_t *begin = rw.finish();
+    out->assign(reinterpret_cast<const char *>(begin), (size_t)(buf.data() + buf.size() - begin));
+    return EXG_OK;
+}
+
 // parse_cigar / extract_from_cigar (exon/src/exon/sam_functions/module.cpp:32-131, rust/src/sam_functions.rs:114-200): the
 // per-row arithmetic of the SQL scalars the shim registers, on the rules of exg_cigarfn.hpp (exg_cigar_op is the same on scan
 // columns that are still in HBM).  A status instead of an exception, like SequenceMap.

@@ -275,6 +275,57 @@ extern "C" int exon_tf_alignment_score_batch(const char *texts, const uint64_t *
     }
     return EXG_OK;
 }
+// alignment_string / alignment_string_wfa_gap_affine as the shim registers them (alignment_functions/module.cpp:150-247), in
+// the same three forms.  0, the CIGAR in out and its length in *out_len; EXG_E_CAPACITY when out_cap is too small (*out_len =
+// what it takes); EXG_E_INVALID_ARG with the exception's text in err
+extern "C" int exon_tf_alignment_string(int n_args, const char *text, uint64_t n, const char *pattern, uint64_t m, int64_t match,
+                                        int64_t mismatch, int64_t gap_opening, int64_t gap_extension, const char *memory_model,
+                                        uint64_t memory_model_len, char *out, uint64_t out_cap, uint64_t *out_len, char *err, uint64_t err_cap) {
+    if (err_cap) err[0] = 0;
+    *out_len = 0;
+    auto fail = [&](const std::string &msg) {
+        if (err_cap) snprintf(err, (size_t)err_cap, "%s", msg.c_str());
+        return EXG_E_INVALID_ARG;
+    };
+    exon_scan::AlignmentParams prm;
+    if (n_args == 6 || n_args == 7) {
+        const std::string msg = exon_scan::AlignmentStringBindError(n_args == 7, match, mismatch, gap_opening, gap_extension, memory_model,
+                                                                    (size_t)memory_model_len, &prm);
+        if (!msg.empty()) return fail(msg);
+    } else if (n_args != 2) {
+        return fail("Invalid number of arguments for align function");
+    }
+    std::string cigar;
+    const int rc = exon_scan::AlignmentString(text, (size_t)n, pattern, (size_t)m, prm, &cigar);
+    if (rc == EXG_E_CAPACITY) return fail("alignment_string: the pair is longer than 2^21 bytes");
+    if (rc == EXG_E_NOMEM) return fail(exg::alignfn::kHistoryLimitText);
+    if (rc != EXG_OK) return rc;
+    *out_len = cigar.size();
+    if (cigar.size() > out_cap) return EXG_E_CAPACITY;
+    memcpy(out, cigar.data(), cigar.size());
+    return EXG_OK;
+}
+// the same host scalar over n pairs in one call (tools/alignstr_bench.py times it): the CIGARs behind one another in out,
+// out_off[i] .. out_off[i + 1]; EXG_E_CAPACITY when out_cap is too small
+extern "C" int exon_tf_alignment_string_batch(const char *texts, const uint64_t *t_off, const char *patterns, const uint64_t *p_off, uint64_t n,
+                                              int32_t mismatch, int32_t gap_opening, int32_t gap_extension, char *out, uint64_t out_cap,
+                                              uint64_t *out_off) {
+    exon_scan::AlignmentParams prm;
+    prm.mismatch = mismatch, prm.gap_opening = gap_opening, prm.gap_extension = gap_extension;
+    std::string cigar;
+    uint64_t at = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        const int rc = exon_scan::AlignmentString(texts + t_off[i], (size_t)(t_off[i + 1] - t_off[i]), patterns + p_off[i],
+                                                  (size_t)(p_off[i + 1] - p_off[i]), prm, &cigar);
+        if (rc != EXG_OK) return rc;
+        out_off[i] = at;
+        if (at + cigar.size() > out_cap) return EXG_E_CAPACITY;
+        memcpy(out + at, cigar.data(), cigar.size());
+        at += cigar.size();
+    }
+    out_off[n] = at;
+    return EXG_OK;
+}
 static int cigar_failure(const exon_scan::CigarStatus &st, const std::string &text, uint32_t *code, uint64_t *offset, char *err, uint64_t err_cap) {
     *code = st.code, *offset = st.offset;
     if (err_cap) snprintf(err, (size_t)err_cap, "%s", text.c_str());

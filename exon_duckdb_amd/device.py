@@ -226,6 +226,51 @@ def align_score(text, text_payload, text_payload_base, pattern, pattern_payload,
     return scores[:n_rows], r
 
 
+ALIGN_OUT_BASE = 1 << 47   # string_t.ptr of align_string's out-of-line rows = ALIGN_OUT_BASE + offset in out_payload
+
+
+def align_string(text, text_payload, text_payload_base, pattern, pattern_payload, pattern_payload_base, n_rows, max_pair_bytes,
+                 out_capacity, mismatch=4, gap_opening=6, gap_extension=2, max_penalty=0, valid=None, lanes=0, want_score=False):
+    """alignment_string / alignment_string_wfa_gap_affine (reference alignment_functions/module.cpp:150-247) on two VARCHAR
+    columns that are still in HBM, addressed as in align_score.  Returns (out_strings [n_rows, 2] int64 = string_t, out_payload
+    uint8, scores [n_rows] float32 or None, result): the run-length CIGAR of the optimal global alignment that the backtrace rule
+    of csrc/exg_alignfn.hpp picks; a CIGAR longer than 12 bytes points at ALIGN_OUT_BASE + offset in out_payload, the offsets
+    being the prefix sums of the long rows' lengths.  out_capacity = 2 * (the bytes of both columns) never overflows; a smaller
+    one that does raises ExgError (EXG_E_CAPACITY) naming result.out_bytes.  The workspace grows with the square of the largest
+    penalty a row may reach: give long pairs a max_penalty.  A row above it is NULL (16 zero bytes), its bit cleared in `valid`
+    and counted in result.n_capped.  A row with |text| + |pattern| > max_pair_bytes raises ExgError naming the lowest such row."""
+    torch = _torch()
+    lib = load_library()
+    dev = text.device
+    a = abi.AlignStringArgs()
+    a.d_text, a.d_pattern = text.data_ptr(), pattern.data_ptr()
+    a.d_text_payload = text_payload.data_ptr() if text_payload is not None else None
+    a.d_pattern_payload = pattern_payload.data_ptr() if pattern_payload is not None else None
+    a.text_payload_base, a.pattern_payload_base = text_payload_base, pattern_payload_base
+    a.n_rows = n_rows
+    a.mismatch, a.gap_opening, a.gap_extension = mismatch, gap_opening, gap_extension
+    a.max_penalty, a.max_pair_bytes, a.lanes = max_penalty, max_pair_bytes, lanes
+    out_strings = torch.empty((max(n_rows, 1), 2), dtype=torch.int64, device=dev)
+    out_payload = torch.empty(max(int(out_capacity), 16), dtype=torch.uint8, device=dev)
+    scores = torch.empty(max(n_rows, 1), dtype=torch.float32, device=dev) if want_score else None
+    a.d_out_strings, a.d_out_payload = out_strings.data_ptr(), out_payload.data_ptr()
+    a.out_capacity, a.out_payload_base = int(out_capacity), ALIGN_OUT_BASE
+    a.d_out_score = scores.data_ptr() if want_score else None
+    a.d_out_valid = valid.data_ptr() if valid is not None else None
+    ws_bytes = int(lib.exg_align_string_workspace_bytes(n_rows, max_pair_bytes, mismatch, gap_opening, gap_extension, max_penalty, int(out_capacity)))
+    if not ws_bytes:
+        raise ExgError(abi.EXG_E_INVALID_ARG, "align_string: parameters out of range, or a wavefront history above 2^48 bytes (set max_penalty)")
+    ws = torch.empty(ws_bytes // 8 + 2, dtype=torch.int64, device=dev)
+    result = torch.empty(8, dtype=torch.int64, device=dev)
+    a.d_workspace, a.workspace_bytes = ws.data_ptr(), ws_bytes
+    a.d_result = result.data_ptr()
+    a.stream = stream_ptr().value
+    check(lib.exg_align_string(C.byref(a)))
+    r = abi.AlignStringResult()
+    check(lib.exg_align_string_result(C.c_void_p(result.data_ptr()), stream_ptr(), C.byref(r)))
+    return out_strings[:n_rows], out_payload[:int(r.out_bytes)], (scores[:n_rows] if want_score else None), r
+
+
 def _cigar_call(a, n_rows, cigar, cigar_payload, cigar_payload_base, cigar_payload_bytes):
     """the common half of a exg_cigar_op call: the cigar column, workspace and result block; runs it and fetches the result"""
     torch = _torch()

@@ -385,6 +385,32 @@ def alignment_score(text, pattern, *args):
 alignment_score_wfa_gap_affine = alignment_score
 
 
+def alignment_string(text, pattern, *args):
+    """the SQL scalar alignment_string as the DuckDB shim registers it (reference alignment_functions/module.cpp:150-247), in
+    the three forms of alignment_score.  The run-length CIGAR (M equal, X unequal, I consumes a text byte, D a pattern byte)
+    of the optimal global gap-affine alignment that the backtrace rule of csrc/exg_alignfn.hpp picks, as bytes.  A match
+    score below 0 is folded into the penalties.  NULL in, NULL out; a bind-time error raises ExgError with the exception's
+    text."""
+    if len(args) not in (0, 4, 5):
+        raise ExgError(abi.EXG_E_INVALID_ARG, "Invalid number of arguments for align function")
+    match, (x, o, e), model = 0, (0, 0, 0), b""
+    if args:
+        match = args[0] if len(args) == 5 else 0
+        x, o, e = args[-4:-1]
+        model = args[-1].encode() if isinstance(args[-1], str) else bytes(args[-1])
+    null = text is None or pattern is None
+    t, p = (b"", b"") if null else (text, pattern)
+    out, n_out, err = C.create_string_buffer(2 * (len(t) + len(p)) + 16), C.c_uint64(0), C.create_string_buffer(320)
+    rc = _lib().exon_tf_alignment_string(2 + len(args), t, len(t), p, len(p), match, x, o, e, model, len(model), out, len(out),
+                                         C.byref(n_out), err, len(err))
+    if rc != 0:
+        raise ExgError(rc, err.value.decode("latin-1"))
+    return None if null else out.raw[:n_out.value]
+
+
+alignment_string_wfa_gap_affine = alignment_string
+
+
 def _sequence_fn(op, s):
     """one row through the host arithmetic of a sequence scalar as the DuckDB shim registers it (reference
     sequence_functions/module.cpp:30-370): NULL in, NULL out; an invalid row raises ExgError with the reference's text"""

@@ -45,8 +45,8 @@ extern "C" {
 
 /* 9 still: read_bed_file (EXG_FMT_BED, exg_bed_scan, EXG_PE_BED_*), the sequence scalars (exg_sequence_op,
  * EXG_SEQ_*, EXG_PE_SEQ_*), the alignment scores (exg_align_score, EXG_PE_ALIGN_TOO_LONG) and read_sam_file_records
- * (EXG_FMT_SAM, exg_sam_scan, EXG_PE_SAM_*) and the CIGAR scalars (exg_cigar_op, EXG_CIGAR_*, EXG_PE_CIGAR_*) are pure additions — no
- * existing struct, constant or entry point changed. */
+ * (EXG_FMT_SAM, exg_sam_scan, EXG_PE_SAM_*), the CIGAR scalars (exg_cigar_op, EXG_CIGAR_*, EXG_PE_CIGAR_*) and the alignment
+ * strings (exg_align_string; no new error code) are pure additions — no existing struct, constant or entry point changed. */
 #define EXG_ABI_VERSION 9
 
 /* DuckDB v0.8.1 STANDARD_VECTOR_SIZE; the reference asks the Rust side for
@@ -544,6 +544,72 @@ int exg_align_score(const exg_align_score_args *args);
 /* Synchronising copy of the 64-byte result to the host.  error_code != 0: EXG_E_PARSE, and the thread's last error message is
  * `Alignment pair too long: <n> bytes (at most <max_pair_bytes>) in row <r>`; *out is filled either way. */
 int exg_align_result(const exg_align_score_result *d_result, void *stream, exg_align_score_result *out);
+
+/* ---- gap-affine alignment CIGARs on device-resident columns ----------------------------------------------
+ * alignment_string / alignment_string_wfa_gap_affine of exon/src/exon/alignment_functions/module.cpp:150-247 for two VARCHAR
+ * columns that are still in HBM: the run-length CIGAR (M equal pair, X unequal pair, I consumes a text byte, D a pattern
+ * byte) of ONE optimal global alignment.  Which optimum is the backtrace rule of exon_duckdb_amd/csrc/exg_alignfn.hpp
+ * ("Alignment strings"); the result is a valid input of exg_cigar_op.  A match score below 0 is the caller's
+ * to fold into the penalties (2x - 2a, 2o, 2e - a) as the host scalar does.
+ *
+ * The input side is exg_align_score's, with the same limits and the same too-long rule (EXG_PE_ALIGN_TOO_LONG, the lowest
+ * row wins).  Output: d_out_strings[r] holds a CIGAR of up to 12 bytes inlined; a longer one has its 4-byte prefix and
+ * ptr = out_payload_base + offset, where offset is the sum of the lengths of the longer-than-12 rows in front of it — the
+ * layout is a function of the input alone, two launches are byte-identical in both arrays.  result.out_bytes is the payload
+ * the call needs, exact even on overflow; out_bytes > out_capacity is an error (exg_align_string_result: EXG_E_CAPACITY),
+ * nothing is written at or past d_out_payload + out_capacity and the strings are unspecified.  A run's text is at most twice
+ * the bytes it covers, so out_capacity = 2 * sum(|text| + |pattern|) can never overflow.
+ * A row whose optimum exceeds a non-zero max_penalty gets 16 zero bytes, its bit cleared in d_out_valid (when given),
+ * -INFINITY in d_out_score (when given) and is counted in n_capped; a row at exactly the cap keeps its CIGAR.
+ * d_out_score, optional: the float exg_align_score gives for the row.
+ * The workspace keeps every wavefront of the pairs in flight (the reference's memory_high): it grows with the square of the
+ * largest penalty a row may reach — max_penalty, or 2 * gap_opening + gap_extension * max_pair_bytes when that is 0 — so long
+ * pairs want a max_penalty.  exg_align_string_workspace_bytes returns 0 for arguments exg_align_string refuses and for a
+ * workspace above 2^48 bytes.  n_rows = 0 is valid. */
+struct exg_align_string_result { /* 64 bytes, written by the device */
+    uint64_t n_capped;      /* rows whose optimum exceeds max_penalty */
+    uint64_t error_row;     /* lowest row that is too long */
+    uint64_t error_length;  /* its |text| + |pattern| */
+    uint64_t error_limit;   /* max_pair_bytes of the call */
+    uint64_t n_global;      /* rows whose wavefront ring did not fit LDS */
+    uint64_t out_bytes;     /* payload bytes the call needs: the lengths of the CIGARs longer than 12 bytes */
+    uint32_t error_code;    /* 0 or EXG_PE_ALIGN_TOO_LONG */
+    uint32_t flags;         /* 0 (bit 0: a score loop ran into its hard bound, bit 1: a history slot filled up, bit 2: a
+                               backtrace met a contradiction — defects, never expected) */
+    uint64_t out_capacity;  /* of the call: what exg_align_string_result compares out_bytes with */
+};
+typedef struct exg_align_string_args {
+    const exg_string_t *d_text;    /* as in exg_align_score_args, up to max_pair_bytes */
+    const void *d_text_payload;
+    uint64_t text_payload_base;
+    const exg_string_t *d_pattern;
+    const void *d_pattern_payload;
+    uint64_t pattern_payload_base;
+    uint64_t n_rows;
+    uint32_t mismatch, gap_opening, gap_extension;
+    uint32_t max_penalty;          /* 0 = none */
+    uint64_t max_pair_bytes;
+    exg_string_t *d_out_strings;   /* out: device, 16-byte aligned, n_rows entries */
+    uint8_t *d_out_payload;        /* out: device, out_capacity bytes; may be NULL when out_capacity is 0 */
+    uint64_t out_capacity;
+    uint64_t out_payload_base;     /* string_t.ptr of an out-of-line CIGAR = out_payload_base + its offset in d_out_payload */
+    float *d_out_score;            /* optional: device, n_rows entries */
+    uint64_t *d_out_valid;         /* optional: device validity words; bits are cleared only */
+    void *d_workspace;             /* device, 16-byte aligned, exg_align_string_workspace_bytes(...) */
+    uint64_t workspace_bytes;
+    struct exg_align_string_result *d_result; /* device, 64 bytes, 8-byte aligned */
+    void *stream;
+    uint32_t lanes;                /* as in exg_align_score_args */
+    uint32_t reserved;             /* 0 */
+} exg_align_string_args;
+uint64_t exg_align_string_workspace_bytes(uint64_t n_rows, uint64_t max_pair_bytes, uint32_t mismatch, uint32_t gap_opening,
+                                          uint32_t gap_extension, uint32_t max_penalty, uint64_t out_capacity);
+/* Enqueue on args->stream; asynchronous. */
+int exg_align_string(const exg_align_string_args *args);
+/* Synchronising copy of the 64-byte result to the host; *out is filled either way.  error_code != 0: EXG_E_PARSE with the text
+ * of exg_align_result.  out_bytes > the call's out_capacity: EXG_E_CAPACITY, `exg_align_string: the CIGARs take <out_bytes>
+ * payload bytes, out_capacity is <out_capacity>`. */
+int exg_align_string_result(const struct exg_align_string_result *d_result, void *stream, struct exg_align_string_result *out);
 
 /* ---- CIGAR scalars on device-resident columns -------------------------------------------------------------
  * parse_cigar(VARCHAR) -> LIST(STRUCT(op VARCHAR, len INTEGER)) and extract_from_cigar(VARCHAR, VARCHAR) ->
