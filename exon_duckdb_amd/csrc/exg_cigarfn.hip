@@ -26,20 +26,16 @@
 #include "exg_common.hpp"
 #include "exg_scan.hpp"
 #include "exg_cigarfn.hpp"
+#include "exg_strcol.hpp"
 
 namespace exg {
 namespace cigarfn {
 
 static constexpr uint32_t kTile = 4096;
-static constexpr uint32_t kTileRows = kTile / (EXG_INLINE_LENGTH + 1) + 3;  // first + last + the whole rows between: <= 318
+static constexpr uint32_t kTileRows = tile_rows(kTile);  // <= 318
 static constexpr uint32_t kGrid = 8192;  // waves that take the tiles in turn: 32 a CU
 static constexpr uint32_t kRangeKey = 0xFFFFFFFFu;
 
-struct Col {
-    const uint4 *rows;
-    const uint8_t *base;
-    uint64_t payload_base;
-};
 // workspace: goff | lidx | loff | ent | lpre (n + 1 u64 each) | tpre (tiles + 1) | scan scratch | err (u64) | lrow | rowops
 // (u32 x n) | tcnt (u32 x tiles); ent, lpre, tpre, rowops and tcnt for parse_cigar only
 struct Ws {
@@ -67,10 +63,6 @@ static Ws ws_layout(uint32_t op, uint64_t n, uint64_t tiles, void *base) {
     return w;
 }
 
-__device__ __forceinline__ const uint8_t *src_of(const Col &c, uint64_t r, uint4 v) {
-    if (v.x <= EXG_INLINE_LENGTH) return reinterpret_cast<const uint8_t *>(c.rows + r) + 4;
-    return c.base + (((uint64_t)v.z | ((uint64_t)v.w << 32)) - c.payload_base);
-}
 struct LongLenF {
     Col c;
     __device__ __forceinline__ uint64_t operator()(uint64_t r) const {
@@ -114,21 +106,6 @@ __global__ __launch_bounds__(256) void k_rows(Col c, uint64_t n, Ws w, bool pars
     w.rowops[r] = letters;
     const Check ck = check(s, len);
     if (!ck.ok) atomicMin((unsigned long long *)w.err, (unsigned long long)syntax_key(r, ck.offset));
-}
-
-// largest k in [lo, hi) with a[k] <= pos, for a[lo] <= pos < a[hi]; one wave, 64 probes a round (as in exg_seqfn.hip)
-__device__ __forceinline__ uint64_t wave_search(const uint64_t *__restrict__ a, uint64_t lo, uint64_t hi, uint64_t pos) {
-    const uint32_t lane = lane_id();
-    while (hi - lo > 1) {
-        const uint64_t step = (hi - lo + 63) >> 6;
-        uint64_t idx = lo + (lane + 1) * step;
-        if (idx > hi) idx = hi;  // (a[hi] > pos: a clamped probe never counts)
-        const uint64_t c = __popcll(__ballot(a[idx] <= pos));
-        const uint64_t nh = lo + (c + 1) * step;
-        lo += c * step;
-        hi = nh < hi ? nh : hi;
-    }
-    return lo;
 }
 
 // ---- tiles: a wave each ---------------------------------------------------------------------------------------
@@ -225,14 +202,7 @@ __global__ __launch_bounds__(64) void k_tiles(Col c, uint64_t n, Ws w, bool pars
             if (lane == 0) w.tcnt[tile] = letters;
         }
     }
-    if (!kCount) {
-#pragma unroll
-        for (int dlt = 32; dlt; dlt >>= 1) {
-            const uint64_t o = __shfl_xor((unsigned long long)key, dlt, 64);
-            key = o < key ? o : key;
-        }
-        if (lane == 0 && key != kNoError) atomicMin((unsigned long long *)w.err, (unsigned long long)key);
-    }
+    if (!kCount) wave_min_error(key, w.err, lane);
 }
 
 // ---- parse_cigar, a thread per row: the list entries, and the operations of the short rows ----------------------
@@ -293,14 +263,12 @@ __global__ __launch_bounds__(256) void k_extract(Col c, Col q, uint64_t n, Ws w,
             uint32_t o[3] = {0, 0, 0};
 #pragma unroll
             for (int i = 0; i < EXG_INLINE_LENGTH; i++)
-                if ((uint32_t)i < (m > EXG_INLINE_LENGTH ? 4u : m)) o[i >> 2] |= (uint32_t)p[i] << (8 * (i & 3));
+                if ((uint32_t)i < (m > EXG_INLINE_LENGTH ? 4u : m)) put_byte(o, i, p[i]);
             out_start[r] = start, out_end[r] = end;
-            if (m > EXG_INLINE_LENGTH) {  // a slice of the caller's payload: the input's pointer + start
-                const uint64_t ptr = ((uint64_t)sv.z | ((uint64_t)sv.w << 32)) + (uint32_t)start;
-                out_seq[r] = make_uint4(m, o[0], (uint32_t)ptr, (uint32_t)(ptr >> 32));
-            } else {
-                out_seq[r] = make_uint4(m, o[0], o[1], o[2]);
-            }
+            if (m > EXG_INLINE_LENGTH)  // a slice of the caller's payload: the input's pointer + start
+                out_seq[r] = long_string(m, o[0], ((uint64_t)sv.z | ((uint64_t)sv.w << 32)) + (uint32_t)start);
+            else
+                out_seq[r] = inline_string(m, o);
         }
     }
     if (key != kNoError) atomicMin((unsigned long long *)w.err, (unsigned long long)key);
@@ -425,13 +393,7 @@ extern "C" int exg_cigar_op(const exg_cigar_op_args *a) {
 }
 
 extern "C" int exg_cigar_result(const struct exg_cigar_result *d_result, void *stream, struct exg_cigar_result *out) {
-    if (!d_result || !out) {
-        set_error("exg_cigar_result: null pointer");
-        return EXG_E_INVALID_ARG;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    EXG_HIP_CHECK(hipMemcpyAsync(out, d_result, sizeof(*out), hipMemcpyDeviceToHost, s));
-    EXG_HIP_CHECK(hipStreamSynchronize(s));
+    if (const int rc = fetch_result("exg_cigar_result", d_result, stream, out)) return rc;
     if (out->error_code) {
         char text[96];
         format_error(out->error_code, out->error_row, out->error_offset, text, sizeof text);

@@ -22,19 +22,15 @@
 #include "exg_common.hpp"
 #include "exg_scan.hpp"
 #include "exg_seqfn.hpp"
+#include "exg_strcol.hpp"
 
 namespace exg {
 namespace seqfn {
 
 static constexpr uint32_t kTile = 16384;
-static constexpr uint32_t kTileRows = kTile / (EXG_INLINE_LENGTH + 1) + 3;  // first + last + the whole rows between: <= 1262
+static constexpr uint32_t kTileRows = tile_rows(kTile);  // <= 1262
 static constexpr uint32_t kGrid = 1024;  // 4 workgroups a CU: every run of tiles is resident at once
 
-struct Col {
-    const uint4 *rows;
-    const uint8_t *base;
-    uint64_t payload_base;
-};
 // workspace: goff | lidx | loff (n + 1 u64 each) | scan scratch | err (u64) | lrow (u32 x n) | count (u32 x n, gc_content)
 struct Ws {
     uint64_t *goff, *lidx, *loff, *tmp, *err;
@@ -55,10 +51,6 @@ static Ws ws_layout(uint32_t op, uint64_t n, void *base) {
     return w;
 }
 
-__device__ __forceinline__ const uint8_t *src_of(const Col &c, uint64_t r, uint4 v) {
-    if (v.x <= EXG_INLINE_LENGTH) return reinterpret_cast<const uint8_t *>(c.rows + r) + 4;
-    return c.base + (((uint64_t)v.z | ((uint64_t)v.w << 32)) - c.payload_base);
-}
 __device__ __forceinline__ uint64_t tile_len(uint32_t op, uint32_t len) {
     const uint64_t w = output_length(op, len);
     return w > EXG_INLINE_LENGTH ? w : 0;
@@ -119,33 +111,13 @@ __global__ __launch_bounds__(256) void k_rows(Col c, uint32_t op, uint64_t n, Ws
             b = base_to(m.to, x);
         }
         if (!ok && key == kNoError) key = (r << 32) | ((translate ? 3 * i : i) + 1);
-        o[i >> 2] |= b << (8 * (i & 3));
+        put_byte(o, i, b);
     }
-    if (wl > EXG_INLINE_LENGTH) {
-        const uint64_t p = out_base + w.goff[r];
-        out[r] = make_uint4(wl, o[0], (uint32_t)p, (uint32_t)(p >> 32));
-    } else {
-        out[r] = make_uint4(wl, o[0], o[1], o[2]);
-    }
+    out[r] = wl > EXG_INLINE_LENGTH ? long_string(wl, o[0], out_base + w.goff[r]) : inline_string(wl, o);
     if (key != kNoError) atomicMin((unsigned long long *)w.err, (unsigned long long)key);
 }
 
 // ---- tiles ----------------------------------------------------------------------------------------------------
-// largest k in [lo, hi) with a[k] <= pos, for a[lo] <= pos < a[hi]; one wave, 64 probes a round
-__device__ __forceinline__ uint64_t wave_search(const uint64_t *__restrict__ a, uint64_t lo, uint64_t hi, uint64_t pos) {
-    const uint32_t lane = lane_id();
-    while (hi - lo > 1) {
-        const uint64_t step = (hi - lo + 63) >> 6;
-        uint64_t idx = lo + (lane + 1) * step;
-        if (idx > hi) idx = hi;  // (a[hi] > pos: a clamped probe never counts)
-        const uint64_t c = __popcll(__ballot(a[idx] <= pos));
-        const uint64_t nh = lo + (c + 1) * step;
-        lo += c * step;
-        hi = nh < hi ? nh : hi;
-    }
-    return lo;
-}
-
 // The window of n16 x 16 bytes at address A (any alignment) from aligned 16-byte loads.  Only the bytes [A + lo, A + hi) of
 // it belong to a row: an aligned block is read — whole — when it holds one of them, so every block read lies in a page the
 // row lies in; the other blocks read as zeros (A itself may lie in front of the row).
@@ -338,14 +310,7 @@ __global__ __launch_bounds__(256) void k_tiles(Col c, uint32_t op, uint64_t n, W
             }
         }
     }
-    if (kKind != kGc) {
-#pragma unroll
-        for (int dlt = 32; dlt; dlt >>= 1) {
-            const uint64_t o = __shfl_xor((unsigned long long)key, dlt, 64);
-            key = o < key ? o : key;
-        }
-        if ((t & 63) == 0 && key != kNoError) atomicMin((unsigned long long *)w.err, (unsigned long long)key);
-    }
+    if (kKind != kGc) wave_min_error(key, w.err, t & 63);
 }
 
 // gc_content of the rows that span tiles: their counters are complete now
@@ -451,13 +416,7 @@ extern "C" int exg_sequence_op(const exg_sequence_op_args *a) {
 }
 
 extern "C" int exg_sequence_result(const exg_seq_result *d_result, void *stream, exg_seq_result *out) {
-    if (!d_result || !out) {
-        set_error("exg_sequence_result: null pointer");
-        return EXG_E_INVALID_ARG;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    EXG_HIP_CHECK(hipMemcpyAsync(out, d_result, sizeof(*out), hipMemcpyDeviceToHost, s));
-    EXG_HIP_CHECK(hipStreamSynchronize(s));
+    if (const int rc = fetch_result("exg_sequence_result", d_result, stream, out)) return rc;
     if (out->error_code) {
         char text[96];
         format_error(out->error_code, out->error_bytes, out->error_length, text, sizeof text);

@@ -81,3 +81,33 @@ def mutate(rng, s, rate):
         else:
             out.append(c)
     return bytes(out)
+
+
+MIXED_MAX_PAIR_BYTES, MIXED_MAX_PENALTY = 4096, 400
+
+
+def mixed_phase_pairs():
+    """(texts, patterns, kinds): 200 rows in a fixed shuffled order whose pairs are in different phases of the forward pass at
+    once when one wave holds several of them — kinds "empty" (0 + 0 and 0 + k bytes, NULL among them), "same" (done at s = 0),
+    "near" (20..150 bytes at 5 %), "capped" (a penalty above MIXED_MAX_PENALTY), "long" (above MIXED_MAX_PAIR_BYTES) and "global"
+    (2 x 1 200 bytes at 2 %: 74 454 bytes of rings and strings, more than a pair's LDS share at any lane width)"""
+    rng = np.random.default_rng(2024)
+    rows = [(b"", b"", "empty"), (None, None, "empty"), (None, b"ACGTACGTACGTA", "empty"), (b"", b"ACG", "empty")]
+    rows += [(random_seq(rng, int(k)), b"" if k % 2 else None, "empty") for k in rng.integers(1, 40, 12)]
+    for k in rng.integers(20, 151, 30):
+        s = random_seq(rng, int(k))
+        rows.append((s, s, "same"))
+    for k in rng.integers(20, 151, 145):
+        s = random_seq(rng, int(k))
+        rows.append((s, mutate(rng, s, 0.05), "near"))
+    rows += [(bytes([a]) * k, bytes([b]) * k, "capped") for a, b, k in zip(b"ACGT", b"CGTA", (150, 140, 130, 120))]
+    for _ in range(3):
+        s = random_seq(rng, 1200)
+        rows.append((s, mutate(rng, s, 0.02), "global"))
+    for k in (2100, 2049):
+        s = random_seq(rng, k)
+        rows.append((s, s[:-1], "long"))
+    assert len(rows) == 200
+    order = rng.permutation(len(rows))
+    texts, patterns, kinds = zip(*[rows[i] for i in order])
+    return list(texts), list(patterns), np.array(kinds)

@@ -282,6 +282,43 @@ def test_max_pair_bytes(gpu):
     assert np.array_equal(run.scores().view(np.uint32), want_scores(texts[:123], patterns[:123], ref.DEFAULTS).view(np.uint32))
 
 
+def mixed_launch(lanes, valid=None):
+    """one exg_align_score call over align_ref.mixed_phase_pairs() at its limits"""
+    texts, patterns, _ = ref.mixed_phase_pairs()
+    d_t, d_tp = upload(texts, BASE_T)
+    d_p, d_pp = upload(patterns, BASE_P)
+    return Launch(d_t, d_tp, d_p, d_pp, len(texts), max_pair_bytes=ref.MIXED_MAX_PAIR_BYTES, max_penalty=ref.MIXED_MAX_PENALTY, lanes=lanes,
+                  valid=valid)
+
+
+@pytest.mark.parametrize("lanes", LANES)
+def test_pairs_in_every_phase_in_one_wave(gpu, lanes):
+    """one call whose groups claim, step, end and go to the global pass at different times (at 16 and 32 lanes: inside one wave):
+    scores, validity bits, n_capped, n_global and the error row are the oracle's, and a second launch is byte-identical"""
+    import torch
+    from exon_duckdb_amd import abi
+    texts, patterns, kinds = ref.mixed_phase_pairs()
+    done = (kinds != "capped") & (kinds != "long")
+    want = want_scores([t for t, d in zip(texts, done) if d], [p for p, d in zip(patterns, done) if d], ref.DEFAULTS)
+    capped = want_scores([t for t, k in zip(texts, kinds) if k == "capped"], [p for p, k in zip(patterns, kinds) if k == "capped"], ref.DEFAULTS)
+    assert (-want <= ref.MIXED_MAX_PENALTY).all() and (-capped > ref.MIXED_MAX_PENALTY).all() and (want[kinds[done] == "same"] == 0).all()
+    valid = torch.full((len(texts) // 64 + 2,), -1, dtype=torch.int64, device="cuda")
+    run = mixed_launch(lanes, valid)
+    first_long = int(np.flatnonzero(kinds == "long")[0])
+    length = len(texts[first_long]) + len(patterns[first_long])
+    assert length > ref.MIXED_MAX_PAIR_BYTES and run.rc == 0 and run.result_rc == abi.EXG_E_PARSE
+    r = run.result
+    assert (r.error_code, r.error_row, r.error_length, r.error_limit, r.flags) == (abi.EXG_PE_ALIGN_TOO_LONG, first_long, length, ref.MIXED_MAX_PAIR_BYTES, 0)
+    assert (r.n_capped, r.n_global) == (4, 3)
+    got = run.scores()
+    assert np.array_equal(got[done].view(np.uint32), want.view(np.uint32))
+    assert np.isneginf(got[kinds == "capped"]).all() and (got[kinds == "long"] == SENTINEL).all()
+    bits = np.unpackbits(valid.cpu().numpy().view(np.uint8), bitorder="little")
+    assert np.array_equal(bits[:len(texts)] == 0, kinds == "capped") and bits[len(texts):].all()
+    again = mixed_launch(lanes)
+    assert again.scores().tobytes() == got.tobytes() and bytes(again.result) == bytes(r)
+
+
 def fastq(reads):
     return b"".join(b"@r%d\n%s\n+\n%s\n" % (i, s, b"I" * len(s)) for i, s in enumerate(reads))
 

@@ -161,6 +161,20 @@ def test_library_surface_of_the_alignment_op():
     assert lib.exg_align_result(None, None, None) == abi.EXG_E_INVALID_ARG and b"exg_align_result" in lib.exg_last_error_message()
 
 
+def test_workspace_sizes_are_pinned():
+    """exg_align_workspace_bytes(n_rows, max_pair_bytes, mismatch, gap_opening, gap_extension) as the tree before the forward pass
+    was stated once (exg_align_core.hpp) returned it: n_rows around the 16-byte rounding of the list, max_pair_bytes on both sides
+    of the all-LDS threshold (lds_need(15, 526) = 16 360 <= 16 384 < lds_need(15, 527)) and of 30 000, and a ring too deep for LDS"""
+    from exon_duckdb_amd import load_library
+    ws = load_library().exg_align_workspace_bytes
+    pins = {(0, 300, 4, 6, 2): 64, (1, 300, 4, 6, 2): 80, (3, 526, 4, 6, 2): 80, (3, 527, 4, 6, 2): 8110160,
+            (1023, 526, 4, 6, 2): 4160, (1024, 527, 4, 6, 2): 8114240, (1025, 300, 4, 6, 2): 4176, (100000, 300, 4, 6, 2): 400064,
+            (100000, 29999, 4, 6, 2): 461200064, (100000, 30000, 4, 6, 2): 461216448, (1025, 29999, 4, 6, 2): 460804176,
+            (1, 30000, 4, 6, 2): 460816464, (1024, 300, 5, 200, 1): 63500352}
+    for args, want in pins.items():
+        assert ws(*args) == want, args
+
+
 def test_host_functions_under_asan_ubsan(tmp_path):
     """tests/align_asan_driver.cpp: a stand-alone program over exg_alignfn.hpp and the host scalar of exon_table_function.hpp
     (exactly-sized heap strings, every parameter set, the limits and the bind-time errors), built with AddressSanitizer + UBSan"""
@@ -179,7 +193,8 @@ def test_host_functions_under_asan_ubsan(tmp_path):
 
 @pytest.mark.skipif(not (os.path.exists(HIPCC) or shutil.which("hipcc")), reason="hipcc is not installed")
 def test_kernel_resources(tmp_path):
-    """the code object's own report for the four instances of k_align: no scratch anywhere; the LDS policy's
+    """the code object's own report for the four instances of k_align with the score recorder (the string op's
+    instances of the same template are held to their own bounds by test_alignstr_host.py): no scratch anywhere; the LDS policy's
     instances declare no static LDS (a pair's share is sized at launch) and keep at most 64 VGPRs = 8 waves a SIMD, so that
     LDS alone decides how many pairs a CU holds (16 of 150 bp reads: four waves a SIMD at 64 lanes a pair)"""
     from exon_duckdb_amd import build as B
@@ -196,8 +211,9 @@ def test_kernel_resources(tmp_path):
         seen[name] = dict(vgprs=field("VGPRs"), scratch=field("ScratchSize [bytes/lane]"), occupancy=field("Occupancy [waves/SIMD]"),
                           lds=field("LDS Size [bytes/block]"))
         print(name, seen[name])
-    lds = [v for k, v in seen.items() if "k_align" in k and "LdsPolicy" in k]
-    glob = [v for k, v in seen.items() if "k_align" in k and "GlobalPolicy" in k]
+    assert not any("HistoryRec" in k for k in seen)
+    lds = [v for k, v in seen.items() if "k_align" in k and "ScoreRec" in k and "LdsPolicy" in k]
+    glob = [v for k, v in seen.items() if "k_align" in k and "ScoreRec" in k and "GlobalPolicy" in k]
     assert len(lds) == 3 and len(glob) == 1 and len(seen) == 6
     assert all(v["scratch"] == 0 for v in seen.values())
     for v in lds:

@@ -366,6 +366,48 @@ def test_max_pair_bytes(gpu):
     check_outputs(run, want_cigars(texts[:123], patterns[:123], align_ref.DEFAULTS))
 
 
+@pytest.mark.parametrize("lanes", LANES)
+def test_pairs_in_every_phase_in_one_wave(gpu, lanes):
+    """one call over align_ref.mixed_phase_pairs(), whose groups claim, step, trace, end and go to the global pass at different
+    times (at 16 and 32 lanes: inside one wave): every string_t, the payload, out_bytes, the scores, validity bits, n_capped,
+    n_global and the error row are the oracle's; exg_align_score gives the same scores; a second launch is byte-identical"""
+    import torch
+    import test_alignfn_gpu as score_suite
+    from exon_duckdb_amd import abi
+    texts, patterns, kinds = align_ref.mixed_phase_pairs()
+    limit, cap = align_ref.MIXED_MAX_PAIR_BYTES, align_ref.MIXED_MAX_PENALTY
+    done = (kinds != "capped") & (kinds != "long")
+    found = iter(oracle([t for t, d in zip(texts, done) if d], [p for p, d in zip(patterns, done) if d], align_ref.DEFAULTS))
+    want = [next(found) if d else (b"", None) for d in done]
+    pens = np.array([pen for (_, pen), d in zip(want, done) if d], np.int64)
+    assert (pens <= cap).all() and all(align_ref.penalty(t, p) > cap for t, p, k in zip(texts, patterns, kinds) if k == "capped")
+    d_t, d_tp = upload(texts, BASE_T)
+    d_p, d_pp = upload(patterns, BASE_P)
+
+    def launch(valid=None):
+        return Launch(d_t, d_tp, d_p, d_pp, len(texts), max_pair_bytes=limit, max_penalty=cap, lanes=lanes, valid=valid, out_capacity=1 << 16)
+
+    valid = torch.full((len(texts) // 64 + 2,), -1, dtype=torch.int64, device="cuda")
+    run = launch(valid)
+    first_long = int(np.flatnonzero(kinds == "long")[0])
+    length = len(texts[first_long]) + len(patterns[first_long])
+    assert run.rc == 0 and run.result_rc == abi.EXG_E_PARSE
+    r = run.result
+    assert (r.error_code, r.error_row, r.error_length, r.error_limit, r.flags) == (abi.EXG_PE_ALIGN_TOO_LONG, first_long, length, limit, 0)
+    assert (r.n_capped, r.n_global, r.out_capacity) == (4, 3, 1 << 16)
+    check_outputs(run, [c for c, _ in want])
+    assert not run.outputs()[0][~done].any()
+    got = run.scores()
+    assert np.array_equal(got[done].view(np.uint32), (-pens).astype(np.float32).view(np.uint32))
+    assert np.isneginf(got[kinds == "capped"]).all() and (got[kinds == "long"] == SENTINEL).all()
+    bits = np.unpackbits(valid.cpu().numpy().view(np.uint8), bitorder="little")
+    assert np.array_equal(bits[:len(texts)] == 0, kinds == "capped") and bits[len(texts):].all()
+    assert score_suite.mixed_launch(lanes).scores().tobytes() == got.tobytes()
+    again = launch()
+    assert all(a.tobytes() == b.tobytes() for a, b in zip(again.outputs(), run.outputs()))
+    assert again.scores().tobytes() == got.tobytes() and bytes(again.result) == bytes(r)
+
+
 @pytest.mark.parametrize("n", [0, 1, 63, 64, 65, 100000])
 def test_row_counts(gpu, n):
     rng = np.random.default_rng(12)

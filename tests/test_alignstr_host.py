@@ -208,6 +208,23 @@ def test_workspace_function():
         assert ws(*bad) == 0                                       # (the last two: a workspace above 2^48 bytes)
 
 
+def test_workspace_sizes_are_pinned():
+    """exg_align_string_workspace_bytes(n_rows, max_pair_bytes, mismatch, gap_opening, gap_extension, max_penalty, out_capacity) as
+    the tree before the forward pass was stated once (exg_align_core.hpp) returned it: n_rows around kPairs = 1 024 slots,
+    max_pair_bytes on both sides of the all-LDS threshold (526 | 527 at the defaults) and of the 16-bit history (29 999 | 30 000),
+    max_penalty 0 and 100, a ring too deep for LDS, and a history above 2^48 bytes (0)"""
+    from exon_duckdb_amd import load_library
+    ws = load_library().exg_align_string_workspace_bytes
+    pins = {(0, 300, 4, 6, 2, 0, 0): 96, (1, 300, 4, 6, 2, 100, 64): 136480, (3, 526, 4, 6, 2, 0, 1000): 10236336,
+            (3, 527, 4, 6, 2, 0, 1000): 18384816, (1023, 526, 4, 6, 2, 100, 0): 35364960, (1024, 527, 4, 6, 2, 100, 0): 43475056,
+            (1025, 300, 4, 6, 2, 0, 4096): 869724320, (100000, 300, 4, 6, 2, 100, 1 << 20): 38330416,
+            (100000, 29999, 4, 6, 2, 100, 0): 558899248, (100000, 30000, 4, 6, 2, 100, 0): 591503408,
+            (1025, 29999, 4, 6, 2, 0, 0): 8298301661344, (3, 30000, 4, 6, 2, 0, 0): 65287938112,
+            (1024, 300, 5, 200, 1, 100, 100): 129745120, (1000, 1 << 21, 4, 6, 2, 0, 0): 0}
+    for args, want in pins.items():
+        assert ws(*args) == want, args
+
+
 def test_argument_errors_that_need_no_device():
     from exon_duckdb_amd import abi, load_library
     lib = load_library()
@@ -265,9 +282,10 @@ def test_host_functions_under_asan_ubsan(tmp_path):
 
 @pytest.mark.skipif(not (os.path.exists(HIPCC) or shutil.which("hipcc")), reason="hipcc is not installed")
 def test_kernel_resources(tmp_path):
-    """the code object's own report for exg_alignstr.hip: no scratch in any kernel; the LDS policy's instances
-    declare no static LDS (a pair's share is sized at launch).  Observed: 83 / 83 / 74 VGPRs at 16 / 32 / 64 lanes, 104 in the
-    two global instances.  1 024 resident pairs are four waves a CU at most, one a SIMD: the occupancy relied on is 1; the
+    """the code object's own report for exg_alignstr.hip: no scratch in any kernel; the instances of k_align with
+    the history recorder that use the LDS policy declare no static LDS (a pair's share is sized at launch).  Observed: 86 / 86 /
+    77 VGPRs at 16 / 32 / 64 lanes, 108 in the two global instances, in the tree before the forward pass was stated once and in
+    this one (profiles/strcol_refactor_ab.md).  1 024 resident pairs are four waves a CU at most, one a SIMD: the occupancy relied on is 1; the
     bounds below keep the instances away from the 128-VGPR step all the same."""
     from exon_duckdb_amd import build as B
     src = os.path.join(B.CSRC, "exg_alignstr.hip")
@@ -283,8 +301,9 @@ def test_kernel_resources(tmp_path):
         seen[name] = dict(vgprs=field("VGPRs"), scratch=field("ScratchSize [bytes/lane]"), occupancy=field("Occupancy [waves/SIMD]"),
                           lds=field("LDS Size [bytes/block]"))
         print(name, seen[name])
-    lds = [v for k, v in seen.items() if "k_align_str" in k and "LdsPolicy" in k]
-    glob = [v for k, v in seen.items() if "k_align_str" in k and "GlobalPolicy" in k]
+    assert not any("ScoreRec" in k for k in seen)
+    lds = [v for k, v in seen.items() if "k_align" in k and "HistoryRec" in k and "LdsPolicy" in k]
+    glob = [v for k, v in seen.items() if "k_align" in k and "HistoryRec" in k and "GlobalPolicy" in k]
     assert len(lds) == 3 and len(glob) == 2
     assert any("k_place" in k for k in seen) and any("k_finish" in k for k in seen)
     assert all(v["scratch"] == 0 for v in seen.values())
