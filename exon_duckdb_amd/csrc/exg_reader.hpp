@@ -544,7 +544,7 @@ int fail(exg_reader *r, int code, const std::string &msg);
 int open_next_file(exg_reader *r);
 // Scan the next device batch of the current file (see exg_reader.cpp)
 int next_batch(exg_reader *r, bool count_only, uint64_t *n_records_out);
-// exg_arrow_stream.cpp — the nested VCF columns at the chunk boundary (DuckDB vector layouts built on the device):
+// exg_vcf_nested_build.cpp — the nested VCF columns at the chunk boundary (DuckDB vector layouts built on the device):
 // header keys + schema trees (needs the first file open), and the columns of one scanned batch
 int nested_prepare(exg_reader *r);
 void nested_schema(exg_reader *r, exg_schema *out);

@@ -25,30 +25,17 @@
 #include <stdint.h>
 
 #include "../../include/exon_gpu.h"
+#include "exg_vcf_keys.hpp"  // Key, its value types, key_hash_step / kKeyHashSeed / key_slot: shared with the host's table builder
 
 namespace exg {
 namespace vn {
 
-enum : uint8_t { kFlag = 0, kInt = 1, kFloat = 2, kString = 3 };  // (= exg::arrow::kVt*, exg_rd::kKey*)
-
-// one declared key (device array, header order)
-struct Key {
-    uint32_t name_off;  // in KeyTab::names
-    uint16_t name_len;
-    uint8_t type, is_list;
-    uint32_t hash;     // key_hash(name)
-    int32_t list_idx;  // index among the list keys of its kind, -1: scalar
-};
 struct KeyTab {
     const Key *keys;
     const uint32_t *slots;  // open addressing, linear probing: key index + 1, 0 = empty; slot_mask + 1 entries (>= 2 x n_keys)
     const uint8_t *names;
     uint32_t n_keys, slot_mask, names_bytes, n_lists;
 };
-// host and device agree on the hash (FNV-1a) and the first slot
-inline __host__ __device__ uint32_t key_hash_step(uint32_t h, uint32_t b) { return (h ^ b) * 16777619u; }
-static constexpr uint32_t kKeyHashSeed = 2166136261u;
-inline __host__ __device__ uint32_t key_slot(uint32_t h, uint32_t mask) { return (h ^ (h >> 15)) & mask; }
 
 // where the children of one key go (device array per kind and batch)
 struct KeyOut {
