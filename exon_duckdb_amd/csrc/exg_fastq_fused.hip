@@ -14,8 +14,9 @@
 //     (bytes are only parked in LDS for the random access that field extraction needs).
 //     Why: the global line index arrives ~5 us after a tile's count is published (below), and a
 //     CU can hold at most 160 KiB of LDS-staged bytes; keeping the waiting bytes in registers
-//     multiplies the bytes in flight per CU (6 workgroups x 48 KiB) at 24.7 KiB of LDS each, which is
-//     what hides that latency (A/B in one box: 2 halves 52.1 %, 3 halves 53.7 %, 4 halves 50.6 % of peak);
+//     multiplies the bytes in flight per CU (7 workgroups x 48 KiB) at 22.2 KiB of LDS each, which is
+//     what hides that latency (A/B in one box: 2 halves 52.1 %, 3 halves 53.7 %, 4 halves 50.6 % of peak;
+//     six -> seven workgroups per CU at 3 halves: 3.0 % faster, profiles/fastq_seven_waves_ab.md);
 //   * the 1 KiB that precedes a half is staged too (from memory for the first half, from the
 //     previous half's tail for the others), so a record straddling the left edge is resolved from
 //     LDS.  A record that begins in front of that window (a long read: every PacBio / ONT file) is
@@ -139,13 +140,16 @@ __device__ __forceinline__ void fastq_emit_half(const L &s, const FastqDev &a, S
                 if (e0 > s0 && !(c.is_eof_tile && e0 == c.lim_e) && ldb(s, e0 - 1) == '\r') e0--;
                 int ns = s0 + 1 < e0 ? s0 + 1 : e0;
                 int sp = e0;
-                for (uint32_t aa = (uint32_t)ns & ~3u; aa < (uint32_t)e0 && sp == e0; aa += 32) {
-                    uint32_t w8[8];
+                // (the lean scan looks at 16 bytes a step, the any-shape scans at 32: eight words in flight are four registers
+                // more than the lean scan has at seven waves per SIMD, and a read's name ends within the first step or two)
+                constexpr int kStep = kMode == kLean ? 4 : 8;  // words per step
+                for (uint32_t aa = (uint32_t)ns & ~3u; aa < (uint32_t)e0 && sp == e0; aa += 4 * kStep) {
+                    uint32_t w8[kStep];
 #pragma unroll
-                    for (int q = 0; q < 8; q++) w8[q] = ldw(s, aa + 4 * q);  // in-bounds: the buffer has slack
-                    uint32_t bits = 0;  // one bit per byte of the 32-byte block
+                    for (int q = 0; q < kStep; q++) w8[q] = ldw(s, aa + 4 * q);  // in-bounds: the buffer has slack
+                    uint32_t bits = 0;  // one bit per byte of the block
 #pragma unroll
-                    for (int q = 0; q < 8; q++) bits |= nib4(match4(w8[q], 0x20202020u)) << (4 * q);
+                    for (int q = 0; q < kStep; q++) bits |= nib4(match4(w8[q], 0x20202020u)) << (4 * q);
                     if (aa < (uint32_t)ns) bits &= 0xFFFFFFFFu << ((uint32_t)ns - aa);
                     if (bits) {
                         uint32_t pos = aa + (uint32_t)__ffs(bits) - 1;
@@ -230,7 +234,11 @@ struct FastqFormat {
     static constexpr bool kBarriers = true;   // (exg_fused_core.hpp opaque: its lean scan spills without them)
     static constexpr int kHalves = kFastqHalves;
     static constexpr int kHalvesFull = kHalves;
-    static constexpr int kMinWavesPerSimd = 6;  // 80 VGPRs, no scratch: 6 x 48 KiB in flight per CU
+    static constexpr bool kParkHalf0 = true;  // (exg_fused_core.hpp FusedLdsT PARK) 22 744 B of LDS: seven workgroups fit in 160 KiB
+#ifndef EXG_FASTQ_WAVES
+#define EXG_FASTQ_WAVES 7
+#endif
+    static constexpr int kMinWavesPerSimd = EXG_FASTQ_WAVES;  // 72 VGPRs, no scratch: 7 x 48 KiB in flight per CU
 #ifndef EXG_FASTQ_WAVES_FULL
 #define EXG_FASTQ_WAVES_FULL 5
 #endif

@@ -21,8 +21,9 @@
 //   F::kTabMapLean / kTabMapFull          also keep a '\t' bitmap of every half (VCF's lean scan: short lines, every byte lies within 64 bytes of a
 //                                         line start; not its any-shape scan: on wide lines only the first nine tabs of a line are ever looked at)
 //   F::kHalves                            16 KiB halves per workgroup (bytes waiting in registers: 16 VGPRs each)
-//   F::kMinWavesPerSimd                   occupancy the register allocator must respect (FASTQ lean scan: 6 = six workgroups per CU at
-//                                         80 VGPRs and 24.7 KiB of LDS each; VCF: 5; the any-shape instances one less)
+//   F::kMinWavesPerSimd                   occupancy the register allocator must respect (FASTQ lean scan: 7 = seven workgroups per CU at
+//                                         72 VGPRs and 22.2 KiB of LDS each; VCF: 5; the FASTQ any-shape instances 5)
+//   F::kParkHalf0                         (lean scan) half 0's newline masks wait in the byte buffer, not in a map of their own: FusedLdsT PARK
 #pragma once
 #include "exg_fastq_ws.hpp"
 
@@ -51,10 +52,16 @@ static constexpr unsigned long long kFlag = 1ull << 63;  // descriptor word is p
 static constexpr unsigned long long kVal = (1ull << 48) - 1;
 
 // NL = newline positions kept per half (a half with more lines goes to the general path)
-template <int NL, int H, bool TABS = false>
+// PARK (F::kParkHalf0, lean scan): half 0's newline masks have no storage of their own.  Until half 0 is staged the byte buffer
+// is empty, so the mask of chunk c of half 0 waits in it, at the place only its READER writes to afterwards: thread t reads the
+// masks of chunks 4 t .. 4 t + 3 (8 bytes) and later stages its row-3 chunk, 16 bytes at kWin + 3 * 4096 + 16 t — the masks
+// lie in the first 8 of those.  No barrier beyond #1: each thread reads its masks before it stages over them.
+template <int NL, int H, bool TABS = false, bool PARK = false>
 struct FusedLdsT {
     static constexpr int kNlCap = NL;
     static constexpr bool kHasTabs = TABS;
+    static constexpr bool kPark = PARK;
+    static constexpr int kMapHalves = PARK ? H - 1 : H;
     // TABS (VCF): '\t' mask of every 16-byte chunk next to the '\n' one; a line's first eight tabs are then eight
     // bit pops out of one funnel-shifted 64-bit word instead of a SWAR search over the line's bytes.  Rows carry
     // 8 bytes of slack so that the word after a line's last one can always be read.
@@ -62,7 +69,25 @@ struct FusedLdsT {
     __attribute__((aligned(8))) uint16_t tabmap[TABS ? H : 1][kTabRow];
     uint8_t bytes[kLdsBytes];        // [0,kWin) window, then the half; e = p + kWin
     uint16_t nlist[4 + NL + 4];  // e-offsets of newlines: [0..3] the 4 before the half (oldest first)
-    uint16_t bitmap[H][kTile / 16];  // '\n' mask of every 16-byte chunk, written by the first pass
+    uint16_t bitmap[kMapHalves][kTile / 16];  // '\n' mask of every 16-byte chunk, written by the first pass (PARK: of halves 1 ..)
+    // where the mask of chunk c (0 .. kTile / 16 - 1) of half h waits for the half to be staged
+    __device__ __forceinline__ uint16_t *map_entry(int h, uint32_t c) {
+        if constexpr (PARK) {
+            if (h == 0) return reinterpret_cast<uint16_t *>(bytes + kWin + (kRows - 1) * kThreads * 16 + (c >> 2) * 16 + (c & 3u) * 2);
+            return &bitmap[h - 1][c];
+        } else {
+            return &bitmap[h][c];
+        }
+    }
+    // the four masks of thread t's 64 contiguous bytes of half h
+    __device__ __forceinline__ unsigned long long map_word(int h, uint32_t t) const {
+        if constexpr (PARK) {
+            if (h == 0) return *reinterpret_cast<const unsigned long long *>(bytes + kWin + (kRows - 1) * kThreads * 16 + t * 16);
+            return *reinterpret_cast<const unsigned long long *>(&bitmap[h - 1][t * 4]);
+        } else {
+            return *reinterpret_cast<const unsigned long long *>(&bitmap[h][t * 4]);
+        }
+    }
     uint32_t wtot[4];   // per-wave newline counts of the staged half
     uint32_t wcnt[4];   // per-wave packed (half 0 | half 1 << 16) newline counts
     unsigned long long prefix;            // '\n' in the buffer before this super-tile
@@ -393,14 +418,16 @@ __global__ __launch_bounds__(kThreads, kMode == kLean ? F::kMinWavesPerSimd : (k
     // (the any-shape scan that runs ALONE may cut its super-tiles differently from the lean scan and its redo run, which share
     // tile_redo: every per-half / per-super-tile array of the workspace is sized by 16 KiB tiles)
     constexpr int kHalves = (kMode == kFullPrimary || kMode == kFullIndex) ? F::kHalvesFull : F::kHalves;
-    using FusedLds = FusedLdsT<F::kNlCap, kHalves, (kMode == kLean ? F::kTabMapLean : F::kTabMapFull)>;
+    using FusedLds = FusedLdsT<F::kNlCap, kHalves, (kMode == kLean ? F::kTabMapLean : F::kTabMapFull), (kMode == kLean && F::kParkHalf0)>;
     constexpr int kNlCap = F::kNlCap;
     constexpr int kSuper = kTile * kHalves;
     constexpr bool kFull = kMode != kLean;
     constexpr bool kB = F::kBarriers;
+    constexpr bool kLeanB = kB && !kFull;  // barriers that only the lean scan needs (FASTQ: 72 registers for seven waves per SIMD)
     __shared__ __attribute__((aligned(16))) FusedLds s;
     const uint32_t tid = threadIdx.x;
-    const uint32_t lane = tid & 63, wave = tid >> 6;
+    // (kLeanB: the wave's number as a scalar — "wave == 3", the column a wave emits and its slot addresses cost no vector register)
+    const uint32_t lane = tid & 63, wave = kLeanB ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6;
     // DEV ONLY (tools/dev_probe.py): flags bits 8..11 select ablations on the synthetic FASTQ-150 file
     //   1: analytic prefix instead of the scanner   2: 1 + no output stores
     //   3: 1 + no emission at all                    4: scanner, no emission
@@ -440,8 +467,15 @@ __global__ __launch_bounds__(kThreads, kMode == kLean ? F::kMinWavesPerSimd : (k
     // loads of the common one: s_waitcnt vmcnt(1) + v_mov after every other load — two loads in flight per wave, not twelve
     // (the ISA of the lean FASTQ scan; A/B in one box: 2.247 -> 2.171 ms per 10 GB).  The address is a uniform base + a 32-bit
     // offset, which also takes the 64-bit vector adds out.
+    // (kLeanB: the window chunk is asked for AHEAD of the twelve, so it has arrived when the first of them has, and goes to its LDS
+    // slot — free from the start — behind the first chunk's classification: four registers that are not held across the phase)
+    uint4 wv = make_uint4(0, 0, 0, 0);
+    const int64_t woff = (int64_t)super_off - kWin + (int64_t)lane * 16;  // wave 3 only
     uint4 v[kHalves * kRows];
     if (lim_s > 0) {
+        if constexpr (kLeanB) {  // (inside this block: the waits behind it then know that it is the oldest load in flight)
+            if (wave == 3 && woff >= 0) wv = *reinterpret_cast<const uint4 *>(d_in + woff);
+        }
         const uint8_t *base = d_in + super_off;
         const uint32_t last = (((uint32_t)lim_s + 15u) & ~15u) - 16u;
 #pragma unroll
@@ -453,9 +487,9 @@ __global__ __launch_bounds__(kThreads, kMode == kLean ? F::kMinWavesPerSimd : (k
 #pragma unroll
         for (int j = 0; j < kHalves * kRows; j++) v[j] = make_uint4(0, 0, 0, 0);
     }
-    uint4 wv = make_uint4(0, 0, 0, 0);
-    const int64_t woff = (int64_t)super_off - kWin + (int64_t)lane * 16;  // wave 3 only
-    if (wave == 3 && woff >= 0) wv = *reinterpret_cast<const uint4 *>(d_in + woff);
+    if constexpr (!kLeanB) {
+        if (wave == 3 && woff >= 0) wv = *reinterpret_cast<const uint4 *>(d_in + woff);
+    }
 
     // ---- classify ONCE, in registers: 16-bit '\n' mask per chunk -> LDS bitmap; count for the publish ----
     // (the kernel is instruction-issue bound: classifying again when a half is staged cost 20 % more VALU)
@@ -470,9 +504,18 @@ __global__ __launch_bounds__(kThreads, kMode == kLean ? F::kMinWavesPerSimd : (k
     for (int j = 0; j < kHalves * kRows; j++) {
         const uint32_t mj = match16(v[j], 0x0A0A0A0Au);
         hi |= v[j].x | v[j].y | v[j].z | v[j].w;
-        s.bitmap[j / kRows][(j % kRows) * kThreads + tid] = (uint16_t)mj;
+        *s.map_entry(j / kRows, (j % kRows) * kThreads + tid) = (uint16_t)mj;
         if constexpr (FusedLds::kHasTabs) s.tabmap[j / kRows][(j % kRows) * kThreads + tid] = (uint16_t)match16(v[j], 0x09090909u);
         cnt += __popc(mj);
+        if constexpr (kLeanB) {
+            if (j == 0 && wave == 3) {
+                hi |= wv.x | wv.y | wv.z | wv.w;
+                *reinterpret_cast<uint4 *>(s.bytes + lane * 16) = wv;
+            }
+        }
+        // (kLeanB: a chunk's mask is stored and counted before the next chunk is looked at — the scheduler otherwise keeps up to
+        // twelve masks waiting for their store and their popcount, registers the 72 of seven waves per SIMD do not have)
+        if constexpr (kLeanB) __builtin_amdgcn_sched_barrier(0);
     }
     if (lim_s != kSuper) {
         // the input ends inside this super-tile: every thread takes the bytes past the end out of its own map entries (written
@@ -481,7 +524,7 @@ __global__ __launch_bounds__(kThreads, kMode == kLean ? F::kMinWavesPerSimd : (k
 #pragma unroll 1
         for (int j = 0; j < kHalves * kRows; j++) {
             const int rem = lim_s - (int)(j * kThreads + tid) * 16;
-            uint16_t *bm = &s.bitmap[j / kRows][(j % kRows) * kThreads + tid];
+            uint16_t *bm = s.map_entry(j / kRows, (j % kRows) * kThreads + tid);
             uint32_t mj = *bm;
             if (rem < 16) mj &= rem <= 0 ? 0u : ((1u << rem) - 1u);
             *bm = (uint16_t)mj;
@@ -493,7 +536,9 @@ __global__ __launch_bounds__(kThreads, kMode == kLean ? F::kMinWavesPerSimd : (k
     }
     hi &= 0x80808080u;
     for (int o = 32; o > 0; o >>= 1) cnt += __shfl_down(cnt, o, 64);
-    if (wave == 3) hi |= (wv.x | wv.y | wv.z | wv.w) & 0x80808080u;
+    if constexpr (!kLeanB) {
+        if (wave == 3) hi |= (wv.x | wv.y | wv.z | wv.w) & 0x80808080u;
+    }
     uint32_t any_hi = __any(hi != 0);
     if (lane == 0) {
         s.hi_or[wave] = any_hi;
@@ -539,7 +584,8 @@ __global__ __launch_bounds__(kThreads, kMode == kLean ? F::kMinWavesPerSimd : (k
         // ---- stage the half: window, bytes, newline list ------------------------------------------
         if (h == 0) {
             if (wave == 3) {
-                *reinterpret_cast<uint4 *>(s.bytes + lane * 16) = wv;
+                if constexpr (kLeanB) wv = *reinterpret_cast<const uint4 *>(s.bytes + lane * 16);  // (its own store, above)
+                else *reinterpret_cast<uint4 *>(s.bytes + lane * 16) = wv;
                 if (lane < 4) s.nlist[lane] = (uint16_t)kNoneE;
                 if constexpr (kFull) {
                     if (lane < 4) s.prev32[lane] = (int32_t)lane - 4;  // slot 3 = the newest newline in front of the super-tile
@@ -577,14 +623,17 @@ __global__ __launch_bounds__(kThreads, kMode == kLean ? F::kMinWavesPerSimd : (k
                 }
             }
         }
+        // Each thread owns 64 CONTIGUOUS bytes of the half (4 chunks): their masks are one 8-byte read of the bitmap, so newline
+        // ranks follow from one 32-bit wave scan.  (PARK: read ahead of the staging — half 0's parked masks lie where this
+        // thread's last chunk goes.)
+        unsigned long long mask = 0;
+        if constexpr (FusedLds::kPark) mask = s.map_word(h, tid);
 #pragma unroll
         for (int j = 0; j < kRows; j++)
             *reinterpret_cast<uint4 *>(s.bytes + kWin + (j * kThreads + tid) * 16) = v[h * kRows + j];
         uint32_t n_nl_h = 0;  // '\n' in this half
         {
-            // Each thread now owns 64 CONTIGUOUS bytes of the half (4 chunks): their masks are one 8-byte
-            // read of the bitmap, so newline ranks follow from one 32-bit wave scan.
-            unsigned long long mask = *reinterpret_cast<const unsigned long long *>(&s.bitmap[h][tid * 4]);
+            if constexpr (!FusedLds::kPark) mask = s.map_word(h, tid);
             uint32_t c = (uint32_t)__popcll(mask);
             uint32_t inc = wave_incl_sum_dpp(c);  // (on the VALU: three registers and twelve spilled scalars fewer than by ds_bpermute)
             if (lane == 63) s.wtot[wave] = inc;
@@ -702,7 +751,7 @@ __global__ __launch_bounds__(kThreads, kMode == kLean ? F::kMinWavesPerSimd : (k
             // ---- any shape ----------------------------------------------------------------------------------
             // positions of the newlines of ranks [base, base + kNlCap) -> the list (a later pass of a dense half)
             auto fill_list = [&](uint32_t base) {
-                unsigned long long mask = *reinterpret_cast<const unsigned long long *>(&s.bitmap[h][tid * 4]);
+                unsigned long long mask = s.map_word(h, tid);
                 uint32_t cc = (uint32_t)__popcll(mask);
                 uint32_t inc = wave_incl_sum(cc);
                 uint32_t r = inc - cc + (wave > 0 ? s.wtot[0] : 0) + (wave > 1 ? s.wtot[1] : 0) + (wave > 2 ? s.wtot[2] : 0) - base;

@@ -127,6 +127,7 @@ struct LineRowsFormat {
     // a line's tabs come from its 64-byte words in LDS, read when the line is cut (LdsSrc::tabs64): no '\t' map
     static constexpr bool kTabMapLean = false, kTabMapFull = false;
     static constexpr bool kBarriers = false;
+    static constexpr bool kParkHalf0 = false;
     static constexpr int kMinWavesPerSimd = R::kWavesFull, kMinWavesPerSimdRedo = R::kWavesFull;
     static constexpr int kMinWavesPerSimdFull = R::kWavesFull;
     __device__ static __forceinline__ uint32_t eof_extra_lines(unsigned long long) { return 0; }

@@ -225,6 +225,7 @@ struct VcfFormat {
     // a file, the 2 KiB map per half and its stores are gone (round 5: 2.04 -> TB/s on 100-sample lines)
     static constexpr bool kTabMapLean = true, kTabMapFull = false;
     static constexpr bool kBarriers = false;  // (exg_fused_core.hpp opaque: its lean scan ran 3 % slower with them)
+    static constexpr bool kParkHalf0 = false;  // (exg_fused_core.hpp FusedLdsT PARK: registers, not LDS, bound its residency)
 #ifndef EXG_VCF_WAVES
 #define EXG_VCF_WAVES 5
 #endif
