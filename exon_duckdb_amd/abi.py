@@ -53,8 +53,18 @@ EXG_PE_SAM_CIGAR = 41
 EXG_PE_SAM_LENGTHS = 42
 EXG_PE_CIGAR_INVALID = 44   # (43 is unassigned)
 EXG_PE_CIGAR_RANGE = 45
+EXG_PE_BCF_RECORD_LENGTH = 47   # (46 is unassigned)
+EXG_PE_BCF_TRUNCATED = 48
+EXG_PE_BCF_TYPE = 49
+EXG_PE_BCF_RESERVED_VALUE = 50
+EXG_PE_BCF_OVERRUN = 51
+EXG_PE_BCF_CHROM = 52
+EXG_PE_BCF_DICT_INDEX = 53
+EXG_PE_BCF_NO_ALLELE = 54
+EXG_PE_BCF_SAMPLE_COUNT = 55
 
 EXG_FMT_FASTA, EXG_FMT_FASTQ, EXG_FMT_VCF, EXG_FMT_BAM, EXG_FMT_BED, EXG_FMT_SAM = 1, 2, 3, 4, 5, 6
+EXG_FMT_BCF = 7
 EXG_BAM_COLUMNS = 10
 EXG_BED_COLUMNS = 12
 EXG_SAM_COLUMNS = 10
@@ -397,6 +407,20 @@ class OpenArgs(C.Structure):
                 ("shard_index", C.c_uint32), ("shard_count", C.c_uint32), ("columns", C.c_uint64), ("flags", C.c_uint64)]
 
 
+class BcfToVcfResult(C.Structure):
+    _fields_ = [("n_records", C.c_uint64), ("consumed_bytes", C.c_uint64), ("text_bytes_needed", C.c_uint64), ("text_bytes", C.c_uint64),
+                ("error_record", C.c_uint64), ("error_offset", C.c_uint64), ("error_code", C.c_uint32), ("flags", C.c_uint32),
+                ("tiles_rewalked", C.c_uint64)]
+
+
+class BcfToVcfArgs(C.Structure):
+    _fields_ = [("d_input", C.c_void_p), ("n_bytes", C.c_uint64), ("flags", C.c_uint32), ("n_samples", C.c_uint32),
+                ("d_contig_bytes", C.c_void_p), ("d_contig_table", C.c_void_p), ("n_contigs", C.c_uint32), ("n_strings", C.c_uint32),
+                ("d_string_bytes", C.c_void_p), ("d_string_table", C.c_void_p), ("gt_index", C.c_uint32), ("reserved", C.c_uint32),
+                ("d_output", C.c_void_p), ("output_capacity", C.c_uint64), ("d_workspace", C.c_void_p), ("workspace_bytes", C.c_uint64),
+                ("d_result", C.c_void_p), ("stream", C.c_void_p)]
+
+
 class InflateMember(C.Structure):
     _fields_ = [("comp_off", C.c_uint64), ("comp_size", C.c_uint64), ("out_off", C.c_uint64), ("out_cap", C.c_uint64)]
 
@@ -419,6 +443,9 @@ SIGNATURES = {
     "exg_bam_scan": (C.c_int, [C.POINTER(BamScanArgs)]),
     "exg_bed_scan": (C.c_int, [C.POINTER(BedScanArgs)]),
     "exg_sam_scan": (C.c_int, [C.POINTER(SamScanArgs)]),
+    "exg_bcf_workspace_bytes": (C.c_uint64, [C.c_uint64, C.c_uint32]),
+    "exg_bcf_to_vcf": (C.c_int, [C.POINTER(BcfToVcfArgs)]),
+    "exg_bcf_result": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(BcfToVcfResult)]),
     "exg_gzip_index": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),
                                  C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
     "exg_inflate_members": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),

@@ -93,6 +93,15 @@ extern "C" const char *exg_parse_error_string(uint32_t code) {
         case EXG_PE_SAM_LENGTHS: return "sequence and quality scores differ in length";
         case EXG_PE_CIGAR_INVALID: return "invalid CIGAR string";
         case EXG_PE_CIGAR_RANGE: return "CIGAR insertions exceed the sequence";
+        case EXG_PE_BCF_RECORD_LENGTH: return "l_shared below 24";
+        case EXG_PE_BCF_TRUNCATED: return "BCF record runs past the end of the stream";
+        case EXG_PE_BCF_TYPE: return "invalid BCF value type";
+        case EXG_PE_BCF_RESERVED_VALUE: return "reserved BCF integer value";
+        case EXG_PE_BCF_OVERRUN: return "BCF value runs past its record";
+        case EXG_PE_BCF_CHROM: return "CHROM outside the header's contigs";
+        case EXG_PE_BCF_DICT_INDEX: return "key outside the header's dictionary";
+        case EXG_PE_BCF_NO_ALLELE: return "BCF record without alleles";
+        case EXG_PE_BCF_SAMPLE_COUNT: return "sample count differs from the header's";
         default: return "unknown parse error";
     }
 }

@@ -1,18 +1,10 @@
 // exg_bam.hip — BAM records (SAM v1 §4.2) -> the ten columns of read_bam_file_records, on decoded bytes resident in HBM.
 //
-// A BAM record has no delimiter: record k + 1 begins at start_k + 4 + block_size_k, one dependent load per record.  The chain is
-// broken up by SPECULATION and repaired by a STITCH, so that the result is exactly the serial chain from byte 0:
+// A BAM record has no delimiter: record k + 1 begins at start_k + 4 + block_size_k, one dependent load per record.  The records
+// are found by exg_chain.hpp (speculation per 32 KiB tile, a stitch from byte 0, an index of the offsets); what is BAM's own
+// there is the test for a plausible record: header fields in range, a printable NUL-terminated name, the declared lengths fit
+// block_size, and the successor at + 4 + block_size passes the field test too.  Then:
 //
-//   k_speculate  one wavefront per 32 KiB tile: all lanes test candidate offsets for a plausible record (header fields in
-//                range, a printable NUL-terminated name, the declared lengths fit block_size, and the successor at
-//                + 4 + block_size passes the field test too); from the first hit one lane walks the chain to the tile's end and
-//                notes entry, exit (the first start at or behind the tile's end), record count and how the walk stopped.
-//   k_stitch     one workgroup, the tile table staged through LDS 2048 tiles at a time: the chain from byte 0 visits tile
-//                t = cur / 32 KiB; the tile's speculated walk is taken when its entry is exactly `cur`, else the tile is
-//                walked again from `cur` (tiles_rewalked).  Tiles a long record jumps over are never looked at.  The running
-//                row count is every visited tile's first row: no separate scan.  One wavefront does it, 64 tiles at a step
-//                where every one of them is entered exactly where it was speculated (the usual case), else tile by tile.
-//   k_index      one thread per visited tile: the record offsets, from the true entry.
 //   k_rows       one wavefront per record: validation, reference span of the CIGAR (-> end), length of its text, whether the
 //                qualities are absent, the validity bits, the bytes the row needs in the side buffer.
 //   (prefix sum of those -> the rows' offsets in the side buffer)
@@ -22,27 +14,27 @@
 //                INTEGER values.  Strings of at most 12 bytes are inlined and take no side bytes.
 //   k_validity   the validity words of columns 2, 3, 4, 5, 7 (a ballot per 64 rows).
 //
-// Speculation is never a source of truth: a tile's walk is used only when the true chain arrives at its entry, and a walk is
-// a pure function of its entry.  A read name or an aux value that holds a plausible record costs a second walk, not a row.
+// A read name or an aux value that holds a plausible record costs a second walk, not a row.
 #include "exg_bam.hpp"
+#include "exg_chain.hpp"
 #include "exg_common.hpp"
 #include "exg_scan.hpp"
 
 namespace exg {
 namespace bam {
 
-static constexpr uint64_t kNone = ~0ull;
-static constexpr uint32_t kStitchChunk = 2048;
+using chain::kNone;
+using chain::ld32;
 
-struct Ws {
-    uint64_t *spec_entry, *spec_exit, *true_entry, *row_base, *ctl, *rec_off, *side_off, *scan_tmp;
-    uint32_t *spec_cnt, *spec_stop, *cnt, *rec_meta, *rec_side;
+struct Ws : chain::Tiles {
+    uint64_t *ctl, *rec_off, *side_off, *scan_tmp;
+    uint32_t *rec_meta, *rec_side;
     int32_t *rec_end;
-    uint64_t tiles, cap, total;
+    uint64_t cap, total;
 };
 static Ws layout(uint8_t *base, uint64_t n) {
     Ws w;
-    w.tiles = n / kTileBytes + 1;
+    w.tiles = chain::tiles_of(n);
     w.cap = n / kMinRecordBytes + 2;
     uint64_t off = 0;
     auto take = [&](uint64_t bytes) {
@@ -69,10 +61,6 @@ static Ws layout(uint8_t *base, uint64_t n) {
 }
 uint64_t workspace_bytes(uint64_t n_bytes) { return layout(nullptr, n_bytes).total; }
 
-__device__ __forceinline__ uint32_t ld32(const uint8_t *p) {  // (records are byte aligned)
-    return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
-}
-
 struct Rec {
     uint32_t bs, l_name, mapq, n_cig, flag;
     int32_t ref, pos, l_seq, nref, npos;
@@ -94,29 +82,6 @@ __device__ __forceinline__ Rec ld_rec(const uint8_t *p) {
 }
 __device__ __forceinline__ uint64_t fields_bytes(const Rec &r) {  // what block_size must hold at least (l_seq >= 0)
     return 32ull + r.l_name + 4ull * r.n_cig + ((uint64_t)r.l_seq + 1) / 2 + (uint64_t)r.l_seq;
-}
-
-// ---- the chain ------------------------------------------------------------------------------------------------------------
-// 0: a complete record at s (*next = the one behind it), 1: the tail (no complete record at s), 2: block_size < 32
-__device__ __forceinline__ int chain_step(const uint8_t *in, uint64_t n, uint64_t s, uint64_t *next) {
-    if (s + 4 > n) return 1;
-    const uint32_t bs = ld32(in + s);
-    if (bs < 32) return 2;
-    if (s + 4 + (uint64_t)bs > n) return 1;
-    *next = s + 4 + (uint64_t)bs;
-    return 0;
-}
-// the records that begin in [s, hi): a pure function of s
-__device__ void walk(const uint8_t *in, uint64_t n, uint64_t s, uint64_t hi, uint32_t *cnt, uint64_t *exit, uint32_t *stop) {
-    uint32_t c = 0, st = 0;
-    while (s < hi) {
-        uint64_t nx = 0;
-        st = (uint32_t)chain_step(in, n, s, &nx);
-        if (st) break;
-        c++;
-        s = nx;
-    }
-    *cnt = c, *exit = s, *stop = st;
 }
 
 // ---- speculation -------------------------------------------------------------------------------------------------------------
@@ -144,118 +109,40 @@ __device__ bool plausible(const uint8_t *in, uint64_t n, uint64_t s, int32_t n_r
     return fields_plausible(in, n, end, n_ref, false, &end2);
 }
 
-__global__ __launch_bounds__(256) void k_speculate(const uint8_t *__restrict__ in, uint64_t n, int32_t n_ref, Ws w) {
-    const uint64_t t = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (t >= w.tiles) return;
-    const uint32_t lane = threadIdx.x & 63;
-    const uint64_t lo = t * kTileBytes, hi = lo + kTileBytes < n ? lo + kTileBytes : n;
-    uint64_t entry = kNone;
-    if (t == 0) {
-        entry = 0;  // the buffer begins at a record start
-    } else {
-        for (uint64_t base = lo; base < hi; base += 64) {
-            const uint64_t cand = base + lane;
-            const bool ok = cand < hi && plausible(in, n, cand, n_ref);
-            const unsigned long long m = __ballot(ok);
-            if (m) {
-                entry = base + (uint64_t)__builtin_ctzll(m);
-                break;
-            }
-        }
+// ---- the chain (exg_chain.hpp) -----------------------------------------------------------------------------------------------
+struct BamChain {
+    int32_t n_ref;
+    // 0: a complete record at s (*next = the one behind it), 1: the tail (no complete record at s), 2: block_size < 32
+    __device__ __forceinline__ int step(const uint8_t *in, uint64_t n, uint64_t s, uint64_t *next) const {
+        if (s + 4 > n) return 1;
+        const uint32_t bs = ld32(in + s);
+        if (bs < 32) return 2;
+        if (s + 4 + (uint64_t)bs > n) return 1;
+        *next = s + 4 + (uint64_t)bs;
+        return 0;
     }
-    if (lane) return;
-    uint32_t cnt = 0, stop = 0;
-    uint64_t exit = entry;
-    if (entry != kNone) walk(in, n, entry, hi, &cnt, &exit, &stop);
-    w.spec_entry[t] = entry, w.spec_exit[t] = exit, w.spec_cnt[t] = cnt, w.spec_stop[t] = stop;
-}
+    __device__ __forceinline__ uint64_t next(const uint8_t *in, uint64_t s) const { return s + 4 + (uint64_t)ld32(in + s); }
+    __device__ __forceinline__ bool plausible(const uint8_t *in, uint64_t n, uint64_t s) const { return bam::plausible(in, n, s, n_ref); }
+};
 
-// ---- stitch -----------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_stitch(const uint8_t *__restrict__ in, uint64_t n, uint32_t flags, Ws w, exg_bam_scan_result *res) {
-    __shared__ uint64_t s_entry[kStitchChunk], s_exit[kStitchChunk];
-    __shared__ uint32_t s_cnt[kStitchChunk], s_stop[kStitchChunk];
-    __shared__ uint64_t s_cur, s_rows, s_rewalked;
-    __shared__ uint32_t s_done, s_stopped;
-    if (threadIdx.x == 0) s_cur = 0, s_rows = 0, s_rewalked = 0, s_done = 0, s_stopped = 0;
-    __syncthreads();
-    for (uint64_t c0 = 0; c0 < w.tiles; c0 += kStitchChunk) {
-        if (s_done) break;  // (uniform: written before the barrier below)
-        if (s_cur / kTileBytes >= c0 + kStitchChunk) continue;  // a record jumped over the whole chunk
-        for (uint32_t i = threadIdx.x; i < kStitchChunk && c0 + i < w.tiles; i += 256) {
-            s_entry[i] = w.spec_entry[c0 + i], s_exit[i] = w.spec_exit[c0 + i];
-            s_cnt[i] = w.spec_cnt[c0 + i], s_stop[i] = w.spec_stop[c0 + i];
-        }
-        __syncthreads();
-        if (threadIdx.x < 64) {
-            // wave 0, every lane with the same cur / rows (what differs per lane is said so).  The common case — the chain enters 64
-            // tiles in a row exactly where they were speculated — is taken 64 tiles at a step: lane l holds tile t + l and checks
-            // that its walk ends where tile t + l + 1's begins; anything else goes one tile at a time
-            const uint32_t lane = threadIdx.x;
-            const uint64_t loaded = w.tiles - c0 < kStitchChunk ? w.tiles - c0 : kStitchChunk;
-            uint64_t cur = s_cur, rows = s_rows, rewalked = s_rewalked;
-            for (;;) {
-                if (cur >= n) {
-                    s_done = 1;
-                    break;
-                }
-                const uint64_t t = cur / kTileBytes;
-                if (t >= c0 + kStitchChunk) break;
-                const uint32_t i = (uint32_t)(t - c0);
-                if (i + 64 < loaded) {
-                    const uint64_t e = s_entry[i + lane], x = s_exit[i + lane];
-                    const uint32_t c = s_cnt[i + lane];
-                    const bool ok = s_stop[i + lane] == 0 && x == s_entry[i + lane + 1] && x / kTileBytes == t + lane + 1 && (lane != 0 || e == cur);
-                    if (__all(ok)) {
-                        const uint32_t incl = wave_incl_sum(c);
-                        w.true_entry[t + lane] = e, w.row_base[t + lane] = rows + incl - c, w.cnt[t + lane] = c;
-                        rows += __shfl(incl, 63, 64);
-                        cur = __shfl((unsigned long long)x, 63, 64);
-                        continue;
-                    }
-                }
-                uint32_t cnt = s_cnt[i], stop = s_stop[i];
-                uint64_t exit = s_exit[i];
-                if (s_entry[i] != cur) {
-                    const uint64_t hi = (t + 1) * kTileBytes < n ? (t + 1) * kTileBytes : n;
-                    walk(in, n, cur, hi, &cnt, &exit, &stop);  // (all lanes the same loads)
-                    rewalked++;
-                }
-                if (!lane) w.true_entry[t] = cur, w.row_base[t] = rows, w.cnt[t] = cnt;
-                rows += cnt;
-                cur = exit;
-                if (stop) {
-                    s_done = 1, s_stopped = stop;
-                    break;
-                }
-            }
-            if (!lane) s_cur = cur, s_rows = rows, s_rewalked = rewalked;
-        }
-        __syncthreads();
+// a tail at the end of the stream is a record that runs past it; a block_size below 32 ends the chain where it stands
+struct BamStitched {
+    uint32_t flags;
+    uint64_t *ctl;
+    uint64_t tiles;
+    exg_bam_scan_result *res;
+    __device__ void operator()(uint64_t rows, uint64_t cur, uint64_t rewalked, uint32_t stopped) const {
+        uint64_t err = kNoError;
+        if (stopped == 2) err = (rows << 8) | EXG_PE_BAM_BLOCK_SIZE;
+        else if (stopped == 1 && (flags & EXG_F_EOF)) err = (rows << 8) | EXG_PE_BAM_TRUNCATED;
+        ctl[0] = err;
+        res->n_records = rows;
+        res->consumed_bytes = cur;
+        res->side_bytes = 0;
+        res->error_record = 0, res->error_offset = ~0ull, res->error_code = 0, res->flags = 0;
+        res->tiles = tiles, res->tiles_rewalked = rewalked;
     }
-    if (threadIdx.x) return;
-    // a tail at the end of the stream is a record that runs past it; a block_size below 32 ends the chain where it stands
-    uint64_t err = kNoError;
-    if (s_stopped == 2) err = (s_rows << 8) | EXG_PE_BAM_BLOCK_SIZE;
-    else if (s_stopped == 1 && (flags & EXG_F_EOF)) err = (s_rows << 8) | EXG_PE_BAM_TRUNCATED;
-    w.ctl[0] = err;
-    res->n_records = s_rows;
-    res->consumed_bytes = s_cur < n ? s_cur : n;
-    res->side_bytes = 0;
-    res->error_record = 0, res->error_offset = ~0ull, res->error_code = 0, res->flags = 0;
-    res->tiles = w.tiles, res->tiles_rewalked = s_rewalked;
-}
-
-__global__ __launch_bounds__(256) void k_index(const uint8_t *__restrict__ in, Ws w) {
-    const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (t >= w.tiles) return;
-    uint64_t s = w.true_entry[t];
-    if (s == kNone) return;
-    uint64_t row = w.row_base[t];
-    for (uint32_t k = w.cnt[t]; k; k--) {  // (the stitch counted complete records: every block_size read here lies inside the buffer)
-        w.rec_off[row++] = s;
-        s += 4 + (uint64_t)ld32(in + s);
-    }
-}
+};
 
 // ---- rows ---------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ uint32_t ndigits(uint32_t v) {
@@ -507,15 +394,14 @@ int discover(const exg_bam_scan_args *a, exg_bam_scan_result *out) {
     hipStream_t st = (hipStream_t)a->stream;
     const Ws w = layout((uint8_t *)a->d_workspace, a->n_bytes);
     const uint8_t *in = (const uint8_t *)a->d_input;
-    EXG_HIP_CHECK(hipMemsetAsync(w.true_entry, 0xFF, w.tiles * 8, st));
-    hipLaunchKernelGGL(k_speculate, dim3((uint32_t)((w.tiles + 3) / 4)), dim3(256), 0, st, in, a->n_bytes, a->n_ref, w);
-    hipLaunchKernelGGL(k_stitch, dim3(1), dim3(256), 0, st, in, a->n_bytes, a->flags, w, a->d_result);
+    const BamChain f{a->n_ref};
+    EXG_HIP_CHECK(chain::find(in, a->n_bytes, f, w, BamStitched{a->flags, w.ctl, w.tiles, a->d_result}, st));
     EXG_HIP_CHECK(hipMemcpyAsync(out, a->d_result, sizeof *out, hipMemcpyDeviceToHost, st));
     EXG_HIP_CHECK(hipStreamSynchronize(st));
     const uint64_t found = out->n_records;
     const bool with_side = !(a->flags & EXG_F_NO_STORE);
     if (found) {
-        hipLaunchKernelGGL(k_index, dim3((uint32_t)((w.tiles + 255) / 256)), dim3(256), 0, st, in, w);
+        chain::index(in, f, w, w.rec_off, st);
         hipLaunchKernelGGL(k_rows, dim3((uint32_t)((found + 3) / 4)), dim3(256), 0, st, in, found, a->n_ref, selected(a), w);
         if (with_side) launch_xscan(SideLen{w.rec_side}, found, w.side_off, w.scan_tmp, st);
     }

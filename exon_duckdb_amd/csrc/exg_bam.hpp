@@ -9,7 +9,7 @@
 namespace exg {
 namespace bam {
 
-static constexpr uint32_t kTileBytes = 32768;
+static constexpr uint32_t kTileBytes = 32768;  // (exg_chain.hpp's tile)
 static constexpr uint32_t kMinRecordBytes = 36;  // block_size + the 32 bytes of fixed fields
 
 uint64_t workspace_bytes(uint64_t n_bytes);

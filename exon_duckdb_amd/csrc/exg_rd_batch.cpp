@@ -212,7 +212,9 @@ static int open_source(exg_reader *r, std::shared_ptr<PinnedBlock> &blk, const s
     r->gz_header_prefix = 0;
     const size_t queued = getenv("EXG_SOURCE_QUEUE") ? (size_t)std::max(1, atoi(getenv("EXG_SOURCE_QUEUE"))) : r->mem_cap ? 1 : 2;
     auto make = [&](uint64_t c_begin, uint64_t c_end, bool bgzf_only, const uint64_t *marks) {
-        std::unique_ptr<SegmentProducer> prod = r->compression == kGzip    ? make_gzip_producer(r, fd, c_begin, c_end, target, path, bgzf_only, reserve, marks)
+        std::unique_ptr<SegmentProducer> prod = r->bcf ? make_bcf_producer(r, make_gzip_producer(r, fd, c_begin, c_end, bcf_input_target(target), path, true, bcf_input_reserve(target), nullptr),
+                                                                           bcf_input_reserve(target), target, path, reserve)  // (BGZF -> BCF records -> VCF text)
+                                                : r->compression == kGzip  ? make_gzip_producer(r, fd, c_begin, c_end, target, path, bgzf_only, reserve, marks)
                                                 : r->compression == kBzip2 ? make_bzip2_producer(r, fd, n, target, path, reserve)
                                                                            : make_zstd_producer(r, fd, n, c_begin, c_end, target, path, reserve, marks);
         // (EXG_OPEN_CHUNKS: the caller said it will pull chunks — the segments travel to the host from the first one on)

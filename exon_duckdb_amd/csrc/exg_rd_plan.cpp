@@ -55,7 +55,7 @@ using namespace exg_rd;
 // can a file of this format / compression be read as byte-range shards?  (text; BGZF — FEXTRA with a 'BC' subfield in the
 // first member — by members; zstd with several frames by frames)
 static bool file_is_shardable(const std::string &f, const std::string &fmt_lower, Compression comp) {
-    if (fmt_lower == "bam") return false;  // (one file is one shard: sharding BAM by BGZF members is a follow-up)
+    if (fmt_lower == "bam" || fmt_lower == "bcf") return false;  // (one file is one shard: sharding BAM / BCF by BGZF members is a follow-up)
     if (comp == kNone) return true;
     if (comp == kZstd) {
         // by frames: worth it when the file has several (pzstd, the seekable format; the zstd CLI writes one) — the walk over
@@ -207,6 +207,7 @@ extern "C" ReplacementScanResult replacement_scan(const char *uri) {
     if (ext == "fastq" || ext == "fq") res.file_type = "FASTQ";
     if (ext == "vcf") res.file_type = "VCF";
     if (ext == "bam") res.file_type = "BAM";
+    if (ext == "bcf") res.file_type = "BCF";
     if (ext == "bed") res.file_type = "BED";  // (the reference's glue throws for it, module.cpp:376-379: not reproduced)
     // (`.sam` is not replaced yet, as before read_sam_file_records was built — tests/test_bam_host.py holds `x.sam` to NULL —: the
     // table function is called by name; whether exon's ExonFileType::from_str answers "sam" is not in the reference tree)

@@ -268,8 +268,10 @@ int DecodedSource::acquire(uint64_t pos, uint64_t want, const uint8_t **d_pos, u
         if (rc) {
             // the producer failed (a checksum behind the last block, a corrupt member further on): what was decoded in front of
             // the error is handed out first — fewer bytes than asked for, not the stream's end —, the error at the next call
-            if (!error_deferred_ && cur_.hi > pos) {
-                error_deferred_ = true;
+            // (once per position: a consumer that has moved on since — the header's reader, then the first batch — is still in
+            // front of the error; one that asks again from the same place has seen all there is)
+            if (deferred_at_ != pos && cur_.hi > pos) {
+                deferred_at_ = pos;
                 break;
             }
             return rc;

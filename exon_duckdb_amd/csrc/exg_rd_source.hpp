@@ -152,7 +152,7 @@ private:
     Segment cur_;
     bool have_cur_ = false;
     uint64_t private_p0_ = ~0ull;  // where the tail began that last moved into a block of its own (acquire)
-    bool error_deferred_ = false;  // the producer's error was met while bytes in front of it were still to be handed out
+    uint64_t deferred_at_ = ~0ull;  // where the consumer stood when the producer's error was last put off (bytes in front of it were still to be handed out)
     uint64_t n_consumed_ = 0;
     std::atomic<bool> mirror_wanted_{false};
     hipStream_t d2h_stream_ = nullptr;  // the mirrors' copies (made by the first push / mirror_now that wants one)
@@ -236,6 +236,14 @@ std::unique_ptr<SegmentProducer> make_zstd_producer(exg_reader *r, int fd, uint6
 
 // exg_rd_bzip2.cpp: every bzip2 stream of file bytes [0, n) of fd (one file is one shard's: no marks)
 std::unique_ptr<SegmentProducer> make_bzip2_producer(exg_reader *r, int fd, uint64_t n, uint64_t target, const std::string &path, uint64_t reserve);
+
+// exg_rd_bcf.cpp: a BCF file's records as VCF text.  `decoded` produces the file's decoded bytes (the BGZF producer, made with
+// reserve `in_reserve`); the segments pushed hold the header's text, then the records' lines, about `target` bytes each
+std::unique_ptr<SegmentProducer> make_bcf_producer(exg_reader *r, std::unique_ptr<SegmentProducer> decoded, uint64_t in_reserve, uint64_t target,
+                                                   const std::string &path, uint64_t reserve);
+// what the BCF producer asks its decoder for: decoded BCF bytes per segment, and the room in front of them
+uint64_t bcf_input_target(uint64_t target);
+uint64_t bcf_input_reserve(uint64_t target);
 
 int plan_zstd_shard(exg_reader *r, int fd, uint64_t n, const std::string &path, uint64_t halo_want, uint64_t header_bytes, uint64_t *c_begin,
                     uint64_t *c_end, uint64_t *own_lo, uint64_t *own_hi, bool *bytes_follow);

@@ -34,6 +34,10 @@ extern "C" int exg_open(const exg_open_args *args, exg_reader **out) {
         if (r->format == EXG_FMT_BED) r->fused_algo = EXG_ALGO_FUSED_FULL;  // (one single-pass scan: exg_bed.hip; SAM below: exg_sam.hip)
     } else if (fmt == "sam") {  // (not in format_named's answers: see there)
         r->format = EXG_FMT_SAM, r->fused_algo = EXG_ALGO_FUSED_FULL;
+    } else if (fmt == "bcf") {
+        // a BCF file's records become VCF lines on the device in front of the VCF reader (exg_rd_bcf.cpp): from here on the
+        // reader is read_vcf's, on a decoded stream
+        r->format = EXG_FMT_VCF, r->bcf = true;
     } else {
         // rust/src/arrow_reader.rs:93-102
         exg::set_error("could not parse file_format %s", args->file_format);
@@ -42,7 +46,7 @@ extern "C" int exg_open(const exg_open_args *args, exg_reader **out) {
     std::string path = args->path;
     r->compression = compression_of(args);
     // a BAM file is BGZF members whatever its name or the `compression` argument says (x.bam has no .gz suffix)
-    if (r->format == EXG_FMT_BAM) r->compression = kGzip;
+    if (r->format == EXG_FMT_BAM || r->bcf) r->compression = kGzip;  // (BCF likewise: x.bcf is BGZF)
     if (args->batch_rows) r->batch_rows = args->batch_rows;
     if (r->batch_rows % 64) {
         exg::set_error("exg_open: batch_rows must be a multiple of 64 (validity words)");
@@ -58,7 +62,9 @@ extern "C" int exg_open(const exg_open_args *args, exg_reader **out) {
         r->mem_cap = strtoull(e, nullptr, 10) << 20;
         r->meter.cap = r->mem_cap;
         // (the divisor per format, and what it was measured with: exg_rd_format.hpp)
-        const uint64_t div = format_desc(r->format).mem_cap_div;
+        // (BCF: the decoded BCF segments, the transcoder's workspace and its text segments come on top of the VCF reader's own —
+        // measured with tests/test_bcf_gpu.py's 128 MiB of text under a 16 MiB cap: half the batch)
+        const uint64_t div = (uint64_t)format_desc(r->format).mem_cap_div * (r->bcf ? 2 : 1);
         if (r->mem_cap) r->device_batch_bytes = std::max<uint64_t>(64u << 10, std::min<uint64_t>(r->device_batch_bytes, (r->mem_cap / div) & ~15ull));
     }
     r->halo_want = getenv("EXG_SHARD_HALO") ? std::max<uint64_t>(16, strtoull(getenv("EXG_SHARD_HALO"), nullptr, 10)) : kShardHalo;
@@ -76,8 +82,27 @@ extern "C" int exg_open(const exg_open_args *args, exg_reader **out) {
         exg::set_error("exg_open: shards of a BAM input are not supported (shard_count %u): one file is one shard", r->shard_count);
         return EXG_E_UNSUPPORTED;
     }
+    if (r->bcf && r->shard_count > 1) {
+        exg::set_error("exg_open: shards of a BCF input are not supported (shard_count %u): one file is one shard", r->shard_count);
+        return EXG_E_UNSUPPORTED;
+    }
     int rc = list_files(r.get(), path);
     if (rc) return rc;
+    if (r->bcf) {
+        // BCF is read through BGZF (bcftools -Ob / view -O b).  An uncompressed BCF (-Ou) or anything else is refused here, by
+        // name, before a device is asked for (the reference's reader cannot read it either)
+        for (const std::string &f : r->files) {
+            unsigned char h[18] = {0};
+            FILE *fp = fopen(f.c_str(), "rb");
+            const size_t got = fp ? fread(h, 1, sizeof h, fp) : 0;
+            if (fp) fclose(fp);
+            if (!(got == 18 && h[0] == 0x1f && h[1] == 0x8b && h[2] == 8 && (h[3] & 4) && h[12] == 'B' && h[13] == 'C')) {
+                exg::set_error("file_format bcf is not supported for '%s': it is not BGZF-compressed (%s)", f.c_str(),
+                               got >= 5 && memcmp(h, "BCF\2", 4) == 0 ? "an uncompressed BCF, bcftools -Ou: write it with -Ob" : "not a BCF file");
+                return EXG_E_UNSUPPORTED;
+            }
+        }
+    }
     if (r->compression != kNone && r->compression != kGzip && r->compression != kZstd && r->compression != kBzip2) {
         exg::set_error("compression is not supported: gzip, zstd and bzip2 have device decoders, xz does not, and there is no CPU fallback");
         return EXG_E_UNSUPPORTED;

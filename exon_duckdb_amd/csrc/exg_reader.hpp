@@ -520,6 +520,7 @@ struct exg_reader {
     std::shared_ptr<void> nested_state;
     // read_bam_file_records: the header's reference names (host + device) and the scan's buffers (exg_rd_bam.cpp)
     std::shared_ptr<void> bam_state;
+    bool bcf = false;  // file_format "bcf": the records become VCF lines in the decoded stream (exg_rd_bcf.cpp); format is EXG_FMT_VCF
 
     void free_device();
     exg_reader();  // (out of line: `src` is a pointer to a type this header only declares)

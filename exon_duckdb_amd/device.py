@@ -616,3 +616,63 @@ class SamScan(BedScan):
     NAMES = ["name", "flag", "reference", "start", "end", "mapping_quality", "cigar", "mate_reference", "sequence", "quality_score"]
     INT_COLS, NULLABLE = (1, 3, 4), (2, 3, 4, 5, 7)
     N_COLS, INT_DTYPE, FMT, ARGS, ENTRY = abi.EXG_SAM_COLUMNS, "int32", abi.EXG_FMT_SAM, abi.SamScanArgs, "exg_sam_scan"
+
+
+class BcfToVcf:
+    """exg_bcf_to_vcf on decoded BCF records resident in HBM (d_input[0] is a record start): the two dictionaries as lists indexed
+    by dictionary index (bytes, or None where no ID has that index), the header's sample count, an output buffer of
+    `output_capacity` bytes.  run() returns (result block, the text written)."""
+
+    def __init__(self, n_bytes, strings, contigs, n_samples=0, output_capacity=None, device="cuda"):
+        torch = _torch()
+        self.lib = load_library()
+        self.n_bytes, self.n_samples = n_bytes, n_samples
+        self.gt_index = strings.index(b"GT") if b"GT" in strings else 0xFFFFFFFF
+        self.dicts = []
+        for names in (contigs, strings):
+            table, data = [], b""
+            for name in names:
+                table += [len(data), 0xFFFFFFFF if name is None else len(name)]
+                data += name or b""
+            d_table = torch.from_numpy(np.array(table + [0, 0], dtype=np.uint32).view(np.int32)).to(device)
+            self.dicts.append((upload(data + b"\0"), d_table, len(names)))
+        self.output_capacity = int(output_capacity if output_capacity is not None else 8 * n_bytes + 4096)
+        self.out = torch.empty(max(self.output_capacity, 1) + 64, dtype=torch.uint8, device=device)
+        self.ws_bytes = int(self.lib.exg_bcf_workspace_bytes(n_bytes, n_samples))
+        self.ws = torch.empty((self.ws_bytes + 255) // 8, dtype=torch.int64, device=device)
+        self.result = torch.zeros(8, dtype=torch.int64, device=device)
+        self.args = abi.BcfToVcfArgs()
+
+    def launch(self, d_input, n_bytes=None, flags=abi.EXG_F_EOF, output_capacity=None):
+        """one call (it synchronises) -> the result block"""
+        a = self.args
+        cap = self.output_capacity if output_capacity is None else output_capacity
+        assert cap <= self.output_capacity
+        a.d_input = d_input.data_ptr() if hasattr(d_input, "data_ptr") else d_input
+        a.n_bytes = self.n_bytes if n_bytes is None else n_bytes
+        a.flags, a.n_samples = flags, self.n_samples
+        (cb, ct, cn), (sb, st, sn) = self.dicts
+        a.d_contig_bytes, a.d_contig_table, a.n_contigs = cb.data_ptr(), ct.data_ptr(), cn
+        a.d_string_bytes, a.d_string_table, a.n_strings = sb.data_ptr(), st.data_ptr(), sn
+        a.gt_index = self.gt_index
+        a.d_output, a.output_capacity = self.out.data_ptr(), cap
+        a.d_workspace, a.workspace_bytes = self.ws.data_ptr(), self.ws_bytes
+        a.d_result = self.result.data_ptr()
+        a.stream = stream_ptr().value
+        check(self.lib.exg_bcf_to_vcf(C.byref(a)))
+        r = abi.BcfToVcfResult()
+        check(self.lib.exg_bcf_result(C.c_void_p(self.result.data_ptr()), stream_ptr(), C.byref(r)))
+        return r
+
+    def run(self, d_input, n_bytes=None, flags=abi.EXG_F_EOF, output_capacity=None, guard=0xA5):
+        """launch() with the output buffer filled with `guard` first, so that a test sees what was not written -> (result, buffer)"""
+        self.out.fill_(guard)
+        r = self.launch(d_input, n_bytes, flags, output_capacity)
+        return r, self.out.cpu().numpy().tobytes()
+
+
+def read_bcf_file_records(path, columns=None, where=None, filters=None):
+    """the rows of a BCF file through the table function (the VCF schema of the file's own header): a convenience for scripts
+    and tests.  columns / where / filters are Relation.fetchall's."""
+    from . import table_function
+    return table_function.connect().table_function("read_bcf_file_records", path).fetchall(columns=columns, where=where, filters=filters)

@@ -7,6 +7,7 @@ tests, which read like the reference's sqllogictests:
     con.table_function("read_fastq", path).count()
     con.table_function("read_fasta", path, compression="gzip").fetchall()
     con.from_path("x/test.fasta")                     # replacement scan
+    con.table_function("read_bcf_file_records", "x/calls.bcf").fetchall()   # the VCF schema of the file's own header
 """
 import ctypes as C
 

@@ -113,6 +113,16 @@ extern "C" {
 /* (43 stays unassigned, like 29 and 34: callers probe it to see "unknown parse error") */
 #define EXG_PE_CIGAR_INVALID 44       /* CIGAR scalars: a row is not [digits, one of MIDNSHP=X]+ with lengths <= 2^28 - 1 */
 #define EXG_PE_CIGAR_RANGE 45         /* extract_from_cigar: the leading and trailing insertions exceed the sequence */
+/* (46 is unassigned) */
+#define EXG_PE_BCF_RECORD_LENGTH 47   /* BCF: l_shared < 24 (the fixed fields alone are 24 bytes) */
+#define EXG_PE_BCF_TRUNCATED 48       /* BCF: a record runs past the end of the stream */
+#define EXG_PE_BCF_TYPE 49            /* BCF: a typed value of type 4, 6 or 8 .. 15, or no integer where a key / a length stands */
+#define EXG_PE_BCF_RESERVED_VALUE 50  /* BCF: one of the reserved integer values (0x82 .. 0x87 and their wider forms), or a negative GT value */
+#define EXG_PE_BCF_OVERRUN 51         /* BCF: a typed value runs past l_shared / l_indiv */
+#define EXG_PE_BCF_CHROM 52           /* BCF: CHROM is not an index of the header's contig dictionary */
+#define EXG_PE_BCF_DICT_INDEX 53      /* BCF: a FILTER / INFO / FORMAT key is not an index of the header's string dictionary */
+#define EXG_PE_BCF_NO_ALLELE 54       /* BCF: n_allele = 0 (a record has at least REF) */
+#define EXG_PE_BCF_SAMPLE_COUNT 55    /* BCF: n_sample differs from the header's sample count */
 
 /* ---- duckdb::string_t, bit-for-bit (v0.8.1 duckdb/common/types/string_type.hpp)
  * length <= 12: bytes inlined, zero padded.  Otherwise 4-byte prefix + pointer.
@@ -138,6 +148,8 @@ typedef union exg_string_t {
 #define EXG_FMT_BAM 4 /* reader level + exg_bam_scan; the chunk boundary only (new_reader refuses it) */
 #define EXG_FMT_BED 5 /* reader level + exg_bed_scan; the chunk boundary only (new_reader refuses it) */
 #define EXG_FMT_SAM 6 /* reader level + exg_sam_scan; the chunk boundary only (new_reader refuses it) */
+#define EXG_FMT_BCF 7 /* reader level (file_format "bcf": records become VCF lines on the device, exg_bcf_to_vcf, and take the
+                       * VCF path from there: both boundaries, the schema of the file's own header) */
 
 /* ---- scan flags ------------------------------------------------------------ */
 #define EXG_F_BOF 1u /* a line starts at d_input[0] (start of file, or a record-aligned batch) */
@@ -369,6 +381,52 @@ typedef struct exg_sam_scan_args {
     void *stream;
 } exg_sam_scan_args;
 
+/* BCF 2.2 records -> the VCF data lines they stand for (VCF 4.3 spec section 6.3), on decoded bytes resident in HBM.
+ * d_input begins at a record start (the caller has taken the header off).  The lines of all records that lie completely
+ * inside the buffer are written to d_output in order, each ended by LF, closed up.  The two dictionaries of the file's header
+ * are tables of {offset, length} pairs (uint32 each; length 0xFFFFFFFF: no such entry) into their bytes: the contigs, and the
+ * IDs of the FILTER / INFO / FORMAT lines (PASS = 0).  gt_index: the string dictionary's index of `GT` (~0: none).
+ * Rendering rules: INTEGRATION.md (BCF).  A float is rendered with nine significant digits in a spelling the VCF path's
+ * float parser reads back to the same bits.
+ * Records are found like BAM's (speculation per 32 KiB tile, stitch from byte 0: exactly the serial chain).  The first
+ * record in error ends the output: the lines in front of it are written, then error_code / error_record / error_offset say
+ * which.  Output that does not fit: EXG_RF_CAPACITY, the lines of the records that fit are written (nothing behind the last
+ * of them), consumed_bytes is where the next call begins and text_bytes_needed what all of them take.  Without EXG_F_EOF the
+ * tail behind the last complete record is left to the next call; with it, a tail is EXG_PE_BCF_TRUNCATED.
+ * Synchronises the stream (once: the row count comes back to the host between discovery and rendering). */
+typedef struct exg_bcf_to_vcf_result { /* 64 bytes, written by the device */
+    uint64_t n_records;         /* records rendered */
+    uint64_t consumed_bytes;    /* offset just past the last rendered record (the tail is the caller's carry) */
+    uint64_t text_bytes_needed; /* text of all complete records in front of the first error */
+    uint64_t text_bytes;        /* text written to d_output */
+    uint64_t error_record;      /* ordinal (within this buffer) of the first failing record */
+    uint64_t error_offset;      /* its byte offset in d_input */
+    uint32_t error_code;        /* EXG_PE_BCF_* (0 while records in front of the failing one did not fit) */
+    uint32_t flags;             /* EXG_RF_CAPACITY */
+    uint64_t tiles_rewalked;    /* tiles whose speculated entry was not the chain's */
+} exg_bcf_to_vcf_result;
+
+typedef struct exg_bcf_to_vcf_args {
+    const void *d_input; /* device, any alignment */
+    uint64_t n_bytes;
+    uint32_t flags;      /* EXG_F_EOF */
+    uint32_t n_samples;  /* the header's sample count */
+    const uint8_t *d_contig_bytes;
+    const uint32_t *d_contig_table; /* device: n_contigs x {offset, length} */
+    uint32_t n_contigs;
+    uint32_t n_strings;
+    const uint8_t *d_string_bytes;
+    const uint32_t *d_string_table; /* device: n_strings x {offset, length} */
+    uint32_t gt_index;
+    uint32_t reserved;
+    uint8_t *d_output; /* device, output_capacity bytes */
+    uint64_t output_capacity;
+    void *d_workspace; /* device, exg_bcf_workspace_bytes(n_bytes, n_samples), 256-byte aligned */
+    uint64_t workspace_bytes;
+    exg_bcf_to_vcf_result *d_result; /* device, 64 bytes */
+    void *stream;
+} exg_bcf_to_vcf_args;
+
 /* ---- library / device ------------------------------------------------------ */
 int exg_abi_version(void);
 /* Number of visible HIP devices, or EXG_E_NO_DEVICE. Does not initialise a context. */
@@ -389,6 +447,11 @@ int exg_bam_scan(const exg_bam_scan_args *args);
 int exg_bed_scan(const exg_bed_scan_args *args);
 /* Enqueue on args->stream; asynchronous (the result through exg_fetch_result). */
 int exg_sam_scan(const exg_sam_scan_args *args);
+/* BCF records -> VCF lines (see exg_bcf_to_vcf_args).  Synchronises args->stream. */
+uint64_t exg_bcf_workspace_bytes(uint64_t n_bytes, uint32_t n_samples);
+int exg_bcf_to_vcf(const exg_bcf_to_vcf_args *args);
+/* the 64-byte result block of exg_bcf_to_vcf, brought to the host (synchronises `stream`) */
+int exg_bcf_result(const exg_bcf_to_vcf_result *d_result, void *stream, exg_bcf_to_vcf_result *out);
 /* Synchronising copy of the 64-byte result to the host. */
 int exg_fetch_result(const exg_scan_result *d_result, void *stream, exg_scan_result *out);
 /* '\n' count of d_input[begin,end) into *d_count (device u64); used for the shard phase exchange. */

@@ -1,0 +1,506 @@
+"""read_bcf_file_records on the device.  The transcoder (exg_bcf_to_vcf: BCF records -> VCF lines) is held byte for byte — floats
+as float32 — to the independent Python renderer of tests/bcf_files.py: every typed form, records that fool the record-start
+speculation, buffers cut anywhere, output that does not fit, every record error.  The reader is held to read_vcf on the same
+records as VCF text (the reference's index.bcf / index.vcf pair first), however BGZF members and device batches fall, under a
+memory cap, with projection and pushed-down filters."""
+import ctypes as C
+import gzip
+import os
+import random
+import struct
+import zlib
+
+import numpy as np
+import pytest
+
+import bam_files as BAM
+import bcf_files as B
+from bcf_files import EOV, MISSING
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(ROOT, "tests", "golden")
+FN = "read_bcf_file_records"
+TILE = 32768
+
+SAMPLES3 = ("s1", "s2", "s3")
+INFOS = [("DP", "1", "Integer"), ("AF", "A", "Float"), ("DB", "0", "Flag"), ("AC", "A", "Integer"), ("STR", "1", "String"), ("BIG", ".", "Integer")]
+FORMATS = [("GT", "1", "String"), ("GQ", "1", "Integer"), ("PL", "G", "Integer"), ("FT", "1", "String"), ("HQ", "2", "Float")]
+
+
+def header(samples=(), idx=True):
+    return B.header_text(contigs=("c1", "chr2", "a_contig_with_a_longer_name"), filters=("q10", "s50"), infos=INFOS, formats=FORMATS,
+                         samples=samples, idx=idx)
+
+
+def K(text, name):
+    """the string dictionary's index of `name`"""
+    return B.dictionaries(text)[0].index(name.encode())
+
+
+def transcode(records, text, flags=None, capacity=None, n_bytes=None):
+    """records (bytes) through exg_bcf_to_vcf -> (result, output buffer)"""
+    from exon_duckdb_amd import abi, device
+    strings, contigs, n_samples = B.dictionaries(text)
+    d_in = device.upload(records)
+    t = device.BcfToVcf(len(records), strings, contigs, n_samples, output_capacity=capacity)
+    return t.run(d_in, n_bytes=n_bytes, flags=abi.EXG_F_EOF if flags is None else flags)
+
+
+def expect(records, text, eof=True):
+    strings, contigs, n_samples = B.dictionaries(text)
+    return B.Rendered(records, strings, contigs, n_samples, eof=eof)
+
+
+def check_against_renderer(records, text):
+    res, out = transcode(records, text)
+    want = expect(records, text)
+    assert want.error is None and res.error_code == 0, (want.error, res.error_code, res.error_record)
+    assert res.n_records == len(want.lines) and res.consumed_bytes == len(records) and res.flags == 0
+    got = out[:res.text_bytes]
+    assert res.text_bytes == res.text_bytes_needed and got.count(b"\n") == len(want.lines)
+    diff = B.text_equal(got, want.text)
+    assert diff is None, diff
+    assert out[res.text_bytes:res.text_bytes + 64] == b"\xA5" * 64       # nothing behind the text
+    return res, got
+
+
+def vcf_rows(path, fn="read_vcf", **kw):
+    from exon_duckdb_amd import table_function
+    return table_function.connect().table_function(fn, str(path)).fetchall(**kw)
+
+
+def same_rows(a, b):
+    """rows equal, NaN equal to NaN (a float that is NaN on both sides is the same value)"""
+    def norm(v):
+        if isinstance(v, float) and v != v:
+            return "nan"
+        if isinstance(v, (list, tuple)):
+            return type(v)(norm(x) for x in v)
+        if isinstance(v, dict):
+            return {k: norm(x) for k, x in v.items()}
+        return v
+    assert len(a) == len(b), (len(a), len(b))
+    for i, (x, y) in enumerate(zip(a, b)):
+        assert norm(x) == norm(y), (i, x, y)
+
+
+# ---------------------------------------------------------------- 1. the reference's pair: index.bcf is bcftools view -O b of index.vcf
+def test_index_bcf_equals_index_vcf(gpu):
+    from exon_duckdb_amd import table_function
+    from exon_duckdb_amd.arrow import new_reader
+    from exon_duckdb_amd.reader import ShardReader
+    bcf, vcf = os.path.join(GOLDEN, "bcf", "index.bcf"), os.path.join(GOLDEN, "vcf", "index.vcf")
+    con = table_function.connect()
+    rel_b, rel_v = con.table_function(FN, bcf), con.table_function("read_vcf", vcf)
+    assert rel_b.names == rel_v.names and rel_b.types == rel_v.types and rel_b.trees == rel_v.trees and len(rel_b.names) == 9
+    want = rel_v.fetchall()
+    assert len(want) == 621 and rel_b.count() == 621
+    same_rows(rel_b.fetchall(), want)
+    assert con.from_path(bcf).count() == 621                                # the replacement scan
+    # the chunk boundary: exg_schema_of and the rows
+    rb, rv = ShardReader(bcf, "bcf"), ShardReader(vcf, "vcf")
+    assert rb.names == rv.names and rb.types == rv.types and rb.trees == rv.trees
+    same_rows(rb.rows(), rv.rows())
+    assert rb.stats()["input_compression"] == 1
+    rb.close(), rv.close()
+    rb = ShardReader(bcf, "BCF", compression="uncompressed")             # the compression argument is ignored: BGZF, like BAM
+    assert rb.count() == 621
+    rb.close()
+    # the Arrow boundary (the reference's own FFI): the VCF stream
+    tb, tv = new_reader(bcf, "bcf").read_all(), new_reader(vcf, "vcf").read_all()
+    assert tb.schema == tv.schema and tb.num_rows == 621
+    same_rows(tb.to_pylist(), tv.to_pylist())
+
+
+# ---------------------------------------------------------------- 2. every form a typed value takes
+FLOAT_EDGES = [0x00000000, 0x80000000, 0x00000001, 0x807FFFFF, 0x00800000, 0x7F7FFFFF, 0xFF7FFFFF, 0x3F800000, 0x3DCCCCCD, 0x7F800000, 0xFF800000,
+               0x7FC00000, 0x7F800003, 0x501502F9, 0x2EDBE6FF, 0x4B800000, 0x461C4000]
+
+
+def every_form(text, n_sample):
+    rnd = random.Random(5)
+    k = lambda name: K(text, name)
+    recs = []
+    add = lambda **kw: recs.append(B.record(n_sample=n_sample, fmt=kw.pop("fmt", default_fmt(text, n_sample, rnd)), **kw))
+    add()                                                                   # nothing: empty ID / FILTER / INFO, one allele
+    add(chrom=2, pos=2**31 - 2, id_=b"rs1;rs2", alleles=(b"A", b"T"), qual=30.5, filters=[0])
+    add(chrom=1, pos=-1, alleles=(b"ACGT", b"A", b"<DEL>", b"*"), qual=("bits", B.F_EOV), filters=[k("q10"), k("s50")])
+    for width in (1, 2, 3):                                                 # each integer type, with missing and end-of-vector
+        add(info=[(k("BIG"), B.ints([1, MISSING, -7, 0], width=width)), (k("AC"), B.ints([5, EOV, EOV], width=width)),
+                  (k("DP"), B.ints([MISSING], width=width)), (k("DB"), B.flag()), (k("AC"), B.ints([EOV, EOV], width=width))])
+    add(info=[(k("BIG"), B.ints([127, -120, 32767, -32760, 2**31 - 1, -2**31 + 8])), (k("DP"), B.ints([-32760])), (k("AC"), B.ints([100000]))])
+    add(info=[(k("BIG"), B.ints([], width=1)), (k("STR"), B.chars(b"")), (k("STR"), B.chars(b"ab\0\0", pad_to=6)), (k("AF"), B.floats([]))])
+    add(info=[(k("BIG"), B.ints(list(range(-150, 150)))), (k("DP"), B.ints([3], long_form=True)),              # length-15 descriptors
+              (k("STR"), B.chars(bytes(rnd.choice(b"ACGTN") for _ in range(70_000)))), (k("BIG"), B.ints([1, 2, EOV], long_form=True)),
+              (k("AF"), B.floats([0.25] * 14 + [MISSING] + [1e-7] * 200 + [EOV] * 3)), (k("BIG"), B.ints([MISSING] * 64 + [7] + [EOV] * 70, width=2))])
+    add(info=[(k("AF"), B.floats([("bits", b) for b in FLOAT_EDGES[:8]])), (k("AF"), B.floats([("bits", b) for b in FLOAT_EDGES[8:]] + [MISSING])),
+              (k("AF"), B.floats([MISSING, EOV])), (k("AF"), B.floats([EOV])), (k("AF"), B.floats([0.5, 50.0, 0.0312, 123456.789, 1e-5, 3e38]))],
+        qual=("bits", 0x7FC00000))
+    add(info=[(k(name), B.flag()) for name, _, _ in INFOS] * 30, qual=0)      # 180 entries: three rounds of INFO lanes
+    add(alleles=[b"A"] + [b"<ALT%d>" % i for i in range(299)], id_=b"x" * 300)  # 300 alleles, a long-form ID
+    add(alleles=(b"A" * 40_000, b"C" * 14, b"G" * 15, b""), filters=[k("s50")] * 70)
+    return recs
+
+
+def default_fmt(text, n_sample, rnd):
+    if not n_sample:
+        return ()
+    k = lambda name: K(text, name)
+    gts = [[2, 4], [2, 5], [0, 0], [4], [2, 4, 7], [2, EOV], [0, 5, EOV], [MISSING, 3], [EOV, EOV], [40, 41]]
+    width = rnd.choice((1, 2, 3))
+    gt = [B.ints(rnd.choice(gts), width=width, pad_to=3) for _ in range(n_sample)]
+    gq = [B.ints([rnd.choice([MISSING, 0, 99, -3, 30000])], width=3) for _ in range(n_sample)]
+    pl = [B.ints(rnd.choice([[0, 30, 255], [MISSING], [10, EOV], []]), width=2, pad_to=3) for _ in range(n_sample)]
+    ft = [B.chars(rnd.choice([b"", b"PASS", b"lowq;bias", b"x" * 11]), pad_to=11) for _ in range(n_sample)]
+    hq = [B.floats(rnd.choice([[0.5, 1.5], [MISSING, 2.0], [EOV], [1e-10]]), pad_to=2) for _ in range(n_sample)]
+    return [(k("GT"), gt), (k("GQ"), gq), (k("PL"), pl), (k("FT"), ft), (k("HQ"), hq)]
+
+
+@pytest.mark.parametrize("n_sample", [0, 1, 3, 2504])
+def test_every_typed_form(gpu, n_sample):
+    text = header(samples=tuple(f"s{i}" for i in range(n_sample)))
+    recs = every_form(text, n_sample)
+    if n_sample:                                                            # FORMAT fields but not for this record / a field per key, long per-sample vectors
+        rnd = random.Random(9)
+        recs.append(B.record(n_sample=n_sample, fmt=()))
+        recs.append(B.record(n_sample=n_sample, fmt=[(K(text, "PL"), [B.ints([i % 100, MISSING] + [7] * 18, long_form=True) for i in range(n_sample)]),
+                                                     (K(text, "FT"), [B.chars(b"ab" * (i % 9), pad_to=20) for i in range(n_sample)]),
+                                                     (K(text, "GT"), [B.chars(b"0/1") for _ in range(n_sample)]),        # GT as characters: as it stands
+                                                     (K(text, "GQ"), [B.raw_value(0, 0, b"") for _ in range(n_sample)])]))
+        recs.append(B.record(n_sample=n_sample, fmt=[(K(text, name), [B.ints([rnd.randrange(-100, 100) if name != "GT" else rnd.randrange(0, 100)]) for _ in range(n_sample)]) for name, _, _ in FORMATS] * 14))
+    res, got = check_against_renderer(b"".join(recs), text)
+    assert res.n_records == len(recs)
+
+
+# ---------------------------------------------------------------- 3. discovery: the rows are the serial chain's, whatever the bytes look like
+def adversarial(text):
+    """records of 40 B .. 200 KB mixed, so that tiles are jumped over and entered mid-record; strings and integer vectors that
+    hold byte-exact copies of plausible record heads, placed at tile starts"""
+    rnd = random.Random(11)
+    k = lambda name: K(text, name)
+    head = B.record(chrom=1, pos=12345, qual=0.5, alleles=(b"A", b"C"), info=[(k("DP"), B.ints([9]))])       # a whole plausible record (and its successor)
+    decoy = head + head
+    recs, size = [], 0
+    def add(r):
+        nonlocal size
+        recs.append(r)
+        size += len(r)
+    while size < 40 * TILE:
+        kind = rnd.randrange(6)
+        if kind == 0:
+            for _ in range(rnd.randrange(1, 400)):
+                add(B.record(chrom=rnd.randrange(3), pos=rnd.randrange(1 << 28), alleles=(b"A", rnd.choice((b"C", b"GT")))))
+        elif kind == 1:       # a string that holds decoys at the next tile starts
+            pad = (-(size + 40)) % TILE
+            add(B.record(id_=b"i" * pad + (decoy + b"j" * (TILE - len(decoy))) * rnd.randrange(1, 4)))
+        elif kind == 2:       # an int8 vector whose bytes are decoys (none of them a reserved value: the decoy's bytes are small or positive)
+            body = (b"\x01" * ((-(size + 64)) % TILE) + decoy * 3 + b"\x01" * 100)
+            assert not any(0x80 <= c <= 0x87 for c in body)
+            add(B.record(info=[(k("BIG"), B.raw_value(1, len(body), body, long_form=True))]))
+        elif kind == 3:
+            add(B.record(alleles=(b"A", b"C" * rnd.randrange(30_000, 200_000))))
+        elif kind == 4:
+            add(B.record(info=[(k("BIG"), B.ints([rnd.randrange(-5, 5) for _ in range(rnd.randrange(1, 3000))]))]))
+        else:
+            add(head)
+    return recs
+
+
+def test_discovery_is_the_serial_chain(gpu):
+    from exon_duckdb_amd import abi
+    text = header()
+    recs = adversarial(text)
+    raw = b"".join(recs)
+    res, got = check_against_renderer(raw, text)
+    assert res.n_records == len(recs) and res.tiles_rewalked > 0            # the decoys cost second walks, not rows
+    # a buffer that ends inside a record: at every cut of the last record's first 64 bytes, and at a few cuts inside it
+    last = len(raw) - len(recs[-1])
+    whole = expect(raw[:last], text).text
+    for cut in list(range(0, 65)) + [len(recs[-1]) - 1, len(recs[-1]) // 2]:
+        cut = min(cut, len(recs[-1]) - 1)
+        res, out = transcode(raw[:last + cut], text, flags=0)
+        assert (res.n_records, res.consumed_bytes, res.error_code) == (len(recs) - 1, last, 0), cut
+        assert B.text_equal(out[:res.text_bytes], whole) is None
+    res, out = transcode(raw[:last + 7], text)                             # the same with EXG_F_EOF: a truncated last record
+    assert (res.n_records, res.error_code, res.error_record, res.error_offset) == (len(recs) - 1, abi.EXG_PE_BCF_TRUNCATED, len(recs) - 1, last)
+    assert B.text_equal(out[:res.text_bytes], whole) is None
+
+
+# ---------------------------------------------------------------- 4. output that does not fit
+def test_output_overflow_and_resume(gpu):
+    from exon_duckdb_amd import abi
+    text = header(samples=SAMPLES3)
+    recs = every_form(text, 3)[:9]
+    raw = b"".join(recs)
+    want = expect(raw, text)
+    _, full = check_against_renderer(raw, text)
+    ends = np.cumsum([len(ln) + 1 for ln in full.split(b"\n")[:-1]]).tolist()     # (the device's own spelling of the floats decides the lengths)
+    assert len(ends) == len(recs)
+    for cap, k in [(0, 0), (ends[0] - 1, 0), (ends[0], 1), (ends[3], 4), (ends[3] + 1, 4), (ends[-1] - 1, len(recs) - 1)]:
+        res, out = transcode(raw, text, capacity=cap)
+        assert (res.n_records, res.flags, res.error_code) == (k, abi.EXG_RF_CAPACITY, 0), cap
+        assert res.text_bytes == (ends[k - 1] if k else 0) and res.text_bytes_needed == ends[-1]
+        assert res.consumed_bytes == (want.offsets[k] if k < len(recs) else len(raw))
+        assert out[:res.text_bytes] == full[:res.text_bytes]
+        assert out[res.text_bytes:res.text_bytes + 64] == b"\xA5" * 64     # nothing behind the last fitting record
+    # going on from `consumed` yields the same text as one call
+    pos, pieces, cap = 0, [], max(np.diff([0] + ends)) + 10
+    while pos < len(raw):
+        res, out = transcode(raw[pos:], text, capacity=cap)
+        assert res.n_records > 0 and res.error_code == 0
+        pieces.append(out[:res.text_bytes])
+        pos += res.consumed_bytes
+    assert b"".join(pieces) == full
+
+
+# ---------------------------------------------------------------- 5. record errors
+def bad_records(text):
+    k = lambda name: K(text, name)
+    n_str = len(B.dictionaries(text)[0])
+    ok = dict(n_sample=3, fmt=default_fmt(text, 3, random.Random(1)))
+    return {
+        "reserved int8": (B.record(info=[(k("BIG"), B.raw_value(1, 3, bytes([1, 0x83, 2])))], **ok), B.E_RESERVED),
+        "reserved int16 in a long vector": (B.record(info=[(k("BIG"), B.raw_value(2, 100, struct.pack("<100h", *([5] * 99 + [-32768 + 7])), long_form=True))], **ok), B.E_RESERVED),
+        "reserved int32 in a sample": (B.record(n_sample=3, fmt=[(k("GQ"), [B.raw_value(3, 1, struct.pack("<i", -2**31 + 2)) for _ in range(3)])]), B.E_RESERVED),
+        "negative genotype": (B.record(n_sample=3, fmt=[(k("GT"), [B.ints([2, -3], width=1) for _ in range(3)])]), B.E_RESERVED),
+        "type 4": (B.record(info=[(k("BIG"), B.raw_value(4, 1, b"\0" * 8))], **ok), B.E_TYPE),
+        "type 6 key": (B.record(info=[(bytes([0x16, 1]), B.ints([1]))], **ok), B.E_TYPE),
+        "value past l_shared": (B.record(info=[(k("STR"), B.raw_value(7, 5000, b"abc", long_form=True))], **ok), B.E_OVERRUN),
+        "samples past l_indiv": (B.record(n_sample=3, fmt=[(k("GQ"), [B.ints([1], width=3) for _ in range(3)])], l_indiv=9), B.E_OVERRUN),
+        "chrom out of range": (B.record(chrom=3, **ok), B.E_CHROM),
+        "filter index": (B.record(filters=[n_str], **ok), B.E_DICT),
+        "info index": (B.record(info=[(n_str + 5, B.ints([1]))], **ok), B.E_DICT),
+        "format index": (B.record(n_sample=3, fmt=[(-1, [B.ints([1]) for _ in range(3)])]), B.E_DICT),
+        "no allele": (B.record(alleles=(), **ok), B.E_NO_ALLELE),
+        "sample count": (B.record(n_sample_field=2, **ok), B.E_SAMPLE_COUNT),
+        "l_shared below 24": (B.record(l_shared=23, **ok), B.E_RECORD_LENGTH),
+    }
+
+
+@pytest.mark.parametrize("case", sorted(bad_records(header(samples=SAMPLES3))))
+def test_record_errors(gpu, tmp_path, case):
+    from exon_duckdb_amd import ExgError
+    text = header(samples=SAMPLES3)
+    bad, code = bad_records(text)[case]
+    rnd = random.Random(3)
+    good = [B.record(chrom=i % 3, pos=100 + i, alleles=(b"A", b"G"), n_sample=3, fmt=default_fmt(text, 3, rnd)) for i in range(700)]
+    raw = b"".join(good[:650]) + bad + b"".join(good[650:])
+    want = expect(raw, text)
+    assert want.error == (650, code, len(b"".join(good[:650]))) and len(want.lines) == 650
+    res, out = transcode(raw, text)
+    assert (res.error_code, res.error_record, res.error_offset) == (code, 650, want.error[2]) and res.n_records == 650
+    assert res.consumed_bytes == want.error[2] and B.text_equal(out[:res.text_bytes], want.text) is None
+    # the same through the reader: the rows in front of the record, then the error by name
+    path = tmp_path / "bad.bcf"
+    path.write_bytes(B.bgzf_file(text, [raw]))
+    rows, err = read_chunks(path)
+    gpu.exg_parse_error_string.restype = C.c_char_p
+    assert len(rows) == 650 and isinstance(err, ExgError)
+    assert gpu.exg_parse_error_string(code).decode() in str(err) and "record 650" in str(err) and "bad.bcf" in str(err), str(err)
+
+
+def read_chunks(path, columns=None, **kw):
+    """-> (rows, error or None): the rows that came out before the reader failed, if it did"""
+    from exon_duckdb_amd import ExgError
+    from exon_duckdb_amd.reader import ShardReader
+    from exon_duckdb_amd.table_function import Chunk, decode_vector
+    r = ShardReader(str(path), "bcf", columns=columns, **kw)
+    rows, err = [], None
+    want = range(len(r.names)) if r.columns is None else r.columns
+    while True:
+        ch = Chunk()
+        rc = r._l.exg_next_chunk(r._r, C.byref(ch))
+        if rc != 0:
+            err = ExgError(rc, (r._l.exg_reader_error(r._r) or b"").decode("utf-8", "replace"))
+            break
+        if ch.n_rows == 0:
+            break
+        rows.extend(zip(*[decode_vector(ch.vectors[k].contents, r.trees[k]) for k in want]))
+        r._l.exg_release_chunk(r._r, C.byref(ch))
+    r.close()
+    return rows, err
+
+
+# ---------------------------------------------------------------- 6. the reader
+def cohort(text, n, n_sample, seed=21):
+    """records as a caller writes them, consistent with the header's types"""
+    rnd = random.Random(seed)
+    k = lambda name: K(text, name)
+    recs = []
+    for i in range(n):
+        n_alt = rnd.choice((1, 1, 1, 2, 3))
+        info = [(k("DP"), B.ints([rnd.randrange(5000)])), (k("AF"), B.floats([rnd.random() for _ in range(n_alt)]))]
+        if rnd.random() < 0.3:
+            info.append((k("DB"), B.flag()))
+        if rnd.random() < 0.5:
+            info.append((k("AC"), B.ints([rnd.randrange(200) for _ in range(n_alt)])))
+        if rnd.random() < 0.2:
+            info.append((k("STR"), B.chars(rnd.choice((b"x", b"tandem_repeat", b"a,b")))))
+        if rnd.random() < 0.05:
+            info.append((k("BIG"), B.ints([rnd.randrange(-70000, 70000) for _ in range(rnd.randrange(1, 600))])))
+        fmt = ()
+        if n_sample:
+            ploidy = [rnd.choice(([2, 4], [2, 5], [4, 4], [0, 0], [2 + 2 * n_alt, 3])) for _ in range(n_sample)]
+            fmt = [(k("GT"), [B.ints(g, pad_to=2) for g in ploidy]), (k("GQ"), [B.ints([rnd.choice((MISSING, 7, 99))], width=1) for _ in range(n_sample)]),
+                   (k("PL"), [B.ints([0, rnd.randrange(255), rnd.randrange(3000)], width=2) for _ in range(n_sample)])]
+            if i % 7 == 0:
+                fmt.append((k("HQ"), [B.floats([rnd.random() * 60, MISSING]) for _ in range(n_sample)]))
+        recs.append(B.record(chrom=min(2, i * 3 // n), pos=1000 + 10 * i, id_=b"" if i % 3 else b"rs%d" % i, qual=MISSING if i % 11 == 0 else rnd.random() * 100,
+                             alleles=[rnd.choice((b"A", b"CT"))] + [rnd.choice((b"G", b"T", b"<DEL>")) for _ in range(n_alt)],
+                             filters=rnd.choice((None, [0], [k("q10")], [k("q10"), k("s50")])), info=info, fmt=fmt, n_sample=n_sample))
+    return recs
+
+
+def as_vcf(text, records):
+    return text + expect(b"".join(records), text).text
+
+
+@pytest.fixture(scope="module")
+def cohort3(tmp_path_factory):
+    """3 000 three-sample records: their BCF bytes, the same as VCF text on disk, and read_vcf's rows of that (computed once)"""
+    d = tmp_path_factory.mktemp("cohort3")
+    text = header(samples=SAMPLES3)
+    recs = cohort(text, 3000, 3)
+    (d / "same.vcf").write_bytes(as_vcf(text, recs))
+    return text, recs, vcf_rows(d / "same.vcf")
+
+
+@pytest.mark.parametrize("member,batch", [(5000, None), (65280, None), (5000, 16384), (65280, 70000)])
+def test_any_segmentation(gpu, cohort3, tmp_path, monkeypatch, member, batch):
+    """BGZF blocks of 5 000 B and 65 280 B — records and the header straddle members —, and device batches small enough that every
+    batch carries a tail"""
+    text, recs, want = cohort3
+    if batch:
+        monkeypatch.setenv("EXG_DEVICE_BATCH_BYTES", str(batch))
+    else:
+        monkeypatch.delenv("EXG_DEVICE_BATCH_BYTES", raising=False)
+    path = tmp_path / "c.bcf"
+    path.write_bytes(B.bgzf_file(text, recs, member_bytes=member))
+    same_rows(vcf_rows(path, FN), want)
+    from exon_duckdb_amd.reader import ShardReader
+    r = ShardReader(str(path), "bcf")
+    assert r.count() == len(want)
+    if batch:   # a batch holds at most a segment of `batch` bytes, a quarter more, and the 64 KiB + 4 KiB of room for a carried tail
+        text_bytes = len(as_vcf(text, recs)) - len(text)
+        assert r.stats()["device_batches"] >= text_bytes // (batch + batch // 4 + 65536 + 4096) >= 4
+    r.close()
+
+
+def test_projection_filters_directory_shards(gpu, cohort3, tmp_path):
+    from exon_duckdb_amd import ExgError, abi, table_function
+    from exon_duckdb_amd.reader import ShardReader
+    from exon_duckdb_amd.table_function import F
+    text, recs, want = cohort3
+    path = tmp_path / "c.bcf"
+    path.write_bytes(B.bgzf_file(text, recs))
+    names = table_function.connect().table_function(FN, str(path)).names
+    c, p, r_ = names.index("chrom"), names.index("pos"), names.index("ref")
+    got = vcf_rows(path, FN, columns=["chrom", "pos", "ref"])
+    assert got == [(w[c], w[p], w[r_]) for w in want]
+    # pos > x AND chrom = 'y', pushed down: the rows the renderer's lines give
+    lines = [ln.split(b"\t") for ln in expect(b"".join(recs), text).lines]
+    keep = [i for i, f in enumerate(lines) if int(f[1]) > 12000 and f[0] == b"chr2"]
+    assert 0 < len(keep) < len(lines)
+    got = vcf_rows(path, FN, filters={"pos": F.cmp(">", 12000), "chrom": F.cmp("=", "chr2")})
+    same_rows(got, [want[i] for i in keep])
+    r = ShardReader(str(path), "bcf", filters="pos > 12000 AND chrom = 'chr2'")
+    assert r.count() == len(keep)
+    r.close()
+    # a directory of three files, in name order
+    d = tmp_path / "dir"
+    d.mkdir()
+    for i, (lo, hi) in enumerate(((0, 1000), (1000, 1001), (1001, 3000))):
+        (d / f"part{i}.bcf").write_bytes(B.bgzf_file(text, recs[lo:hi], member_bytes=30000))
+    same_rows(vcf_rows(d, FN), want)
+    # one file is one shard
+    with pytest.raises(ExgError) as e:
+        ShardReader(str(path), "bcf", shard_index=1, shard_count=2)
+    assert e.value.code == abi.EXG_E_UNSUPPORTED and "one file is one shard" in str(e.value)
+    gpu.exg_plan_shards.argtypes = [C.POINTER(abi.OpenArgs), C.POINTER(C.c_uint32), C.POINTER(C.c_int), C.c_uint32]
+    os.environ["EXON_GPU_SHARDS"] = "4"
+    try:
+        n, devs = C.c_uint32(0), (C.c_int * 8)()
+        a = abi.OpenArgs(str(path).encode(), b"bcf", None, 2048, 0, 0, None, 0, 1, 0, 0)
+        assert gpu.exg_plan_shards(C.byref(a), C.byref(n), devs, 8) == 0 and n.value == 1
+    finally:
+        del os.environ["EXON_GPU_SHARDS"]
+
+
+def test_header_only_truncated_and_oversized(gpu, cohort3, tmp_path, monkeypatch):
+    from exon_duckdb_amd import ExgError, abi
+    text, recs, want = cohort3
+    (tmp_path / "empty.bcf").write_bytes(B.bgzf_file(text, []))
+    assert vcf_rows(tmp_path / "empty.bcf", FN) == []
+    # a file truncated mid-member is an error, not a hang; so is a stream that ends inside a record
+    whole = B.bgzf_file(text, recs[:500], member_bytes=8000)
+    (tmp_path / "cut.bcf").write_bytes(whole[:len(whole) * 2 // 3])
+    rows, err = read_chunks(tmp_path / "cut.bcf")
+    assert isinstance(err, ExgError) and "cut.bcf" in str(err) and len(rows) < 500
+    raw = B.file_header(text) + b"".join(recs[:500])
+    (tmp_path / "tail.bcf").write_bytes(BAM.bgzf(raw[:-5]))
+    rows, err = read_chunks(tmp_path / "tail.bcf")
+    assert len(rows) == 499 and isinstance(err, ExgError) and "record 499" in str(err) and "past the end of the stream" in str(err)
+    # a header that is not BCF 2.2 / not terminated: refused with the file's name
+    for name, data in (("minor.bcf", B.file_header(text, minor=1)), ("unterminated.bcf", B.file_header(text, terminate=False)),
+                       ("nochrom.bcf", B.file_header(text.split(b"#CHROM")[0])), ("magic.bcf", b"BAM\1" + b"\0" * 40)):
+        (tmp_path / name).write_bytes(BAM.bgzf(data))
+        with pytest.raises(ExgError) as e:
+            vcf_rows(tmp_path / name, FN)
+        assert name in str(e.value), str(e.value)
+    # a single record whose line exceeds a segment is an error with a message
+    monkeypatch.setenv("EXG_DEVICE_BATCH_BYTES", str(16384))
+    big = B.record(alleles=(b"A", b"C" * 100_000), n_sample=3, fmt=default_fmt(text, 3, random.Random(2)))
+    (tmp_path / "big.bcf").write_bytes(B.bgzf_file(text, recs[:10] + [big] + recs[10:20]))
+    rows, err = read_chunks(tmp_path / "big.bcf")
+    assert isinstance(err, ExgError) and err.code == abi.EXG_E_CAPACITY and "longer than a segment" in str(err) and "record 10" in str(err)
+
+
+def test_memory_stays_bounded(gpu, tmp_path, monkeypatch):
+    """EXG_DEVICE_MEM_CAP_MB=16 on a file whose text is at least 8 x the cap, built by repeating one block of record bytes (records
+    are position independent) compressed at level 1: the peak stays under the cap, as read_vcf's does; the rows by count and
+    by a digest of pos / ref / DP"""
+    from exon_duckdb_amd.reader import ShardReader
+    cap_mb = 16
+    text = header(samples=SAMPLES3)
+    rnd = random.Random(33)
+    k = lambda name: K(text, name)
+    # long lines (300 PL values a sample: ~4 KB of text a record), so that the text is large and the rows few
+    recs = [B.record(chrom=i % 3, pos=5 * i, alleles=(rnd.choice((b"A", b"ACGT")), b"G"), info=[(k("DP"), B.ints([rnd.randrange(9000)]))], n_sample=3,
+                     fmt=[(k("GT"), [B.ints([2, 4]) for _ in range(3)]),
+                          (k("PL"), [B.ints([rnd.randrange(-9, 30000) for _ in range(300)], width=2) for _ in range(3)])]) for i in range(3000)]
+    run = b"".join(recs)
+    lines = expect(run, text).lines
+    line_bytes = sum(len(ln) + 1 for ln in lines)
+    times = (8 * (cap_mb << 20)) // line_bytes + 1
+    path = tmp_path / "big.bcf"
+    BAM.write_repeated(str(path), B.file_header(text), run, times)
+    assert line_bytes * times >= 8 * (cap_mb << 20)
+    fields = [ln.split(b"\t") for ln in lines]
+    dp = [int(dict(kv.split(b"=") for kv in f[7].split(b";") if b"=" in kv)[b"DP"]) for f in fields]
+    one = zlib.crc32(b"".join(b"%s %s %d\n" % (f[1], f[3], d) for f, d in zip(fields, dp)))
+    monkeypatch.setenv("EXG_DEVICE_MEM_CAP_MB", str(cap_mb))
+    r = ShardReader(str(path), "bcf", columns=[1, 3, 7], expect_chunks=True)
+    pos_i, ref_i, info_i = 0, 1, 2
+    n, crc, block = 0, 0, []
+    from exon_duckdb_amd.table_function import Chunk, decode_vector
+    while True:
+        ch = Chunk()
+        assert r._l.exg_next_chunk(r._r, C.byref(ch)) == 0, r._l.exg_reader_error(r._r)
+        if ch.n_rows == 0:
+            break
+        cols = [decode_vector(ch.vectors[k].contents, r.trees[k]) for k in r.columns]
+        for row in zip(*cols):
+            block.append(b"%d %s %d\n" % (row[pos_i], row[ref_i], row[info_i]["DP"]))
+            if len(block) == len(lines):
+                assert zlib.crc32(b"".join(block)) == one, n
+                block = []
+        n += ch.n_rows
+        r._l.exg_release_chunk(r._r, C.byref(ch))
+    st = r.stats()
+    r.close()
+    print(f"cap {cap_mb} MiB: peak {st['device_bytes_peak'] / 1048576:.2f} MiB, {st['decoded_segments']} segments, {st['device_batches']} batches")
+    assert n == len(lines) * times and not block
+    assert st["device_bytes_peak"] <= cap_mb << 20, st
+    assert st["device_batches"] >= 8, st
