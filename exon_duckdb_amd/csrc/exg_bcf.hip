@@ -4,7 +4,8 @@
 //   (exg_chain.hpp)  the records: record k + 1 begins at start_k + 8 + l_shared_k + l_indiv_k.  BCF's test for a plausible
 //                    record: l_shared >= 24, CHROM inside the contig dictionary, POS >= -1, n_allele >= 1, n_sample the
 //                    header's, a typed-string descriptor where the ID stands, and the successor passing the same test.
-//   k_count          one wavefront per record: validation and the exact length of its line.
+//   k_count          one wavefront per record: validation and the exact length of its line; for a record in error one lane
+//                    walks it again left to right to say which error (first_error).
 //   (prefix sum of the lengths -> the lines' offsets in the output)
 //   k_finish         one thread: how many records fit the output capacity (a binary search in the offsets), the first
 //                    error, where the caller goes on.
@@ -595,14 +596,90 @@ __device__ typename LenT<EMIT>::T render(const Ctx &c, const uint8_t *p, uint8_t
 #undef BCF_FAIL
 }
 
+// ---- which error a record reports ------------------------------------------------------------------------------------------------
+// The first one a reader meets going left to right through the record.  render<> says WHETHER a record has an
+// error, in the order that suits 64 lanes: descriptors 64 at a time before any of their values, deferred lane errors by their
+// code.  For a record that has one — and only then — one lane walks it again in the reader's order: the fixed fields, ID, the
+// alleles, FILTER and its indices, every INFO entry (key, descriptor, then its elements), every FORMAT field's key and
+// descriptor, then the samples in order and within a sample the fields in order.
+
+// a reserved value (for a genotype also a negative one) among the integers in front of the first end-of-vector
+__device__ uint32_t vec_error(const uint8_t *q, uint32_t type, uint32_t cnt, bool gt) {
+    if (type < 1 || type > 3) return 0;
+    const uint32_t sz = esize(type);
+    for (uint32_t i = 0; i < cnt; i++) {
+        const int32_t v = ld_int(q + (uint64_t)i * sz, type);
+        const uint32_t kind = int_kind(v, type);
+        if (kind == 2) break;
+        if (kind == 3 || (gt && kind == 0 && v < 0)) return EXG_PE_BCF_RESERVED_VALUE;
+    }
+    return 0;
+}
+
+__device__ __noinline__ uint32_t first_error(const Ctx c, const uint8_t *p) {
+    const uint32_t ls = ld32(p), li = ld32(p + 4), nai = ld32(p + 24), nfs = ld32(p + 28);
+    const uint32_t n_allele = nai >> 16, n_info = nai & 0xFFFF, n_fmt = nfs >> 24, n_sample = nfs & 0xFFFFFF;
+    const uint64_t lim_s = 8 + (uint64_t)ls, lim_i = lim_s + li;
+    if (!c.contig.has((int32_t)ld32(p + 8))) return EXG_PE_BCF_CHROM;
+    if (!n_allele) return EXG_PE_BCF_NO_ALLELE;
+    if (n_sample != c.n_sample) return EXG_PE_BCF_SAMPLE_COUNT;
+    uint64_t o = 32;
+    Val v;
+    for (uint32_t j = 0; j <= n_allele; j++) {  // ID, the alleles
+        if (const uint32_t e = rd_value(p, o, lim_s, &v)) return e;
+        if (v.type != 7 && v.type != 0) return EXG_PE_BCF_TYPE;
+    }
+    if (const uint32_t e = rd_value(p, o, lim_s, &v)) return e;  // FILTER
+    if (v.type > 3) return EXG_PE_BCF_TYPE;
+    for (uint32_t i = 0; v.type && i < v.cnt; i++)
+        if (!c.str.has(ld_int(p + v.data + (uint64_t)i * esize(v.type), v.type))) return EXG_PE_BCF_DICT_INDEX;
+    for (uint32_t j = 0; j < n_info; j++) {
+        int32_t key = 0;
+        if (const uint32_t e = rd_typed_int(p, o, lim_s, &key)) return e;
+        if (!c.str.has(key)) return EXG_PE_BCF_DICT_INDEX;
+        if (const uint32_t e = rd_value(p, o, lim_s, &v)) return e;
+        if (const uint32_t e = vec_error(p + v.data, v.type, v.cnt, false)) return e;
+    }
+    if (!n_fmt || !n_sample) return 0;
+    o = lim_s;
+    for (uint32_t f = 0; f < n_fmt; f++) {
+        int32_t key = 0;
+        uint32_t type = 0, cnt = 0;
+        if (const uint32_t e = rd_typed_int(p, o, lim_i, &key)) return e;
+        if (!c.str.has(key)) return EXG_PE_BCF_DICT_INDEX;
+        if (const uint32_t e = rd_desc(p, o, lim_i, &type, &cnt)) return e;
+        const uint64_t bytes = (uint64_t)n_sample * cnt * esize(type);
+        if (o + bytes > lim_i) return EXG_PE_BCF_OVERRUN;
+        o += bytes;
+    }
+    for (uint32_t s = 0; s < n_sample; s++) {
+        o = lim_s;
+        for (uint32_t f = 0; f < n_fmt; f++) {  // (the fields were validated above)
+            int32_t key = 0;
+            uint32_t type = 0, cnt = 0;
+            (void)rd_typed_int(p, o, lim_i, &key);
+            (void)rd_desc(p, o, lim_i, &type, &cnt);
+            const uint64_t one = (uint64_t)cnt * esize(type);
+            if (const uint32_t e = vec_error(p + o + s * one, type, cnt, (uint32_t)key == c.gt)) return e;
+            o += n_sample * one;
+        }
+    }
+    return 0;
+}
+
 __global__ __launch_bounds__(256) void k_count(const uint8_t *__restrict__ in, uint64_t n_rows, Ctx c, Ws w) {
     const uint64_t r = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= n_rows) return;
     const uint32_t lane = threadIdx.x & 63;
     uint32_t code = 0;
     const uint64_t len = render<false>(c, in + w.rec_off[r], nullptr, lane, &code);
-    if (!code && len > 0x7FFFFFFFull) code = EXG_PE_FIELD_TOO_LONG;
     if (lane) return;
+    if (code) {  // which of the record's errors: the leftmost
+        const uint32_t first = first_error(c, in + w.rec_off[r]);
+        code = first ? first : code;
+    } else if (len > 0x7FFFFFFFull) {
+        code = EXG_PE_FIELD_TOO_LONG;
+    }
     w.rec_len[r] = code ? 0 : len;
     if (code) atomicMin((unsigned long long *)&w.ctl[0], (unsigned long long)((r << 8) | code));
 }

@@ -390,7 +390,9 @@ typedef struct exg_sam_scan_args {
  * float parser reads back to the same bits.
  * Records are found like BAM's (speculation per 32 KiB tile, stitch from byte 0: exactly the serial chain).  The first
  * record in error ends the output: the lines in front of it are written, then error_code / error_record / error_offset say
- * which.  Output that does not fit: EXG_RF_CAPACITY, the lines of the records that fit are written (nothing behind the last
+ * which.  error_code is the first error a reader meets going left to right through that record (fixed fields, ID, alleles,
+ * FILTER, each INFO entry with its elements, the FORMAT fields' descriptors, then the samples in order), not the lowest code
+ * and not the order the device happens to look in.  Output that does not fit: EXG_RF_CAPACITY, the lines of the records that fit are written (nothing behind the last
  * of them), consumed_bytes is where the next call begins and text_bytes_needed what all of them take.  Without EXG_F_EOF the
  * tail behind the last complete record is left to the next call; with it, a tail is EXG_PE_BCF_TRUNCATED.
  * Synchronises the stream (once: the row count comes back to the host between discovery and rendering). */

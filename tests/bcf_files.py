@@ -227,6 +227,8 @@ def _elements(b, t, n, o):
 
 
 def render_value(b, t, n, o):
+    if t == 0:          # no data whatever the count says
+        return b"."
     if t == 7:
         s = bytes(b[o:o + n]).split(b"\0")[0]
         return s or b"."

@@ -276,6 +276,19 @@ def bad_records(text):
         "no allele": (B.record(alleles=(), **ok), B.E_NO_ALLELE),
         "sample count": (B.record(n_sample_field=2, **ok), B.E_SAMPLE_COUNT),
         "l_shared below 24": (B.record(l_shared=23, **ok), B.E_RECORD_LENGTH),
+        # two faults in one record: the first one going left to right is reported, whichever the device meets first
+        "two: filter index, then type 4": (B.record(filters=[n_str], info=[(k("BIG"), B.raw_value(4, 1, b"\0" * 8))], **ok), B.E_DICT),
+        "two: filter type 4, then info index": (B.record(filter_value=B.raw_value(4, 1, b"\0"), info=[(n_str + 5, B.ints([1]))], **ok), B.E_TYPE),
+        "two: reserved int8, then info index": (B.record(info=[(k("BIG"), B.raw_value(1, 3, bytes([1, 0x83, 2]))), (n_str + 5, B.ints([1]))], **ok), B.E_RESERVED),
+        "two: info index, then reserved int8": (B.record(info=[(n_str + 5, B.ints([1])), (k("BIG"), B.raw_value(1, 3, bytes([1, 0x83, 2])))], **ok), B.E_DICT),
+        "two: filter index, then reserved int8": (B.record(filters=[0, n_str], info=[(k("BIG"), B.raw_value(1, 3, bytes([1, 0x83, 2])))], **ok), B.E_DICT),
+        "two: reserved int16 in a long vector, then type 6": (B.record(info=[(k("BIG"), B.raw_value(2, 100, struct.pack("<100h", *([5] * 99 + [-32768 + 7])), long_form=True)),
+                                                                              (k("DP"), B.raw_value(6, 1, b"\0"))], **ok), B.E_RESERVED),
+        "two: reserved info value, then format index": (B.record(info=[(k("BIG"), B.raw_value(1, 3, bytes([1, 0x83, 2])))], n_sample=3,
+                                                                 fmt=[(-1, [B.ints([1]) for _ in range(3)])]), B.E_RESERVED),
+        # (every FORMAT descriptor is read before any sample: the second field's type comes first)
+        "two: negative genotype, then type 4 in the next field": (B.record(n_sample=3, fmt=[
+            (k("GT"), [B.ints([2, -3], width=1) for _ in range(3)]), (k("GQ"), [B.raw_value(4, 1, b"\0") for _ in range(3)])]), B.E_TYPE),
     }
 
 
