@@ -11,6 +11,11 @@ namespace exg {
 // thread-local error text returned by exg_last_error_message()
 void set_error(const char *fmt, ...);
 
+// exg_gzip.cpp: the RFC 1952 header of the member at data[pos] (what zlib accepts).  EXG_OK, kGzipHeaderShort (it runs past
+// data[n)) or EXG_E_PARSE; *bsize: BSIZE of its 'BC' subfield, -1 without one
+constexpr int kGzipHeaderShort = -1;
+int gzip_header(const uint8_t *data, uint64_t n, uint64_t pos, uint64_t *hdr_len, int64_t *bsize);
+
 #define EXG_HIP_CHECK(expr)                                                                   \
     do {                                                                                      \
         hipError_t _e = (expr);                                                               \

@@ -312,7 +312,7 @@ static int open_source(exg_reader *r, std::shared_ptr<PinnedBlock> &blk, const s
             r->range_eof = true;  // (a shard of a FASTA is a FASTA file of its own)
         }
     } else {
-        r->src = make(0, n, false, nullptr);
+        r->src = make(0, n, r->format == EXG_FMT_BAM, nullptr);  // (a BAM file is BGZF, SAM spec 4.1: any other gzip member in it is refused, like in a BCF)
         if (has_text_header(r)) {
             int rc = source_header_prefix(r, r->src.get(), *out_blk);
             if (rc) return rc;

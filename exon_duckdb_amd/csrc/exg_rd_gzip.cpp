@@ -103,15 +103,18 @@ private:
     int new_segment(SegmentSink &sink, uint64_t out_bytes, Segment *seg, std::string *err);
     int bgzf_run(SegmentSink &sink, std::string *err);
     int bgzf_issue(SegmentSink &sink, Lane &l, bool *not_bgzf, std::string *err);
-    int bgzf_finish(Lane &l, std::string *err);
+    int bgzf_finish(Lane &l, uint64_t *good_bytes, std::string *err);
     int plain_member(SegmentSink &sink, std::string *err);
     int small_member(SegmentSink &sink, uint64_t stream_off, std::string *err);
     int big_member(SegmentSink &sink, uint64_t stream_off, std::string *err);
     int crc_of(const void *d, uint64_t n, hipStream_t st, uint32_t *crc, std::string *err);
     int read_trailer(uint64_t at, uint32_t *crc, uint32_t *isize, std::string *err);
+    bool wrong_size(uint64_t member_end, std::string *err);
 
     int device_, fd_;
     uint64_t c_pos_, c_end_, target_;
+    uint64_t lim_ = 0;  // the member being decoded ends at or in front of it: its BC subfield's end, else c_end_ (plain_member)
+    bool sized_ = false;  // ... it has a BC subfield: it ends AT lim_
     uint64_t member_round_ = 0;  // decoded bytes a round of the chunked decoder aims at
     std::string path_;
     bool bgzf_only_;
@@ -162,7 +165,7 @@ int GzipProducer::new_segment(SegmentSink &sink, uint64_t out_bytes, Segment *se
 int GzipProducer::read_trailer(uint64_t at, uint32_t *crc, uint32_t *isize, std::string *err) {
     uint8_t t[8];
     size_t got = 0;
-    while (at + 8 <= c_end_ && got < 8) {
+    while (at + 8 <= lim_ && got < 8) {
         const ssize_t k = pread(fd_, t + got, 8 - got, (off_t)(at + got));
         if (k <= 0) break;
         got += (size_t)k;
@@ -253,13 +256,8 @@ int GzipProducer::bgzf_issue(SegmentSink &sink, Lane &l, bool *not_bgzf, std::st
         if (mem.size() >= 0x7FFFFFFFu) break;
     }
     if (mem.empty()) {
-        // not a (whole) BGZF member at c_pos_: another kind of gzip member (the caller looks), or a truncated file
-        const uint8_t *h = pk.at(rel, 18);
-        const bool looks_bgzf = h && h[0] == 0x1f && h[1] == 0x8b && h[2] == 8 && (h[3] & 4) && h[12] == 'B' && h[13] == 'C';
-        if (looks_bgzf || !h) {
-            *err = "truncated gzip member at byte " + std::to_string(c_pos_) + in_file(path_);
-            return EXG_E_PARSE;
-        }
+        // not a (whole) BGZF member at c_pos_: another kind of gzip member, or a truncated file — the caller looks (a member
+        // with a 'BC' subfield that this walk refuses is still a gzip member: plain_member reads it, or says what is wrong)
         *not_bgzf = true;
         return EXG_OK;
     }
@@ -333,14 +331,24 @@ void GzipProducer::start_read(Lane &l, uint64_t a0, uint64_t len) {
     });
 }
 
-int GzipProducer::bgzf_finish(Lane &l, std::string *err) {
+// *good_bytes: decoded bytes of the members in front of the first one that fails (all of them when none does)
+int GzipProducer::bgzf_finish(Lane &l, uint64_t *good_bytes, std::string *err) {
+    *good_bytes = 0;
     PRODUCER_HIP(hipEventSynchronize(l.ev));
     const exg_inflate_member *m = (const exg_inflate_member *)l.tab.p;
     const exg_inflate_status *s = (const exg_inflate_status *)(l.tab.p + l.k * sizeof(exg_inflate_member));
     const uint32_t *c = (const uint32_t *)((const char *)s + l.k * sizeof(exg_inflate_status));
     for (uint64_t i = 0; i < l.k; i++) {
+        *good_bytes = m[i].out_off - m[0].out_off;
         if (s[i].code || s[i].produced != m[i].out_cap) {
             *err = "corrupt deflate stream (member " + std::to_string(l.first_member + i) + ", code " + std::to_string(s[i].code) + ")" + in_file(path_);
+            return EXG_E_PARSE;
+        }
+        // BSIZE binds: the DEFLATE stream ends right in front of the trailer (no slack inside the member, no BSIZE that takes in
+        // bytes of the next member)
+        if (s[i].consumed + 8 != m[i].comp_size) {
+            *err = "corrupt gzip stream: the deflate stream of member " + std::to_string(l.first_member + i) + " ends " + std::to_string(s[i].consumed) +
+                   " bytes in, its BSIZE says " + std::to_string(m[i].comp_size - 8) + in_file(path_);
             return EXG_E_PARSE;
         }
         if (c[i] != l.crc_expect[i]) {
@@ -348,6 +356,7 @@ int GzipProducer::bgzf_finish(Lane &l, std::string *err) {
             return EXG_E_PARSE;
         }
     }
+    if (l.k) *good_bytes = m[l.k - 1].out_off + m[l.k - 1].out_cap - m[0].out_off;
     return EXG_OK;
 }
 
@@ -389,7 +398,7 @@ int GzipProducer::bgzf_run(SegmentSink &sink, std::string *err) {
         // the window after the ones in flight is read while this thread waits for the device below: its lane is the one that
         // will be issued next, idle as soon as its last segment has been handed over
         auto read_ahead = [&] {
-            static const bool off = getenv("EXG_GZ_NO_READAHEAD") != nullptr;
+            const bool off = getenv("EXG_GZ_NO_READAHEAD") != nullptr;  // (read per window, not once per process: a test switches it)
             if (off || stop || c_pos_ >= c_end_ || lanes_.size() <= next_lane) return;
             Lane &nl = *lanes_[next_lane];
             if (nl.ra_valid || nl.ra.joinable()) return;
@@ -403,9 +412,20 @@ int GzipProducer::bgzf_run(SegmentSink &sink, std::string *err) {
         Lane &l = *lanes_[inflight.front()];
         std::string e2;
         trace_at("P finish-wait", l.first_member);
-        const int frc = bgzf_finish(l, &e2);
+        uint64_t good = 0;
+        const int frc = bgzf_finish(l, &good, &e2);
         trace_at("P finished", l.first_member);
         if (frc) {
+            // the members in front of the failing one are handed out first, like a streaming decoder hands out what it decoded
+            // before it fails (big_member does the same with a wrong trailer)
+            if (good && frc == EXG_E_PARSE && hipMemsetAsync(const_cast<uint8_t *>(l.seg.at(l.seg.lo + good)), 0, 64, l.st) == hipSuccess &&
+                hipStreamSynchronize(l.st) == hipSuccess) {
+                inflight.pop_front();
+                l.seg.hi = l.seg.lo + good;
+                l.seg.last = false;
+                pushed_last_ = false;
+                (void)sink.push(std::move(l.seg));
+            }
             drain();
             *err = e2;
             return frc;
@@ -431,34 +451,63 @@ int GzipProducer::bgzf_run(SegmentSink &sink, std::string *err) {
 
 // ---- a member that does not state its size ----------------------------------------------------------------------------
 int GzipProducer::plain_member(SegmentSink &sink, std::string *err) {
-    // the RFC 1952 header (FEXTRA / FNAME / FCOMMENT / FHCRC are skipped by the index walk of exg_gzip.cpp)
-    const size_t peek = (size_t)std::min<uint64_t>(c_end_ - c_pos_, 70000);
-    std::vector<uint8_t> head(peek);
-    size_t got = 0;
-    while (got < peek) {
-        const ssize_t k = pread(fd_, head.data() + got, peek - got, (off_t)(c_pos_ + got));
-        if (k <= 0) break;
-        got += (size_t)k;
+    // the RFC 1952 header (exg::gzip_header of exg_gzip.cpp: FEXTRA / FNAME / FCOMMENT of any length, FHCRC verified).  FNAME and
+    // FCOMMENT have no length limit: the peek grows until the header is whole or the file ends
+    std::vector<uint8_t> head;
+    uint64_t hdr_len = 0;
+    int64_t bsize = -1;
+    for (size_t peek = 4096;; peek *= 16) {
+        peek = (size_t)std::min<uint64_t>(c_end_ - c_pos_, peek);
+        size_t got = head.size();
+        head.resize(peek);
+        while (got < peek) {
+            const ssize_t k = pread(fd_, head.data() + got, peek - got, (off_t)(c_pos_ + got));
+            if (k <= 0) break;
+            got += (size_t)k;
+        }
+        head.resize(got);
+        if (got < 18) {  // (no member is shorter: 10 bytes of header, an empty DEFLATE stream, the trailer)
+            *err = "invalid gzip header (member at byte " + std::to_string(c_pos_) + ")" + in_file(path_);
+            return EXG_E_PARSE;
+        }
+        const int rc = exg::gzip_header(head.data(), got, 0, &hdr_len, &bsize);
+        if (rc == exg::kGzipHeaderShort && got == peek && c_pos_ + peek < c_end_) continue;
+        if (rc == exg::kGzipHeaderShort) {
+            *err = "truncated gzip member at byte " + std::to_string(c_pos_) + " (the file ends inside its header)" + in_file(path_);
+            return EXG_E_PARSE;
+        }
+        if (rc) {
+            *err = std::string(exg_last_error_message()) + " (member at byte " + std::to_string(c_pos_) + ")" + in_file(path_);
+            return EXG_E_PARSE;
+        }
+        break;
     }
-    exg_inflate_member m;
-    uint64_t k = 0, total = 0;
-    int open_ended = 0;
-    const int rc = exg_gzip_index(head.data(), got, 0, &m, 1, &k, &total, &open_ended);
-    if (rc == EXG_E_CAPACITY) {  // (a sized member first: BGZF in a window the walk above could not finish — a truncated file)
-        *err = "truncated gzip member at byte " + std::to_string(c_pos_) + in_file(path_);
-        return EXG_E_PARSE;
-    }
-    if (rc || k == 0) {
-        const std::string what = rc ? exg_last_error_message() : "invalid gzip header";
-        *err = what + " (member at byte " + std::to_string(c_pos_) + ")" + in_file(path_);
+    // A 'BC' subfield binds, whichever path decodes the member (SAM spec 4.1: BSIZE = the member's size - 1): zlib, which
+    // skips FEXTRA unread, takes a member whose BSIZE is wrong
+    const uint64_t bc_end = bsize >= 0 ? c_pos_ + (uint64_t)bsize + 1 : 0;
+    if (bsize >= 0 && (bc_end > c_end_ || bc_end < c_pos_ + hdr_len + 8)) {
+        *err = (bc_end > c_end_ ? "truncated gzip member at byte " : "invalid gzip member at byte ") + std::to_string(c_pos_) + " (its BC subfield says " +
+               std::to_string(bsize + 1) + " bytes)" + in_file(path_);
         return EXG_E_PARSE;
     }
     n_members_++;
-    const uint64_t stream_off = c_pos_ + m.comp_off;
+    const uint64_t stream_off = c_pos_ + hdr_len;
+    // the decoders read no byte behind lim_ (a BSIZE that is too small ends the member early) and, for a sized member, want the
+    // trailer to end there (wrong_size)
+    lim_ = bc_end ? bc_end : c_end_;
+    sized_ = bc_end != 0;
     static const uint64_t stream_min = getenv("EXG_STREAM_MIN_BYTES") ? strtoull(getenv("EXG_STREAM_MIN_BYTES"), nullptr, 10) : (128ull << 10);  // (one wavefront does ~13 MB/s: 4 MB took 0.3 s)
     static const bool stream_ok = !getenv("EXG_NO_STREAM_INFLATE");
-    if (stream_ok && c_end_ - stream_off >= stream_min) return big_member(sink, stream_off, err);
+    if (stream_ok && lim_ - stream_off >= stream_min) return big_member(sink, stream_off, err);
     return small_member(sink, stream_off, err);
+}
+
+// a member with a 'BC' subfield whose trailer does not end where its BSIZE says
+bool GzipProducer::wrong_size(uint64_t member_end, std::string *err) {
+    if (!sized_ || member_end == lim_) return false;
+    *err = "corrupt gzip stream: member " + std::to_string(n_members_ - 1) + " ends at byte " + std::to_string(member_end) + ", its BC subfield says " +
+           std::to_string(lim_) + in_file(path_);
+    return true;
 }
 
 // one wavefront: the member (and whatever follows it in the file) is at most a few hundred KiB of input
@@ -468,13 +517,13 @@ int GzipProducer::small_member(SegmentSink &sink, uint64_t stream_off, std::stri
     Lane &l = *lp;
     const uint64_t a0 = stream_off & ~15ull;
     // with the chunked decoder switched off a big member comes here too: bounded by what one block may hold
-    const uint64_t len = c_end_ - a0;
+    const uint64_t len = lim_ - a0;
     if (!l.pin.ensure((size_t)len + 64) || !l.d_comp.ensure((size_t)len + 64)) {
         *err = "out of memory for the compressed bytes of '" + path_ + "'";
         return EXG_E_HIP;
     }
     if (int rc = read_to_device(device_, fd_, a0, (size_t)len, l.pin.p, (char *)l.d_comp.p, l.st, path_, err)) return rc;
-    const uint64_t comp_size = c_end_ - stream_off;
+    const uint64_t comp_size = lim_ - stream_off;
     // DEFLATE expands at most 1032:1; `cat a.vcf.gz b.vcf.gz` of highly compressible members must not be reported as
     // corrupt for outgrowing a guessed ratio.  A big member (only with the chunked decoder off) gets 8:1 + its ISIZE.
     uint64_t bound = comp_size < (128u << 10) ? comp_size * 1032 + 65536 : comp_size * 8 + 65536;
@@ -517,6 +566,7 @@ int GzipProducer::small_member(SegmentSink &sink, uint64_t stream_off, std::stri
         *err = "corrupt gzip stream does not have a matching checksum (member " + std::to_string(n_members_ - 1) + " of '" + path_ + "')";
         rc = EXG_E_PARSE;
     }
+    if (!rc && wrong_size(stream_off + h->s.consumed + 8, err)) rc = EXG_E_PARSE;
     if (!rc && hipMemsetAsync((char *)seg.buf + base + h->s.produced, 0, 64, l.st) != hipSuccess) rc = EXG_E_HIP;
     if (!rc && hipStreamSynchronize(l.st) != hipSuccess) rc = EXG_E_HIP;
     if (rc) {
@@ -570,13 +620,13 @@ int GzipProducer::big_member(SegmentSink &sink, uint64_t stream_off, std::string
         uint64_t want = (uint64_t)((double)member_round_ / std::max(1.0, ratio_)) + (64u << 10);
         want = std::max<uint64_t>(want, 256u << 10) * grow;
         if (getenv("EXG_STREAM_ROUND_BYTES")) want = strtoull(getenv("EXG_STREAM_ROUND_BYTES"), nullptr, 10) * grow;
-        uint64_t len = std::min<uint64_t>(want, c_end_ - a0);
+        uint64_t len = std::min<uint64_t>(want, lim_ - a0);
         // the window this lane read ahead, if it holds where the round before really ended (+ a good part of a round)
         l.join_read();
         bool have = false;
         if (l.ra_valid) {
             l.ra_valid = false;
-            have = l.ra_ok && grow == 1 && a0 >= l.ra_a0 && (l.ra_a0 + l.ra_len >= c_end_ || a0 + len / 2 <= l.ra_a0 + l.ra_len);
+            have = l.ra_ok && grow == 1 && a0 >= l.ra_a0 && (l.ra_a0 + l.ra_len >= lim_ || a0 + len / 2 <= l.ra_a0 + l.ra_len);
             if (have) {
                 a0 = l.ra_a0;  // (bytes in front of the block header are skipped by start_bit)
                 len = l.ra_len;
@@ -584,7 +634,7 @@ int GzipProducer::big_member(SegmentSink &sink, uint64_t stream_off, std::string
                 (void)hipGetLastError();  // (its copies must not land in the buffer read next)
             }
         }
-        const bool partial = a0 + len < c_end_;
+        const bool partial = a0 + len < lim_;
         if (!have) {
             if (!l.pin.ensure((size_t)len + 64) || !l.d_comp.ensure((size_t)len + 64)) {
                 *err = "out of memory for a window of compressed bytes of '" + path_ + "'";
@@ -598,7 +648,7 @@ int GzipProducer::big_member(SegmentSink &sink, uint64_t stream_off, std::string
             const uint64_t chunk = std::max<uint64_t>(32u << 10, (len / 3900 + 16383) & ~16383ull);
             const uint64_t slack = std::max<uint64_t>(4u << 20, 8 * chunk);
             const uint64_t na0 = (a0 + len > slack ? a0 + len - slack : 0) & ~15ull;
-            if (na0 > a0) start_read(*lanes2[li ^ 1], na0, std::min<uint64_t>(want + slack, c_end_ - na0));
+            if (na0 > a0) start_read(*lanes2[li ^ 1], na0, std::min<uint64_t>(want + slack, lim_ - na0));
         }
         PRODUCER_HIP(hipMemsetAsync((char *)l.d_comp.p + len, 0, 64, l.st));
         exg_inflate_round_args a;
@@ -669,6 +719,7 @@ int GzipProducer::big_member(SegmentSink &sink, uint64_t stream_off, std::string
                 *err = "corrupt gzip stream does not have a matching checksum ('" + path_ + "')";
                 trc = EXG_E_PARSE;
             }
+            if (!trc && wrong_size(trailer + 8, err)) trc = EXG_E_PARSE;
             if (trc) {
                 // the rows of this round are handed out before the error, like a streaming decoder hands out what it decoded
                 // before it fails at the trailer (flate2 behind a BufReader: rust/src/arrow_reader.rs:60-91); the zstd
@@ -707,14 +758,9 @@ int GzipProducer::run(SegmentSink &sink, std::string *err) {
             *err = "not a BGZF member at byte " + std::to_string(c_pos_) + " of '" + path_ + "'";
             rc = EXG_E_PARSE;
         } else {
-            const uint8_t *h = pk.at(c_pos_, 18);
-            const bool looks_bgzf = h && h[0] == 0x1f && h[1] == 0x8b && h[2] == 8 && (h[3] & 4) && h[12] == 'B' && h[13] == 'C';
-            if (looks_bgzf) {  // a BGZF header whose member does not fit the file: the walk above says why
-                *err = "truncated gzip member at byte " + std::to_string(c_pos_) + in_file(path_);
-                rc = EXG_E_PARSE;
-            } else {
-                rc = plain_member(sink, err);
-            }
+            // any other RFC 1952 member — one whose 'BC' subfield stands beside FNAME / FCOMMENT / FHCRC or in a long FEXTRA, or
+            // whose ISIZE is beyond a BGZF block's 64 KiB, included: plain_member holds it to its BSIZE
+            rc = plain_member(sink, err);
         }
         if (rc) return rc;
     }

@@ -759,7 +759,8 @@ typedef struct exg_inflate_status {
 } exg_inflate_status;
 /* Host: index the gzip members of data[start, n) (RFC 1952 framing).  Members that carry their size (BGZF 'BC'
  * subfield) are all returned; a member of unknown size is returned last with *open_ended = 1 (inflate it, then
- * index again from comp_off + consumed + 8).  *total_out is in/out: running sum of the output offsets. */
+ * index again from comp_off + consumed + 8).  *total_out is in/out: running sum of the output offsets.
+ * A header zlib refuses is refused (EXG_E_PARSE): wrong magic, CM != 8, a reserved FLG bit, an FHCRC that does not match. */
 int exg_gzip_index(const uint8_t *data, uint64_t n, uint64_t start, exg_inflate_member *members, uint64_t cap,
                    uint64_t *n_members, uint64_t *total_out, int *open_ended);
 /* One wavefront per member; d_members / d_status are device arrays; d_comp 16-byte aligned. Asynchronous. */

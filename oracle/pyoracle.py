@@ -442,6 +442,17 @@ def replacement_scan(uri):
 #   zstd  every frame is decoded, skippable frames are skipped; bytes that begin no frame, a frame that ends early, a
 #         Content_Checksum that does not match are errors;
 #   an error is reported when the rows in front of it have been handed out (through SQL: the query fails).
+# Where the gzip reader differs from this function on purpose (tests/gzip_members.py builds the cases, tests/test_oracle_rules.py
+# names them, DESIGN 2 notes them):
+#   BSIZE binds    a member whose FEXTRA holds a 'BC' subfield with SLEN = 2 (BGZF, SAM spec 4.1) states its own size, BSIZE + 1:
+#                  the reader holds it to that — a BSIZE that is too small, too large, below header + trailer, beyond the file's end
+#                  or that takes in the next member is an error, and so are bytes between the DEFLATE stream and the trailer.  zlib
+#                  skips FEXTRA unread: this function reads such a file without an error.  (Of two such subfields the last counts.)
+#   the member the error lies in    this function hands out every byte zlib decoded before the error — a part of the member that is
+#                  cut short — and nothing of a member whose trailer is wrong (one-shot zlib fails before it returns a byte).  The
+#                  reader hands out whole members in front of the error and nothing of a small or BGZF member that fails; of a big
+#                  member (128 KiB and more, decoded in rounds) the rounds decoded before the trailer was read — all of its rows —
+#                  come first, as from a streaming decoder.  The members IN FRONT of the failing one are handed out by both.
 def decode_by_rule(data: bytes, compression: str):
     """-> (decoded bytes in front of the first error, error text or None)"""
     import zlib

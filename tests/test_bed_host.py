@@ -179,13 +179,15 @@ def test_catalog_replacement_scan_and_bind():
 
 def test_new_reader_says_chunk_boundary_only():
     from exon_duckdb_amd import load_library
+    from exon_duckdb_amd._lib import LIB_PATH
 
     class Stream(C.Structure):
         _fields_ = [("f", C.c_void_p * 5)]
 
     class Result(C.Structure):
         _fields_ = [("error", C.c_char_p)]
-    lib = load_library()
+    load_library()
+    lib = C.CDLL(LIB_PATH)      # a handle of this test's own: the shared one keeps the signature exon_duckdb_amd.arrow gave new_reader
     lib.new_reader.restype = Result
     lib.new_reader.argtypes = [C.POINTER(Stream), C.c_char_p, C.c_size_t, C.c_char_p, C.c_char_p, C.c_char_p]
     st = Stream()

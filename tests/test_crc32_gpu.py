@@ -10,6 +10,8 @@ import zlib
 import numpy as np
 import pytest
 
+import gzip_members
+
 pytestmark = pytest.mark.gpu
 
 
@@ -38,14 +40,7 @@ def test_segments_against_zlib(gpu):
 
 
 def bgzf(data, block=65280):
-    out = []
-    for i in range(0, len(data), block):
-        chunk = data[i:i + block]
-        co = zlib.compressobj(6, zlib.DEFLATED, -15)
-        d = co.compress(chunk) + co.flush()
-        out.append(b"\x1f\x8b\x08\x04" + b"\0" * 4 + b"\0\xff" + struct.pack("<H", 6) + b"BC" + struct.pack("<HH", 2, 12 + 6 + len(d) + 8 - 1)
-                   + d + struct.pack("<II", zlib.crc32(chunk), len(chunk)))
-    return b"".join(out) + bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
+    return gzip_members.bgzf(data, block)
 
 
 def count(path, **kw):

@@ -11,6 +11,9 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# rule tests whose cases the oracle (zlib) reads and this build refuses on purpose (the comment above oracle/pyoracle.py
+# decode_by_rule and DESIGN 2 say why)
+READER_DIFFERS = {"test_gzip_a_bc_subfield_binds_where_zlib_skips_it"}
 
 
 @pytest.fixture(scope="module")
@@ -49,7 +52,7 @@ def test_every_case_of_the_kit_through_the_device_reader(gpu, kit):
     from exon_duckdb_amd.reader import ShardReader
     from exon_duckdb_amd.table_function import type_sql
     out, cases = kit
-    n_rows_cases = n_err_cases = n_schema = 0
+    n_rows_cases = n_err_cases = n_schema = n_differs = 0
     for c in cases:
         exp = json.load(open(out / "expected" / (c["case"] + ".json")))
         path = str(out / c["file"])
@@ -69,7 +72,10 @@ def test_every_case_of_the_kit_through_the_device_reader(gpu, kit):
                 r.close()
         except ExgError as e:
             err = str(e)
-        if exp["error"]:
+        if c["test"] in READER_DIFFERS and not exp["error"]:
+            assert err is not None, (c["case"], "the reader holds a member to its BSIZE", rows)
+            n_differs += 1
+        elif exp["error"]:
             assert err is not None, (c["case"], "expected an error: " + exp["error"], rows)
             n_err_cases += 1
         else:
@@ -79,4 +85,4 @@ def test_every_case_of_the_kit_through_the_device_reader(gpu, kit):
             got = [_plain(dict(zip(names, row))) for row in rows]
             assert len(got) == len(exp["rows"]) and all(_same(g, e) for g, e in zip(got, exp["rows"])), (c["case"], got[:2], exp["rows"][:2])
             n_rows_cases += 1
-    assert n_schema == 3 and n_err_cases >= 20 and n_rows_cases >= 50
+    assert n_schema == 3 and n_err_cases >= 20 and n_rows_cases >= 50 and n_differs == 5

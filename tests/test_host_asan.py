@@ -3,12 +3,11 @@ frame / block walk, the VCF header parser, the shard planner, the `filters` gram
 sanitizers do not exist on the pool; everything these parsers read is user input."""
 import gzip
 import os
-import struct
 import subprocess
-import zlib
 
 import pytest
 
+import gzip_members
 from zstd_util import compress, fastq_text, skippable
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -16,14 +15,7 @@ CSRC = os.path.join(ROOT, "exon_duckdb_amd", "csrc")
 
 
 def bgzf(data, block):
-    out = []
-    for i in range(0, len(data), block):
-        chunk = data[i:i + block]
-        co = zlib.compressobj(6, zlib.DEFLATED, -15)
-        d = co.compress(chunk) + co.flush()
-        out.append(b"\x1f\x8b\x08\x04" + b"\0" * 4 + b"\0\xff" + struct.pack("<H", 6) + b"BC" + struct.pack("<HH", 2, 12 + 6 + len(d) + 8 - 1)
-                   + d + struct.pack("<II", zlib.crc32(chunk), len(chunk)))
-    return b"".join(out)
+    return gzip_members.bgzf(data, block, eof=False)
 
 
 def build_driver(exe):

@@ -9,6 +9,8 @@ import zlib
 import numpy as np
 import pytest
 
+import gzip_members
+
 from exon_duckdb_amd import abi
 
 pytestmark = pytest.mark.gpu
@@ -54,16 +56,8 @@ def roundtrip(gpu, payload: bytes, gz: bytes):
 
 
 def bgzf(payload: bytes, block=65280, level=6):
-    out = []
-    for i in range(0, max(len(payload), 1), block):
-        chunk = payload[i:i + block]
-        co = zlib.compressobj(level, zlib.DEFLATED, -15)
-        raw = co.compress(chunk) + co.flush()
-        bsize = 12 + 6 + len(raw) + 8 - 1
-        out.append(b"\x1f\x8b\x08\x04" + b"\0" * 4 + b"\0\xff" + struct.pack("<H", 6) + b"BC" + struct.pack("<HH", 2, bsize)
-                   + raw + struct.pack("<II", zlib.crc32(chunk), len(chunk)))
-    out.append(bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000"))   # BGZF EOF marker
-    return b"".join(out)
+    """(an empty payload is an empty member in front of the EOF block)"""
+    return (gzip_members.bgzf(payload, block, level) if payload else 2 * gzip_members.EOF_BLOCK)
 
 
 def fastq_like(n, seed=1):

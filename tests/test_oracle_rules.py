@@ -357,16 +357,8 @@ FA_A, FA_B = b">s1 d\nACGT\nAC\n", b">s2\nGG\n"
 
 
 def _bgzf(data, block, eof=True):
-    import struct
-    import zlib
-    out = []
-    for i in range(0, len(data), block):
-        chunk = data[i:i + block]
-        co = zlib.compressobj(6, zlib.DEFLATED, -15)
-        d = co.compress(chunk) + co.flush()
-        out.append(b"\x1f\x8b\x08\x04" + b"\0" * 4 + b"\0\xff" + struct.pack("<H", 6) + b"BC" + struct.pack("<HH", 2, 12 + 6 + len(d) + 8 - 1)
-                   + d + struct.pack("<II", zlib.crc32(chunk), len(chunk)))
-    return b"".join(out) + (bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000") if eof else b"")
+    import gzip_members
+    return gzip_members.bgzf(data, block, 6, eof)
 
 
 def _crows(r):
@@ -426,6 +418,36 @@ def test_empty_gzip_file_and_empty_member(oracle):
     assert oracle.compressed_parse("fastq", b"", "gzip", "fastq.gz").error == "empty gzip file"   # (zero bytes: no member at all)
     r = oracle.compressed_parse("fastq", gzip.compress(b"", 6, mtime=0) + gzip.compress(FQ_B, 6, mtime=0) + gzip.compress(b"", 6, mtime=0), "gzip", "fastq.gz")
     assert r.error is None and _crows(r) == [[b"c", b"y z", b"TTT", b"III"]]
+
+
+def test_gzip_a_bc_subfield_binds_where_zlib_skips_it(oracle):
+    """KEPT DIFFERENCE (the comment above decode_by_rule): zlib never reads FEXTRA, so these rules read a BGZF file whose
+    BSIZE is wrong; the device reader holds a member to its BSIZE and reports an error behind the rows of the members in front
+    (tests/test_gzip_members_gpu.py; tests/test_falsify_kit_gpu.py expects the reader's error for the cases of this test)"""
+    import gzip_members as gm
+    inv = gm.invalid()
+    for name in ("bsize_minus1", "bsize_plus1", "bsize_below_header", "bsize_past_eof", "bsize_takes_in_the_next_member"):
+        c = inv[name]
+        assert c.differs == "bsize_binds"
+        r = oracle.compressed_parse("fastq", c.data, "gzip", "fastq.gz")
+        assert c.text == gm.FQ and r.error is None and len(_crows(r)) >= 5, name         # (FQ: the three rows in front of the member)
+    # slack between the DEFLATE stream and the trailer is an error for both: zlib reads the slack as the trailer
+    assert "corrupt gzip stream" in oracle.compressed_parse("fastq", inv["slack_in_front_of_the_trailer"].data, "gzip", "fastq.gz").error
+
+
+def test_gzip_rows_of_the_member_an_error_lies_in(oracle):
+    """KEPT DIFFERENCE (the comment above decode_by_rule): the members in front of the failing one are handed out by these
+    rules and by the reader alike.  Of the failing member itself these rules hand out what zlib had decoded when the input ended,
+    and nothing when the trailer is wrong; the reader hands out nothing of a small or BGZF member, and every round of a big member
+    that was decoded before its trailer was read."""
+    import gzip_members as gm
+    whole = gm.member(gm.TINY_A) + gm.member(gm.TINY_B + gm.TINY_C)
+    cut = oracle.compressed_parse("fastq", whole[:-3], "gzip", "fastq.gz")              # the second member's trailer is cut
+    assert cut.error == "truncated gzip member" and len(_crows(cut)) == 4               # ... all its rows were decoded: handed out
+    assert len(_crows(oracle.compressed_parse("fastq", gm.member(gm.TINY_A), "gzip", "fastq.gz"))) == 1     # (the reader: this one row)
+    bad = gm.member(gm.TINY_A) + gm.member(gm.TINY_B + gm.TINY_C, crc=0)
+    r = oracle.compressed_parse("fastq", bad, "gzip", "fastq.gz")
+    assert "corrupt gzip stream" in r.error and len(_crows(r)) == 1                     # nothing of the member whose CRC-32 is wrong
 
 
 def test_zstd_concatenated_and_skippable_frames_are_read_through(oracle):

@@ -27,16 +27,8 @@ def _oracle_digest(table, names):
 
 def _bgzf(data, block=65280, level=1):
     """BGZF framing (what bgzip / htslib write) around zlib members; level 1: the tests deflate > 100 MB inputs"""
-    import struct
-    import zlib
-    out = []
-    for i in range(0, len(data), block):
-        chunk = data[i:i + block]
-        co = zlib.compressobj(level, zlib.DEFLATED, -15)
-        d = co.compress(chunk) + co.flush()
-        out.append(b"\x1f\x8b\x08\x04" + b"\0" * 4 + b"\0\xff" + struct.pack("<H", 6) + b"BC" +
-                   struct.pack("<HH", 2, 12 + 6 + len(d) + 8 - 1) + d + struct.pack("<II", zlib.crc32(chunk), len(chunk)))
-    return b"".join(out) + bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")   # + BGZF EOF marker
+    import gzip_members
+    return gzip_members.bgzf(data, block, level)
 
 
 def _open(path, fmt, **kw):
