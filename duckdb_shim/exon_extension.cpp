@@ -65,9 +65,34 @@ struct RealDuck {
 	static constexpr idx_t RowId = COLUMN_IDENTIFIER_ROW_ID;
 	static constexpr idx_t VectorSize = STANDARD_VECTOR_SIZE;
 
+	// MAP(key, value) where the DuckDB at hand has it (v0.8.1 does: LogicalType::MAP(LogicalType, LogicalType), LogicalTypeId::MAP —
+	// a LIST(STRUCT(key, value)) physically), found by overload resolution so that a header without it still compiles: there the
+	// column is the LIST(STRUCT(key, value)) it is laid out as
+	template <class T>
+	static auto MakeMap(const T &key, const T &value, int) -> decltype(T::MAP(key, value)) {
+		return T::MAP(key, value);
+	}
+	template <class T>
+	static T MakeMap(const T &key, const T &value, long) {
+		child_list_t<T> fields;
+		fields.emplace_back("key", key);
+		fields.emplace_back("value", value);
+		return T::LIST(T::STRUCT(std::move(fields)));
+	}
+	template <class E>
+	static auto MapTypeId(int) -> decltype(E::MAP) {
+		return E::MAP;
+	}
+	template <class E>
+	static E MapTypeId(long) {
+		return E::LIST;
+	}
+
 	// module.cpp:126-147 (there: ArrowTableFunction::GetArrowLogicalType over the Arrow schema)
 	static LogicalType ToLogical(const exg_type &t) {
 		switch (t.type) {
+		case EXG_TYPE_MAP: // children[0]: the STRUCT of key and value (read_gtf's attributes)
+			return MakeMap<LogicalType>(ToLogical(t.children[0].children[0]), ToLogical(t.children[0].children[1]), 0);
 		case EXG_TYPE_BIGINT:
 			return LogicalType::BIGINT;
 		case EXG_TYPE_FLOAT:
@@ -94,6 +119,13 @@ struct RealDuck {
 	static void Wrap(Vector &vec, const LogicalType &type, const exg_vector &src, const buffer_ptr<VectorBuffer> &keep) {
 		if (src.validity) {
 			FlatVector::Validity(vec).Initialize(reinterpret_cast<validity_t *>(src.validity));
+		}
+		if (type.id() == MapTypeId<LogicalTypeId>(0)) { // (a MAP is a LIST of STRUCT(key, value): LIST's layout and accessors)
+			FlatVector::SetData(vec, data_ptr_cast(src.data));
+			auto &child = ListVector::GetEntry(vec);
+			Wrap(child, ListType::GetChildType(type), src.children[0], keep);
+			ListVector::SetListSize(vec, src.children[0].length);
+			return;
 		}
 		switch (type.id()) {
 		case LogicalTypeId::LIST: {

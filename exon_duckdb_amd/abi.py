@@ -3,6 +3,7 @@ import ctypes as C
 
 EXG_ABI_VERSION = 9
 EXG_TYPE_VARCHAR, EXG_TYPE_BIGINT, EXG_TYPE_FLOAT, EXG_TYPE_INTEGER, EXG_TYPE_BOOLEAN, EXG_TYPE_LIST, EXG_TYPE_STRUCT = 1, 2, 3, 4, 5, 6, 7
+EXG_TYPE_MAP = 8   # LIST's layout over a STRUCT of key and value
 EXG_VECTOR_SIZE = 2048
 EXG_OPEN_CHUNKS = 1   # exg_open_args.flags
 
@@ -62,9 +63,18 @@ EXG_PE_BCF_CHROM = 52
 EXG_PE_BCF_DICT_INDEX = 53
 EXG_PE_BCF_NO_ALLELE = 54
 EXG_PE_BCF_SAMPLE_COUNT = 55
+EXG_PE_GTF_FIELD_COUNT = 57   # (56 is unassigned)
+EXG_PE_GTF_EMPTY_FIELD = 58
+EXG_PE_GTF_POSITION = 59
+EXG_PE_GTF_SCORE = 60
+EXG_PE_GTF_STRAND = 61
+EXG_PE_GTF_FRAME = 62
+EXG_PE_GTF_ATTRIBUTES = 63
 
 EXG_FMT_FASTA, EXG_FMT_FASTQ, EXG_FMT_VCF, EXG_FMT_BAM, EXG_FMT_BED, EXG_FMT_SAM = 1, 2, 3, 4, 5, 6
 EXG_FMT_BCF = 7
+EXG_FMT_GTF = 8
+EXG_GTF_COLUMNS = 9
 EXG_BAM_COLUMNS = 10
 EXG_BED_COLUMNS = 12
 EXG_SAM_COLUMNS = 10
@@ -72,6 +82,7 @@ EXG_F_BOF, EXG_F_EOF, EXG_F_NO_STORE = 1, 2, 4
 EXG_RF_NON_ASCII, EXG_RF_HEAD_UNRESOLVED, EXG_RF_FALLBACK, EXG_RF_CAPACITY, EXG_RF_INDEX_OVERFLOW = 1, 2, 4, 8, 16
 EXG_RF_QUAL_RANGE = 32
 EXG_RF_REDO = 64
+EXG_RF_ROWS_SKIPPED = 128
 EXG_ALGO_AUTO, EXG_ALGO_MULTIPASS, EXG_ALGO_FUSED, EXG_ALGO_FUSED_FULL, EXG_ALGO_FUSED_INDEX = 0, 1, 2, 3, 4
 
 EXG_SEQ_COMPLEMENT, EXG_SEQ_REVERSE_COMPLEMENT, EXG_SEQ_TRANSCRIBE, EXG_SEQ_REVERSE_TRANSCRIBE = 1, 2, 3, 4
@@ -364,6 +375,58 @@ class AlignStringArgs(C.Structure):
     ]
 
 
+class GtfScanArgs(C.Structure):
+    _fields_ = [
+        ("d_input", C.c_void_p),
+        ("n_bytes", C.c_uint64),
+        ("lead", C.c_uint64),
+        ("payload_base", C.c_uint64),
+        ("flags", C.c_uint32),
+        ("algo", C.c_uint32),
+        ("d_columns", C.c_void_p * EXG_GTF_COLUMNS),
+        ("d_validity", C.c_void_p * EXG_GTF_COLUMNS),
+        ("d_keep", C.c_void_p),
+        ("capacity_records", C.c_uint64),
+        ("d_workspace", C.c_void_p),
+        ("workspace_bytes", C.c_uint64),
+        ("d_result", C.c_void_p),
+        ("stream", C.c_void_p),
+    ]
+
+
+class GtfAttributesResult(C.Structure):
+    _fields_ = [
+        ("total_entries", C.c_uint64),
+        ("error_row", C.c_uint64),
+        ("error_offset", C.c_uint64),
+        ("n_rows", C.c_uint64),
+        ("error_code", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("error_byte", C.c_uint8),
+        ("pad", C.c_uint8 * 23),
+    ]
+
+
+class GtfAttributesArgs(C.Structure):
+    _fields_ = [
+        ("d_strings", C.c_void_p),
+        ("d_payload", C.c_void_p),
+        ("payload_base", C.c_uint64),
+        ("d_row_map", C.c_void_p),
+        ("n_rows", C.c_uint64),
+        ("chunk_rows", C.c_uint64),
+        ("d_out_entries", C.c_void_p),
+        ("d_out_chunk_base", C.c_void_p),
+        ("d_out_keys", C.c_void_p),
+        ("d_out_values", C.c_void_p),
+        ("entries_capacity", C.c_uint64),
+        ("d_workspace", C.c_void_p),
+        ("workspace_bytes", C.c_uint64),
+        ("d_result", C.c_void_p),
+        ("stream", C.c_void_p),
+    ]
+
+
 class CigarResult(C.Structure):
     _fields_ = [
         ("total_ops", C.c_uint64),
@@ -443,6 +506,10 @@ SIGNATURES = {
     "exg_bam_scan": (C.c_int, [C.POINTER(BamScanArgs)]),
     "exg_bed_scan": (C.c_int, [C.POINTER(BedScanArgs)]),
     "exg_sam_scan": (C.c_int, [C.POINTER(SamScanArgs)]),
+    "exg_gtf_scan": (C.c_int, [C.POINTER(GtfScanArgs)]),
+    "exg_gtf_attributes_workspace_bytes": (C.c_uint64, [C.c_uint64]),
+    "exg_gtf_attributes": (C.c_int, [C.POINTER(GtfAttributesArgs)]),
+    "exg_gtf_attributes_result": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(GtfAttributesResult)]),
     "exg_bcf_workspace_bytes": (C.c_uint64, [C.c_uint64, C.c_uint32]),
     "exg_bcf_to_vcf": (C.c_int, [C.POINTER(BcfToVcfArgs)]),
     "exg_bcf_result": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(BcfToVcfResult)]),

@@ -20,6 +20,8 @@ void set_error(const char *fmt, ...) {
     va_end(ap);
 }
 
+uint64_t gtf_slow_list_bytes();  // exg_gtf.hip: the tail of the GTF scan's workspace
+
 }  // namespace exg
 
 using namespace exg;
@@ -102,6 +104,13 @@ extern "C" const char *exg_parse_error_string(uint32_t code) {
         case EXG_PE_BCF_DICT_INDEX: return "key outside the header's dictionary";
         case EXG_PE_BCF_NO_ALLELE: return "BCF record without alleles";
         case EXG_PE_BCF_SAMPLE_COUNT: return "sample count differs from the header's";
+        case EXG_PE_GTF_FIELD_COUNT: return "fewer than 9 GTF fields";
+        case EXG_PE_GTF_EMPTY_FIELD: return "empty GTF seqname or type";
+        case EXG_PE_GTF_POSITION: return "invalid GTF start or end";
+        case EXG_PE_GTF_SCORE: return "invalid GTF score";
+        case EXG_PE_GTF_STRAND: return "invalid GTF strand";
+        case EXG_PE_GTF_FRAME: return "invalid GTF frame";
+        case EXG_PE_GTF_ATTRIBUTES: return "invalid GTF attributes";
         default: return "unknown parse error";
     }
 }
@@ -125,6 +134,15 @@ extern "C" uint64_t exg_scan_workspace_bytes(int format, uint64_t n_bytes) {
         const uint64_t small = n_bytes < (1ull << 20) ? n_bytes : (1ull << 20);
         const uint64_t lines = (n_bytes / 22 > small ? n_bytes / 22 : small) + 8;
         return l.off_nl_pos + (lines + 2) * 8;
+    }
+    if (format == EXG_FMT_GTF) {
+        // as for BED: the per-tile arrays and a line index for one line per 16 bytes (a feature line is 18 bytes and more; a run
+        // of `#` lines is denser: the general path then says EXG_RF_INDEX_OVERFLOW, the single-pass scan has no index), and
+        // behind them the list of score literals the exact float parser decides (exg_gtf.hpp)
+        const FastqWsLayout l = fastq_ws_layout(n_bytes, 0);
+        const uint64_t small = n_bytes < (1ull << 20) ? n_bytes : (1ull << 20);
+        const uint64_t lines = (n_bytes / 16 > small ? n_bytes / 16 : small) + 8;
+        return ((l.off_nl_pos + (lines + 2) * 8 + 255) & ~255ull) + gtf_slow_list_bytes();
     }
     return fastq_ws_layout(n_bytes, 0, exg_rd::format_desc(format).line_index_arrays).total_bytes;  // (FASTA keeps four arrays)
 }

@@ -300,6 +300,7 @@ struct FilterEval {
     const FilterProgram &prog;  // device memory
     const FilterCols &cols;
     const uint8_t *consts;
+    const uint64_t *keep;  // NULL, or bit r: row r exists (a scan that numbers rows by lines: exg_gtf_scan) — others are never TRUE
 
     // what exg_filter_eval.hpp's filter_eval_row fetches of row r: the columns, their validity words
     struct Row {
@@ -319,7 +320,15 @@ struct FilterEval {
         }
         __device__ float f32(uint32_t c) const { return ((const float *)cols.data[c])[r]; }
     };
-    __device__ uint64_t operator()(uint64_t r) const { return filter_eval_row(prog, consts, Row{cols, r}) ? 1 : 0; }
+    __device__ uint64_t operator()(uint64_t r) const {
+        if (keep && !((keep[r >> 6] >> (r & 63)) & 1)) return 0;  // (its slots were never written: not looked at)
+        return filter_eval_row(prog, consts, Row{cols, r}) ? 1 : 0;
+    }
+};
+// the rows a scan kept, without a predicate
+struct KeepEval {
+    const uint64_t *keep;
+    __device__ uint64_t operator()(uint64_t r) const { return (keep[r >> 6] >> (r & 63)) & 1; }
 };
 
 __global__ __launch_bounds__(256) void k_row_map(const uint64_t *__restrict__ goff, uint64_t n, uint32_t *row_map) {
@@ -328,9 +337,9 @@ __global__ __launch_bounds__(256) void k_row_map(const uint64_t *__restrict__ go
 }
 
 void filter_rows(const FilterProgram *d_prog, const FilterCols *d_cols, const uint8_t *d_consts, uint64_t n,
-                 uint64_t *d_goff_tmp, uint64_t *d_tmp, uint32_t *d_row_map, hipStream_t stream) {
-    FilterEval f{*d_prog, *d_cols, d_consts};
-    launch_xscan(f, n, d_goff_tmp, d_tmp, stream);
+                 uint64_t *d_goff_tmp, uint64_t *d_tmp, uint32_t *d_row_map, hipStream_t stream, const uint64_t *d_keep) {
+    if (d_prog) launch_xscan(FilterEval{*d_prog, *d_cols, d_consts, d_keep}, n, d_goff_tmp, d_tmp, stream);
+    else launch_xscan(KeepEval{d_keep}, n, d_goff_tmp, d_tmp, stream);
     if (!n) return;
     uint32_t grid = (uint32_t)((n + 255) / 256 < 8192 ? (n + 255) / 256 : 8192);
     hipLaunchKernelGGL(k_row_map, dim3(grid), dim3(256), 0, stream, d_goff_tmp, n, d_row_map);

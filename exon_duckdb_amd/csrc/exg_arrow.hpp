@@ -86,17 +86,19 @@ struct FilterCols {
     uint64_t payload_base[kMaxFilterCols];
 };
 // d_row_map[0..n_out) = indices of the rows where the predicate is TRUE, d_goff_tmp[n] = n_out (u64);
-// d_goff_tmp has n + 1 entries; program and column table live in device memory
+// d_goff_tmp has n + 1 entries; program and column table live in device memory.  d_keep (optional): validity-style words, bit r
+// clear = row r does not exist (exg_gtf_scan's d_keep) and is never selected; d_prog NULL (then d_keep is not): the kept rows
 void filter_rows(const FilterProgram *d_prog, const FilterCols *d_cols, const uint8_t *d_consts, uint64_t n,
-                 uint64_t *d_goff_tmp, uint64_t *d_tmp, uint32_t *d_row_map, hipStream_t stream);
+                 uint64_t *d_goff_tmp, uint64_t *d_tmp, uint32_t *d_row_map, hipStream_t stream, const uint64_t *d_keep = nullptr);
 // The predicate step of a batch, host side: the column table `fc` goes to d_fc, the rows where the predicate is TRUE become
 // d_row_map (scratch as for filter_rows) and their number comes back in *n_out.  Synchronises `stream` once, at that read-back
 // (fc, a stack object of the caller's, is alive until then).
 inline hipError_t select_rows(const FilterCols &fc, const FilterProgram *d_prog, const uint8_t *d_consts, uint64_t n, uint64_t *d_goff_tmp,
-                              uint64_t *d_tmp, uint32_t *d_row_map, FilterCols *d_fc, hipStream_t stream, uint64_t *n_out) {
-    hipError_t e = hipMemcpyAsync(d_fc, &fc, sizeof fc, hipMemcpyHostToDevice, stream);
+                              uint64_t *d_tmp, uint32_t *d_row_map, FilterCols *d_fc, hipStream_t stream, uint64_t *n_out,
+                              const uint64_t *d_keep = nullptr) {
+    hipError_t e = d_prog ? hipMemcpyAsync(d_fc, &fc, sizeof fc, hipMemcpyHostToDevice, stream) : hipSuccess;
     if (e != hipSuccess) return e;
-    filter_rows(d_prog, d_fc, d_consts, n, d_goff_tmp, d_tmp, d_row_map, stream);
+    filter_rows(d_prog, d_fc, d_consts, n, d_goff_tmp, d_tmp, d_row_map, stream, d_keep);
     if ((e = hipMemcpyAsync(n_out, d_goff_tmp + n, 8, hipMemcpyDeviceToHost, stream)) != hipSuccess) return e;
     return hipStreamSynchronize(stream);
 }

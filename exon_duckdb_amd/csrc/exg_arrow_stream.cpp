@@ -665,6 +665,8 @@ extern "C" ReaderResult new_reader(ArrowArrayStream *stream_ptr, const char *uri
         return result_error("new_reader: BAM is served at the chunk boundary only (exg_open / read_bam_file_records); the Arrow boundary for BAM is not built");
     if (strcasecmp(file_format, "bed") == 0)
         return result_error("new_reader: BED is served at the chunk boundary only (exg_open / read_bed_file); the Arrow boundary for BED is not built");
+    if (strcasecmp(file_format, "gtf") == 0)
+        return result_error("new_reader: GTF is served at the chunk boundary only (exg_open / read_gtf); the Arrow boundary for GTF is not built");
     if (strcasecmp(file_format, "sam") == 0)
         return result_error("new_reader: SAM is served at the chunk boundary only (exg_open / read_sam_file_records); the Arrow boundary for SAM is not built");
     exg_open_args oa;

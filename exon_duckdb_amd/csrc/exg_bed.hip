@@ -33,6 +33,7 @@ struct BedRows {
     static constexpr const char *kName = "exg_bed_scan", *kLabel = "BED";
     static constexpr int kColumns = EXG_BED_COLUMNS;
     static constexpr int kValidBits = 9;
+    static constexpr int kKeepBit = -1;  // every line is a row
     __host__ __device__ static __forceinline__ constexpr int valid_col(int bit) { return 3 + bit; }
     static constexpr uint32_t kGeneralBytesPerLine = 32;
     static constexpr int kNlCap = EXG_BED_NL_CAP;  // BED3 lines of ~25 bytes: 650 per half; denser halves go in passes

@@ -8,6 +8,8 @@
 //   kName, kLabel                         "exg_bed_scan", "BED": for the error messages
 //   kColumns                              columns of a row (d_columns / d_validity of its scan args)
 //   kValidBits, valid_col(bit)            RowInfo::valid bit b says column valid_col(b) is not NULL (ascending in b)
+//   kKeepBit                              -1, or the valid bit that says "this line is a row": a line without it (and without an
+//                                         error) keeps its row number, leaves its slot unwritten and raises EXG_RF_ROWS_SKIPPED
 //   kGeneralBytesPerLine                  what sizes the general path's grid
 //   kNlCap, kHalvesFull, kWavesFull       the fused scan's line list, halves per workgroup and waves per SIMD
 //   line<Src>(src, s, e, dev, out, store) the row function: one line [s, e) (CR already stripped) to row `out`
@@ -51,6 +53,12 @@ __device__ __forceinline__ void put_i64(void *col, unsigned long long out, long 
 __device__ __forceinline__ void row_report(ScanWsHeader *hdr, uint32_t code, unsigned long long out, uint64_t line_off) {
     atomicMin(&hdr->err_word, (out << 8) | (code & 0x7Fu));
     atomicMin(&hdr->err_off, (unsigned long long)line_off);
+}
+// a line that is no row (R::kKeepBit: GTF's `#` lines)
+template <class R>
+__device__ __forceinline__ void note_skipped(ScanWsHeader *hdr, const RowInfo &r) {
+    if constexpr (R::kKeepBit >= 0)
+        if (!r.code && !((r.valid >> R::kKeepBit) & 1u)) atomicOr(&hdr->flags, EXG_RF_ROWS_SKIPPED);
 }
 // the validity words of 64 consecutive rows from out_base on: a ballot per bit
 template <class R>
@@ -168,6 +176,7 @@ struct LineRowsFormat {
                     if (!r.code && c.non_ascii && !utf8_valid_lds(s, s0, e1)) r.code = EXG_PE_INVALID_UTF8;  // noodles reads lines into a String
                     if (r.code) row_report(hdr, r.code, (unsigned long long)out, c.tile_off + s0 - kWin);
                     else valid = r.valid;
+                    note_skipped<R>(hdr, r);
                 }
             }
             if (!no_store) store_row_validity<R>(a, valid, (long long)(c.P + jb + wave * 64) - (long long)halo_nl, lane);
@@ -203,6 +212,7 @@ __global__ __launch_bounds__(256) void k_line_rows(LineRowsDev<R::kColumns> a, c
                 if (!r.code && (hdr->flags & EXG_RF_NON_ASCII) && !utf8_valid_global(a.d_in, s0, e1)) r.code = EXG_PE_INVALID_UTF8;
                 if (r.code) row_report(hdr, r.code, out, s0);
                 else valid = r.valid;
+                note_skipped<R>(hdr, r);
             });
         }
         if (!no_store) store_row_validity<R>(a, valid, (long long)(it * 64) - (long long)halo, lane_id());
@@ -230,6 +240,7 @@ __global__ __launch_bounds__(256) void k_line_far(LineRowsDev<R::kColumns> a, co
         global_line(a, hdr, out, (uint64_t)(p[0] + 1), (uint64_t)p[1], [&](const GlobalSrc &src, uint64_t s0, uint64_t e1) {
             RowInfo r = R::line(src, 0, (int)(e1 - s0), a, out, !no_store);
             if (!r.code && tiles_non_ascii(tileA, kSuper, (int64_t)s0, (int64_t)e1) && !utf8_valid_global(a.d_in, s0, e1)) r.code = EXG_PE_INVALID_UTF8;
+            note_skipped<R>(hdr, r);
             if (r.code) {
                 row_report(hdr, r.code, out, s0);
             } else if (!no_store) {

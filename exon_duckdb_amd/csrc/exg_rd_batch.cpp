@@ -601,9 +601,11 @@ int ensure_device(exg_reader *r, uint64_t need_bytes) {
     for (uint32_t k = 0; k < f.spare_validity; k++)
         if ((arc = r->dev_alloc(&r->d_valid_spare[k], validity_bytes))) return arc;
     if (r->format == EXG_FMT_FASTA && (arc = r->dev_alloc(&r->d_payload, cap + 64))) return arc;
-    if (r->has_filter) {
+    // GTF: which rows are feature lines, and — a batch with `#` lines is gathered like a filtered one — the row map's buffers
+    if (r->format == EXG_FMT_GTF && (arc = r->dev_alloc(&r->d_keep, validity_bytes))) return arc;
+    if (r->has_filter || r->format == EXG_FMT_GTF) {
         if ((arc = r->dev_alloc(&r->d_row_map, r->cap_records * 4 + 64))) return arc;
-        if ((arc = r->dev_alloc(&r->d_gather, r->cap_records * 16))) return arc;
+        if ((arc = r->dev_alloc(&r->d_gather, std::max<uint64_t>(r->cap_records * 16, sizeof(exg::arrow::FilterCols))))) return arc;
         if ((arc = r->dev_alloc(&r->d_filter_tmp, (r->cap_records + 1 + exg::arrow::scan_tmp_entries(r->cap_records)) * 8))) return arc;
     }
     if (!r->d_res && !(r->d_res = exg_rd::dev_pool()->take(r->device, 4096))) return fail(r, EXG_E_HIP, "out of device memory");
@@ -662,7 +664,9 @@ struct BatchRun {
     const uint32_t *row_map = nullptr;
     double t_scan = 0;
 
-    BatchRun(exg_reader *reader, bool count) : r(reader), count_only(count), no_store(count && !reader->has_filter), want(reader->device_batch_bytes) {}
+    // (GTF: COUNT(*) counts feature lines, so the scan stores — d_keep alone: every column is a NULL pointer to it)
+    BatchRun(exg_reader *reader, bool count)
+        : r(reader), count_only(count), no_store(count && !reader->has_filter && reader->format != EXG_FMT_GTF), want(reader->device_batch_bytes) {}
 
     // ---- 1: the size of the attempt, from `want`, the ramp and the range (in.n == 0: nothing of this reader's is left)
     void size_attempt() {
@@ -1014,6 +1018,21 @@ struct BatchRun {
         }
         return scan_rc(exg_sam_scan(&a));
     }
+    int launch_gtf(uint32_t algo) {
+        exg_gtf_scan_args a;
+        fill_common(&a);
+        a.lead = in.lead;
+        a.algo = algo;
+        // (the projection reaches the kernel, as for BED; COUNT(*) without a predicate: no column at all.  Column 8 is the raw
+        // ninth field, what `attributes` is built from)
+        for (int c = 0; c < EXG_GTF_COLUMNS; c++) {
+            if (!(!count_only && r->want(c)) && !((r->filter_cols >> c) & 1ull)) continue;
+            a.d_columns[c] = r->d_cols[c];
+            a.d_validity[c] = (uint64_t *)r->d_col_valid[c];
+        }
+        a.d_keep = (uint64_t *)r->d_keep;
+        return scan_rc(exg_gtf_scan(&a));
+    }
     int launch_fasta() {
         in.b = std::make_shared<Batch>();
         if (!count_only) {
@@ -1037,6 +1056,7 @@ struct BatchRun {
             case EXG_FMT_VCF: return launch_vcf(algo);
             case EXG_FMT_BED: return launch_bed(algo);
             case EXG_FMT_SAM: return launch_sam(algo);
+            case EXG_FMT_GTF: return launch_gtf(algo);
             default: return launch_fasta();
         }
     }
@@ -1090,13 +1110,15 @@ struct BatchRun {
         return EXG_OK;
     }
 
-    // ---- 7: rows where the predicate is TRUE -> row map; the columns are gathered through it on their way out
+    // ---- 7: rows where the predicate is TRUE -> row map; the columns are gathered through it on their way out.  GTF: the rows
+    // that are feature lines (d_keep), ANDed with the predicate when there is one
+    bool rows_skipped() const { return r->format == EXG_FMT_GTF && (res.flags & EXG_RF_ROWS_SKIPPED); }
     int select_rows() {
         namespace ea = exg::arrow;
         ea::FilterCols fc;
         memset(&fc, 0, sizeof fc);
         const FormatDesc &f = format_desc(r->format);
-        for (int c = 0; c < f.n_columns; c++) {
+        for (int c = 0; c < f.n_columns && r->has_filter; c++) {
             fc.kind[c] = filter_col_kind(f.col[c]);
             fc.data[c] = r->column_data(c).data;
             fc.validity[c] = (const uint64_t *)r->d_col_valid[c];
@@ -1109,8 +1131,8 @@ struct BatchRun {
         }
         uint64_t *d_goff = (uint64_t *)r->d_filter_tmp, *d_tmp = d_goff + r->cap_records + 1;
         ea::FilterCols *d_fc = (ea::FilterCols *)r->d_gather;  // the scratch column is free until the gathers
-        RD_HIP(r, ea::select_rows(fc, (const ea::FilterProgram *)r->d_filter_prog, (const uint8_t *)r->d_filter_consts, k, d_goff, d_tmp,
-                                  (uint32_t *)r->d_row_map, d_fc, r->stream, &k));
+        RD_HIP(r, ea::select_rows(fc, r->has_filter ? (const ea::FilterProgram *)r->d_filter_prog : nullptr, (const uint8_t *)r->d_filter_consts, k, d_goff,
+                                  d_tmp, (uint32_t *)r->d_row_map, d_fc, r->stream, &k, rows_skipped() ? (const uint64_t *)r->d_keep : nullptr));
         row_map = (const uint32_t *)r->d_row_map;
         return EXG_OK;
     }
@@ -1153,6 +1175,7 @@ struct BatchRun {
                 (rc = column_to_host(r, b, c, nullptr, 0, r->d_col_valid[c], k, row_map, r->d_gather, cs)))
                 return rc;
         if (r->format == EXG_FMT_VCF && (rc = vcf_nested_columns(cs, &col_drain))) return rc;
+        if (r->format == EXG_FMT_GTF && r->want(8) && (rc = gtf_attributes(&side_scratch))) return rc;
         if (r->format == EXG_FMT_FASTA && res.payload_bytes && r->want(2) && (rc = fasta_sequences(cs))) return rc;
         const double t_cols = now_s();
         RD_HIP(r, hipStreamSynchronize(r->stream));
@@ -1277,6 +1300,71 @@ struct BatchRun {
         }
         return EXG_OK;
     }
+    // read_gtf: `attributes` — the ninth field of the rows that leave (through the row map) -> list entries relative to their
+    // DataChunk + key / value strings that point into the input's bytes (exg_gtf_attributes), on the scan's stream.  The children
+    // are provisioned for an entry per 16 bytes of the batch; a batch of denser entries is counted first and emitted again.
+    int gtf_attributes(SideScratch *scratch) {
+        Batch *b = in.b.get();
+        const uint64_t n_chunks = (k + r->batch_rows - 1) / r->batch_rows;
+        const uint64_t ws_bytes = exg_gtf_attributes_workspace_bytes(k);
+        void *d_ws = scratch->take(ws_bytes), *d_entries = scratch->take(k * 16), *d_bases = scratch->take((n_chunks + 1) * 8);
+        void *d_res = scratch->take(64);
+        if (!d_ws || !d_entries || !d_bases || !d_res) return fail(r, EXG_E_HIP, "out of device memory");
+        exg_gtf_attributes_args a;
+        memset(&a, 0, sizeof a);
+        a.d_strings = (const exg_string_t *)r->d_cols[8];
+        a.d_payload = in.d_input;
+        a.payload_base = (uint64_t)(uintptr_t)in.h;
+        a.d_row_map = row_map;
+        a.n_rows = k;
+        a.chunk_rows = r->batch_rows;
+        a.d_out_entries = (exg_list_entry_t *)d_entries;
+        a.d_out_chunk_base = (uint64_t *)d_bases;
+        a.d_workspace = d_ws, a.workspace_bytes = ws_bytes;
+        a.d_result = (struct exg_gtf_attributes_result *)d_res;
+        a.stream = r->stream;
+        struct exg_gtf_attributes_result ar;
+        uint64_t cap = in.n / 16 + k + 1024;
+        for (int attempt = 0;; attempt++) {
+            a.entries_capacity = cap;
+            if (!(a.d_out_keys = (exg_string_t *)scratch->take(cap * 16)) || !(a.d_out_values = (exg_string_t *)scratch->take(cap * 16)))
+                return fail(r, EXG_E_HIP, "out of device memory");
+            int rc = exg_gtf_attributes(&a);
+            if (rc) return fail(r, rc, exg_last_error_message());
+            rc = exg_gtf_attributes_result(a.d_result, r->stream, &ar);
+            if (rc == EXG_E_PARSE)
+                return fail(r, EXG_E_PARSE, std::string(exg_parse_error_string(EXG_PE_GTF_ATTRIBUTES)) + " at byte " + std::to_string(ar.error_offset) +
+                                                " of the attributes of feature line " + std::to_string(ar.error_row) + " of the batch that ends at byte " +
+                                                std::to_string(in.batch_end) + " of " + r->files[r->file_idx - 1]);
+            if (rc) return fail(r, rc, exg_last_error_message());
+            if (!(ar.flags & EXG_RF_CAPACITY)) break;
+            if (attempt) return fail(r, EXG_E_CAPACITY, "internal: the attributes' entries do not fit the count of the pass before");
+            cap = ar.total_entries;
+        }
+        const uint64_t total = ar.total_entries;
+        void *h_entries = b->host.alloc(k * 16), *h_bases = b->host.alloc((n_chunks + 1) * 8);
+        void *h_keys = b->host.alloc(total * 16 + 16), *h_vals = b->host.alloc(total * 16 + 16);
+        if (!h_entries || !h_bases || !h_keys || !h_vals) return fail(r, EXG_E_HIP, "out of pinned host memory");
+        RD_HIP(r, hipMemcpyAsync(h_entries, d_entries, k * 16, hipMemcpyDeviceToHost, r->stream));
+        RD_HIP(r, hipMemcpyAsync(h_bases, d_bases, (n_chunks + 1) * 8, hipMemcpyDeviceToHost, r->stream));
+        if (total) {
+            RD_HIP(r, hipMemcpyAsync(h_keys, a.d_out_keys, total * 16, hipMemcpyDeviceToHost, r->stream));
+            RD_HIP(r, hipMemcpyAsync(h_vals, a.d_out_values, total * 16, hipMemcpyDeviceToHost, r->stream));
+        }
+        r->host_vector_bytes += k * 16 + (n_chunks + 1) * 8 + total * 32;
+        b->nested.resize((size_t)b->n_cols);
+        NVec &m = b->nested[8];
+        m.type = EXG_TYPE_MAP, m.data = h_entries, m.elem = 16, m.length = k, m.child_base = (const uint64_t *)h_bases;
+        m.children.resize(1);
+        NVec &st = m.children[0];
+        st.type = EXG_TYPE_STRUCT, st.length = total;
+        st.children.resize(2);
+        st.children[0].type = st.children[1].type = EXG_TYPE_VARCHAR;
+        st.children[0].elem = st.children[1].elem = 16;
+        st.children[0].length = st.children[1].length = total;
+        st.children[0].data = h_keys, st.children[1].data = h_vals;
+        return EXG_OK;
+    }
     // FASTA: the joined sequences
     int fasta_sequences(hipStream_t cs) {
         Batch *b = in.b.get();
@@ -1354,7 +1442,7 @@ int next_batch(exg_reader *r, bool count_only, uint64_t *n_records_out) {
         run.prefetch_next();
         TRACE("prefetch issue", t_pf);
         run.k = run.res.n_records;
-        if (r->has_filter && run.k && !r->arrow_emit && (rc = run.select_rows())) return rc;
+        if ((r->has_filter || run.rows_skipped()) && run.k && !r->arrow_emit && (rc = run.select_rows())) return rc;
         *n_records_out = run.k;
         if (r->arrow_emit && !count_only) rc = run.arrow_emit();
         else rc = run.k && !count_only ? run.columns_to_host() : EXG_OK;

@@ -85,6 +85,8 @@ namespace format_detail {
 constexpr ColumnDesc str(const char *name, bool nullable, bool payload = true) { return {name, EXG_TYPE_VARCHAR, nullable, 16, payload, false, nullable, kNotParsed}; }
 constexpr ColumnDesc i64(const char *name, bool nullable) { return {name, EXG_TYPE_BIGINT, nullable, 8, false, false, nullable, kNotParsed}; }
 constexpr ColumnDesc i32(const char *name, bool nullable) { return {name, EXG_TYPE_INTEGER, nullable, 4, false, false, nullable, kNotParsed}; }
+// a flat FLOAT the scan writes as a number, with validity words (VCF's qual is not one: its number lands in a parsed vector)
+constexpr ColumnDesc f32(const char *name, bool nullable) { return {name, EXG_TYPE_FLOAT, nullable, 4, false, false, nullable, kNotParsed}; }
 constexpr ColumnDesc vcf_nested(const char *name, int type, bool validity = false) { return {name, type, true, 0, true, true, validity, kNotParsed}; }
 
 // (inline: one table for the whole library, so that the addresses format_desc hands out are the same in every unit)
@@ -139,6 +141,17 @@ inline constexpr FormatDesc kFormats[] = {
      {str("name", false), i32("flag", false), str("reference", true), i32("start", true), i32("end", true), str("mapping_quality", true),
       str("cigar", false), str("mate_reference", true), str("sequence", false), str("quality_score", false)},
      128, 64, 22, 2u * 16384u, 1, 0},
+    // test_gtf_scan.test:6-16 pins a row; names, types and nullability as INTEGRATION.md states them.  The scan leaves the ninth
+    // field as one string per row; `attributes` is built from it behind the row selection (exg_gtf_attributes) and leaves as a MAP
+    // whose keys and values point into the input
+    // (128: SAM's budget — ~1.5 B of vectors (92 B a row, a row per 64 bytes), ~0.5 B of workspace and the row map's scratch per byte
+    // of an input slot, two slots, a slot a batch + 1 MiB of prefetch slack; the attributes' children are a batch's own pooled
+    // scratch, ~1.3 B per byte of attribute text (tests/test_gtf_gpu.py::test_reader_memory_cap prints the peak).  Rows: the scan
+    // numbers rows by lines — a feature line under 64 bytes would be unusual, the densest line is `#` + LF)
+    {EXG_FMT_GTF, "gtf", "exg: scan gtf batch", EXG_GTF_COLUMNS,
+     {str("seqname", false), str("source", false), str("type", false), i64("start", false), i64("end", false), f32("score", true), str("strand", true),
+      str("frame", true), {"attributes", EXG_TYPE_MAP, false, 0, true, true, false, kNotParsed}},
+     128, 64, 2, 2u * 16384u, 1, 0},
 };
 constexpr int kNFormats = (int)(sizeof kFormats / sizeof kFormats[0]);
 inline constexpr FormatDesc kNoFormat = {0, "", "", 0, {}, 1, 1, 1, 1, 1, 0};
@@ -163,6 +176,10 @@ constexpr FlatTrees flat_trees() {
     return r;
 }
 inline constexpr FlatTrees kFlatTrees = flat_trees();
+// MAP(VARCHAR, VARCHAR): LIST's layout over a STRUCT of key and value (GTF attributes)
+inline constexpr exg_type kMapKeyValue[2] = {{EXG_TYPE_VARCHAR, 0, "key", 0, nullptr}, {EXG_TYPE_VARCHAR, 0, "value", 0, nullptr}};
+inline constexpr exg_type kMapEntries[1] = {{EXG_TYPE_STRUCT, 0, "entries", 2, kMapKeyValue}};
+inline constexpr exg_type kGtfAttributes = {EXG_TYPE_MAP, 0, "attributes", 1, kMapEntries};
 
 // the masks the stages used to spell as literals
 static_assert(find(EXG_FMT_FASTQ).payload_mask() == 0xF && find(EXG_FMT_FASTQ).string_mask() == 0xF, "FASTQ: four strings into the input");
@@ -177,12 +194,17 @@ static_assert(find(EXG_FMT_BAM).payload_mask() == 0 && find(EXG_FMT_BAM).validit
 static_assert(find(EXG_FMT_SAM).payload_mask() == 0x3E5 && find(EXG_FMT_SAM).string_mask() == 0x3E5, "SAM: all seven VARCHAR columns point into the input");
 static_assert(find(EXG_FMT_SAM).mask_of_type(EXG_TYPE_INTEGER) == 0x1A && find(EXG_FMT_SAM).nullable_mask() == 0xBC && find(EXG_FMT_SAM).validity_mask() == 0xBC, "SAM: BAM's schema");
 static_assert(find(EXG_FMT_FASTQ).validity_mask() == 0x2 && find(EXG_FMT_FASTA).validity_mask() == 0x2, "description");
+static_assert(find(EXG_FMT_GTF).payload_mask() == 0x1C7 && find(EXG_FMT_GTF).string_mask() == 0xC7 && find(EXG_FMT_GTF).nested_mask() == 0x100, "GTF: five flat strings and the attributes point into the input");
+static_assert(find(EXG_FMT_GTF).validity_mask() == 0xE0 && find(EXG_FMT_GTF).nullable_mask() == 0xE0, "GTF: score, strand and frame are nullable");
+static_assert(find(EXG_FMT_GTF).mask_of_type(EXG_TYPE_BIGINT) == 0x18 && find(EXG_FMT_GTF).mask_of_type(EXG_TYPE_FLOAT) == 0x20 && find(EXG_FMT_GTF).scan_elem(5) == 4, "GTF: start and end are BIGINT, score a flat FLOAT");
 }  // namespace format_detail
 
 // the description of EXG_FMT_* `format` (an unknown one: no columns)
 inline const FormatDesc &format_desc(int format) { return format_detail::find(format); }
 // ... and the exg_type leaf of its flat column c
 inline const exg_type *flat_tree(int format, int c) { return &format_detail::kFlatTrees.t[format_detail::index_of(format)][c]; }
+// ... the tree of GTF's attributes column
+inline const exg_type *gtf_attributes_tree() { return &format_detail::kGtfAttributes; }
 // ... of a file_format spelled in lower case (NULL: not one of them)
 inline const FormatDesc *format_named(const char *lower) {
     // ("sam" is not answered here: exg_open takes it in a branch of its own, where it was refused by name until the tokeniser was

@@ -209,6 +209,7 @@ extern "C" ReplacementScanResult replacement_scan(const char *uri) {
     if (ext == "bam") res.file_type = "BAM";
     if (ext == "bcf") res.file_type = "BCF";
     if (ext == "bed") res.file_type = "BED";  // (the reference's glue throws for it, module.cpp:376-379: not reproduced)
+    if (ext == "gtf") res.file_type = "GTF";  // (`.gff` / `.gff3` stay unanswered: read_gff is not built)
     // (`.sam` is not replaced yet, as before read_sam_file_records was built — tests/test_bam_host.py holds `x.sam` to NULL —: the
     // table function is called by name; whether exon's ExonFileType::from_str answers "sam" is not in the reference tree)
     return res;
@@ -220,7 +221,7 @@ extern "C" ReplacementScanResult replacement_scan(const char *uri) {
 // hundred bytes), a 16 KiB half with more lines than its list holds (FASTQ 512: lines of < 32 bytes on average; VCF 1024), bytes
 // >= 0x80 (UTF-8 validation).  A sample of the first MiB tells all of that apart.
 extern "C" int exg_scan_algo_hint(int format, const void *sample, uint64_t n_bytes) {
-    if (format == EXG_FMT_BED || format == EXG_FMT_SAM) return EXG_ALGO_FUSED_FULL;  // (BED and SAM have the any-shape scan only)
+    if (format == EXG_FMT_BED || format == EXG_FMT_SAM || format == EXG_FMT_GTF) return EXG_ALGO_FUSED_FULL;  // (BED, SAM and GTF have the any-shape scan only)
     if (format != EXG_FMT_FASTQ && format != EXG_FMT_VCF) return EXG_ALGO_FUSED;  // (FASTA has one scan)
     const uint8_t *p = (const uint8_t *)sample;
     const uint64_t n = n_bytes < (1u << 20) ? n_bytes : (1u << 20);

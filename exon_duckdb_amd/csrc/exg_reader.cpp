@@ -31,7 +31,7 @@ extern "C" int exg_open(const exg_open_args *args, exg_reader **out) {
     for (char &ch : fmt) ch = (char)tolower((unsigned char)ch);
     if (const FormatDesc *f = format_named(fmt.c_str())) {
         r->format = f->format;
-        if (r->format == EXG_FMT_BED) r->fused_algo = EXG_ALGO_FUSED_FULL;  // (one single-pass scan: exg_bed.hip; SAM below: exg_sam.hip)
+        if (r->format == EXG_FMT_BED || r->format == EXG_FMT_GTF) r->fused_algo = EXG_ALGO_FUSED_FULL;  // (one single-pass scan: exg_bed.hip, exg_gtf.hip; SAM below: exg_sam.hip)
     } else if (fmt == "sam") {  // (not in format_named's answers: see there)
         r->format = EXG_FMT_SAM, r->fused_algo = EXG_ALGO_FUSED_FULL;
     } else if (fmt == "bcf") {
@@ -249,6 +249,7 @@ static void flat_schema(const exg_reader *r, exg_schema *out) {
     for (int c = 0; c < f.n_columns; c++) {
         out->names[c] = f.col[c].name, out->types[c] = f.col[c].type, out->nullable[c] = f.col[c].nullable;
         if (!f.col[c].nested) out->tree[c] = flat_tree(r->format, c);
+        else if (f.col[c].type == EXG_TYPE_MAP) out->tree[c] = gtf_attributes_tree();
     }
 }
 
@@ -296,7 +297,7 @@ static void slice_vector(const NVec &v, uint64_t e0, uint64_t e1, uint64_t chunk
     keep->nodes.emplace_back(new exg_vector[v.children.size()]);
     exg_vector *kids = keep->nodes.back().get();
     for (size_t i = 0; i < v.children.size(); i++) {
-        if (v.type == EXG_TYPE_LIST)
+        if (v.type == EXG_TYPE_LIST || v.type == EXG_TYPE_MAP)
             slice_vector(v.children[i], v.child_base[chunk], v.child_base[chunk + 1], chunk, keep, &kids[i]);
         else
             slice_vector(v.children[i], e0, e1, chunk, keep, &kids[i]);

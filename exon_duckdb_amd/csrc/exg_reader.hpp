@@ -468,6 +468,7 @@ struct exg_reader {
     void *d_cols[exg_rd::kMaxColumns] = {};
     void *d_col_valid[exg_rd::kMaxColumns] = {};
     void *d_valid_spare[2] = {nullptr, nullptr};  // (FormatDesc::spare_validity)
+    void *d_keep = nullptr;  // GTF: the scan numbers rows by lines; bit r = row r is a feature line (exg_gtf_scan_args.d_keep)
     void *d_pos = nullptr, *d_qual = nullptr, *d_payload = nullptr;  // VCF: the parsed POS / QUAL; FASTA: the joined sequences
     // the vector a column's parsed numbers go to, beside the field's text in d_cols (NULL: the column has none)
     void **parsed_vector(exg_rd::ParsedVector which) { return which == exg_rd::kParsedPos ? &d_pos : which == exg_rd::kParsedQual ? &d_qual : nullptr; }

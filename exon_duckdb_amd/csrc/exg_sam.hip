@@ -29,6 +29,7 @@ struct SamRows {
     static constexpr const char *kName = "exg_sam_scan", *kLabel = "SAM";
     static constexpr int kColumns = EXG_SAM_COLUMNS;
     static constexpr int kValidBits = 5;
+    static constexpr int kKeepBit = -1;  // every line is a row
     __host__ __device__ static __forceinline__ constexpr int valid_col(int bit) { return bit == 0 ? 2 : bit == 1 ? 3 : bit == 2 ? 4 : bit == 3 ? 5 : 7; }
     static constexpr uint32_t kGeneralBytesPerLine = 64;
     static constexpr int kNlCap = EXG_SAM_NL_CAP;  // the densest valid line is 22 bytes with its LF: 744 per half

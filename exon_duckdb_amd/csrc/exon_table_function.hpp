@@ -277,7 +277,7 @@ struct ExonTableFunction {
     static idx_t EstimatedCardinality(const BindData &d) {
         if (!d.input_bytes) return 0;
         const double text = (double)d.input_bytes * (d.input_compression ? 3.5 : 1.0);
-        const double per_row = d.file_type == "fastq" ? 300.0 : d.file_type == "vcf" ? 120.0 : d.file_type == "bam" ? 350.0 : d.file_type == "bed" ? 40.0 : d.file_type == "sam" ? 400.0 :
+        const double per_row = d.file_type == "fastq" ? 300.0 : d.file_type == "vcf" ? 120.0 : d.file_type == "bam" ? 350.0 : d.file_type == "bed" ? 40.0 : d.file_type == "sam" ? 400.0 : d.file_type == "gtf" ? 250.0 :
                                d.file_type == "bcf" ? 50.0 : 4096.0;  // (bcf: decoded BCF bytes of a single-sample record, a third of its line)
         const double rows = text / per_row;
         return rows < 1 ? (idx_t)1 : (idx_t)rows;
@@ -305,6 +305,7 @@ struct ExonTableFunction {
         if (ft == "BAM") return "read_bam_file_records";
         if (ft == "BED") return "read_bed_file";
         if (ft == "BCF") return "read_bcf_file_records";
+        if (ft == "GTF") return "read_gtf";
         return "";
     }
 };
@@ -598,6 +599,6 @@ struct Registration {
 static const Registration kRegistrations[] = {
     {"read_fasta", "fasta"}, {"read_fastq", "fastq"}, {"read_vcf_file_records", "vcf"}, {"read_vcf", "vcf"},
     {"read_bam_file_records", "bam"}, {"read_bed_file", "bed"}, {"read_sam_file_records", "sam"},
-    {"read_bcf_file_records", "bcf"}};
+    {"read_bcf_file_records", "bcf"}, {"read_gtf", "gtf"}};
 
 }  // namespace exon_scan

@@ -35,7 +35,8 @@ enum class LogicalTypeId {
     INTEGER = EXG_TYPE_INTEGER,
     BOOLEAN = EXG_TYPE_BOOLEAN,
     LIST = EXG_TYPE_LIST,
-    STRUCT = EXG_TYPE_STRUCT
+    STRUCT = EXG_TYPE_STRUCT,
+    MAP = EXG_TYPE_MAP
 };
 
 // duckdb::LogicalType: LIST carries its child type (ListType::GetChildType), STRUCT its named fields
@@ -55,12 +56,18 @@ struct LogicalType {
         t.children = std::move(fields);
         return t;
     }
+    // duckdb::LogicalType::MAP(key, value): a LIST of STRUCT(key, value) (MapType::KeyType / ValueType)
+    static LogicalType MAP(LogicalType key, LogicalType value) {
+        LogicalType t(LogicalTypeId::MAP);
+        t.children.emplace_back("", STRUCT({{"key", std::move(key)}, {"value", std::move(value)}}));
+        return t;
+    }
     bool operator==(const LogicalType &o) const { return id == o.id && children == o.children; }
 };
 
 using string_t = exg_string_t;
 
-// A flat vector that references memory owned by `buffer` (DuckDB: Vector + VectorBuffer).  LIST: data = list_entry_t[]
+// A flat vector that references memory owned by `buffer` (DuckDB: Vector + VectorBuffer).  LIST and MAP: data = list_entry_t[]
 // and children[0] = the child vector (ListVector::GetEntry / SetListSize = its length); STRUCT: children = the entries
 // (StructVector::GetEntries).
 struct Vector {

@@ -29,6 +29,7 @@ struct MiniDuck {
     static LogicalType ToLogical(const exg_type &t) {
         switch (t.type) {
             case EXG_TYPE_LIST: return LogicalType::LIST(ToLogical(t.children[0]));
+            case EXG_TYPE_MAP: return LogicalType::MAP(ToLogical(t.children[0].children[0]), ToLogical(t.children[0].children[1]));
             case EXG_TYPE_STRUCT: {
                 std::vector<std::pair<std::string, LogicalType>> fields;
                 for (int i = 0; i < t.n_children; i++) fields.emplace_back(t.children[i].name, ToLogical(t.children[i]));
@@ -154,7 +155,7 @@ static void export_type(exon_tf_handle *h, const LogicalType &t, const char *nam
     h->type_nodes.emplace_back(new exg_type[t.children.size()]);
     exg_type *kids = h->type_nodes.back().get();
     for (size_t i = 0; i < t.children.size(); i++)
-        export_type(h, t.children[i].second, t.id == LogicalTypeId::LIST ? "item" : t.children[i].first.c_str(), &kids[i]);
+        export_type(h, t.children[i].second, t.id == LogicalTypeId::LIST ? "item" : t.id == LogicalTypeId::MAP ? "entries" : t.children[i].first.c_str(), &kids[i]);
     out->n_children = (int)t.children.size();
     out->children = kids;
 }

@@ -618,6 +618,122 @@ class SamScan(BedScan):
     N_COLS, INT_DTYPE, FMT, ARGS, ENTRY = abi.EXG_SAM_COLUMNS, "int32", abi.EXG_FMT_SAM, abi.SamScanArgs, "exg_sam_scan"
 
 
+class GtfScan(BedScan):
+    """exg_gtf_scan on GTF lines resident in HBM: BedScan's buffers and decoding with GTF's nine columns (start / end int64,
+    score float32, column 8 the raw ninth field) and the keep words.  The scan numbers rows by LINES: rows(n, ...) gives the
+    rows of the feature lines among the first n (those whose bit is set in d_keep); kept(n) says which they are.
+    `workspace_bytes`: a workspace larger than exg_scan_workspace_bytes (the general path on runs of `#` lines)."""
+    NAMES = ["seqname", "source", "type", "start", "end", "score", "strand", "frame", "attributes"]
+    INT_COLS, NULLABLE = (3, 4), (5, 6, 7)
+    N_COLS, INT_DTYPE, FMT, ARGS, ENTRY = abi.EXG_GTF_COLUMNS, "int64", abi.EXG_FMT_GTF, abi.GtfScanArgs, "exg_gtf_scan"
+
+    def __init__(self, n_bytes, capacity_records=None, device="cuda", workspace_bytes=None):
+        super().__init__(n_bytes, capacity_records, device)
+        torch = _torch()
+        cap = max(self.capacity, 1)
+        self.cols[5] = torch.empty((cap,), dtype=torch.float32, device=device)
+        self.keep = torch.zeros(((cap + 63) // 64,), dtype=torch.int64, device=device)
+        if workspace_bytes is not None and workspace_bytes > self.ws_bytes:
+            self.ws_bytes = int(workspace_bytes)
+            self.ws = torch.empty((self.ws_bytes + 255) // 8, dtype=torch.int64, device=device)
+        self.args.d_keep = self.keep.data_ptr()
+
+    def kept(self, n):
+        """bool per row of the first n: the line is a feature line"""
+        words = self.keep[:(n + 63) // 64].cpu().numpy().view(np.uint64)
+        return np.unpackbits(words.view(np.uint8), bitorder="little")[:n].astype(bool)
+
+    def host(self, n):
+        nw = (n + 63) // 64
+        cols = [self.cols[c][:n].cpu().numpy() if c in self.INT_COLS or c == 5 else self.cols[c][:n].cpu().numpy().view(np.uint8).reshape(n, 16)
+                for c in range(self.N_COLS)]
+        return cols, {c: v[:nw].cpu().numpy().view(np.uint64) for c, v in self.validity.items()}
+
+    def rows(self, n, data: bytes, columns=None, payload_base=None):
+        """the rows of the feature lines among the first n lines; score as the float32's bit pattern (an int), NULL as None"""
+        base = self.PAYLOAD_BASE if payload_base is None else payload_base
+        keep = self.kept(n)
+        cols, words = self.host(n)
+        out = []
+        for c in (range(self.N_COLS) if columns is None else columns):
+            valid = np.unpackbits(words[c].view(np.uint8), bitorder="little")[:n] if c in words else None
+            if c in self.INT_COLS:
+                vals = cols[c].tolist()
+            elif c == 5:
+                vals = cols[c].view(np.uint32).tolist()
+            else:
+                raw = cols[c]
+                lens = raw[:, :4].copy().view(np.uint32).reshape(n)
+                ptrs = raw[:, 8:16].copy().view(np.uint64).reshape(n)
+                vals = []
+                for i in range(n):
+                    ln = int(lens[i])
+                    if not keep[i]:
+                        vals.append(None)
+                    elif ln <= 12:
+                        assert not raw[i, 4 + ln:].any(), "inlined string_t is not zero padded"
+                        vals.append(raw[i, 4:4 + ln].tobytes())
+                    else:
+                        o = int(ptrs[i]) - base
+                        s = data[o:o + ln]
+                        assert 0 <= o and len(s) == ln and s[:4] == raw[i, 4:8].tobytes(), "string_t outside the input, or a wrong prefix"
+                        vals.append(s)
+            if valid is not None:
+                for i in range(n):
+                    if keep[i] and not valid[i]:
+                        assert not np.asarray(cols[c][i]).any(), "a NULL value does not hold zeros"
+                        vals[i] = None
+            out.append(vals)
+        return [row for row, k in zip(zip(*out), keep) if k]
+
+
+def gtf_attributes(strings, n_rows, payload, payload_base, entries_capacity=None, row_map=None, chunk_rows=0):
+    """exg_gtf_attributes on a column of GTF ninth fields that is still in HBM: `strings` is a [cap, 2] int64 tensor of string_t
+    (GtfScan.cols[8]), `payload` the buffer its pointers address, `row_map` an optional int32 tensor of n_rows row numbers.
+    Returns (entries [n_rows, 2] int64 = DuckDB list_entry_t {offset, length}, keys [total, 2] int64, values [total, 2] int64 —
+    string_t that point into the same payload —, chunk_base or None, result).  entries_capacity=None is the two-call form: a
+    counting call, then the exact capacity; with a capacity given, result.flags & EXG_RF_CAPACITY means it was too small and the
+    children were not written.  An invalid row raises ExgError (the result block rides on it as .result)."""
+    torch = _torch()
+    lib = load_library()
+    dev = strings.device
+    a = abi.GtfAttributesArgs()
+    a.d_strings = strings.data_ptr()
+    a.d_payload = payload.data_ptr() if payload is not None else None
+    a.payload_base = payload_base
+    a.d_row_map = row_map.data_ptr() if row_map is not None else None
+    a.n_rows = n_rows
+    ws_bytes = int(lib.exg_gtf_attributes_workspace_bytes(n_rows))
+    ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.int64, device=dev)
+    result = torch.empty(8, dtype=torch.int64, device=dev)
+    a.d_workspace, a.workspace_bytes, a.d_result, a.stream = ws.data_ptr(), ws_bytes, result.data_ptr(), stream_ptr().value
+
+    def call():
+        check(lib.exg_gtf_attributes(C.byref(a)))
+        r = abi.GtfAttributesResult()
+        rc = lib.exg_gtf_attributes_result(C.c_void_p(result.data_ptr()), stream_ptr(), C.byref(r))
+        if rc != 0:
+            try:
+                check(rc)
+            except ExgError as e:
+                e.result = r
+                raise
+        return r
+
+    if entries_capacity is None:
+        entries_capacity = int(call().total_entries)
+    cap = int(entries_capacity)
+    entries = torch.zeros((max(n_rows, 1), 2), dtype=torch.int64, device=dev)
+    keys = torch.zeros((max(cap, 1), 2), dtype=torch.int64, device=dev)
+    values = torch.zeros((max(cap, 1), 2), dtype=torch.int64, device=dev)
+    bases = torch.zeros(((n_rows + chunk_rows - 1) // chunk_rows + 1,), dtype=torch.int64, device=dev) if chunk_rows else None
+    a.d_out_entries, a.d_out_keys, a.d_out_values, a.entries_capacity = entries.data_ptr(), keys.data_ptr(), values.data_ptr(), cap
+    a.chunk_rows, a.d_out_chunk_base = chunk_rows, bases.data_ptr() if chunk_rows else None
+    r = call()
+    k = min(int(r.total_entries), cap) if not (r.flags & abi.EXG_RF_CAPACITY) else 0
+    return entries[:n_rows], keys[:k], values[:k], bases, r
+
+
 class BcfToVcf:
     """exg_bcf_to_vcf on decoded BCF records resident in HBM (d_input[0] is a record start): the two dictionaries as lists indexed
     by dictionary index (bytes, or None where no ID has that index), the header's sample count, an output buffer of

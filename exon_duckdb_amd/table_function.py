@@ -8,6 +8,7 @@ tests, which read like the reference's sqllogictests:
     con.table_function("read_fasta", path, compression="gzip").fetchall()
     con.from_path("x/test.fasta")                     # replacement scan
     con.table_function("read_bcf_file_records", "x/calls.bcf").fetchall()   # the VCF schema of the file's own header
+    con.table_function("read_gtf", "x/genes.gtf").fetchall()    # attributes: MAP(VARCHAR, VARCHAR) -> [(key, value), ...]
 """
 import ctypes as C
 
@@ -56,6 +57,8 @@ def type_sql(tree):
     tid, _, kids = tree
     if tid == abi.EXG_TYPE_LIST:
         return type_sql(kids[0]) + "[]"
+    if tid == abi.EXG_TYPE_MAP:
+        return "MAP(" + ", ".join(type_sql(k) for k in kids[0][2]) + ")"
     if tid == abi.EXG_TYPE_STRUCT:
         return "STRUCT(" + ", ".join(f"{k[1]} {type_sql(k)}" for k in kids) + ")"
     return {abi.EXG_TYPE_VARCHAR: "VARCHAR", abi.EXG_TYPE_BIGINT: "BIGINT", abi.EXG_TYPE_FLOAT: "FLOAT",
@@ -89,6 +92,10 @@ def decode_vector(vec, tree):
                     assert o + l <= len(child), "list entry outside the chunk's child vector"
                     out.append(child[o:o + l])
         return out
+    if tid == abi.EXG_TYPE_MAP:
+        # LIST's layout over a STRUCT of key and value -> the (key, value) pairs in file order (a key may repeat: not a dict)
+        rows = decode_vector(vec, (abi.EXG_TYPE_LIST, "", kids))
+        return [None if r is None else [(e["key"], e["value"]) for e in r] for r in rows]
     if tid == abi.EXG_TYPE_STRUCT:
         cols = [decode_vector(vec.children[i], kids[i]) for i in range(vec.n_children)]
         names = [k[1] for k in kids]
@@ -321,7 +328,7 @@ class Relation:
 
 
 def abi_type(name):
-    return {"VARCHAR": 1, "BIGINT": 2, "FLOAT": 3, "INTEGER": 4, "BOOLEAN": 5, "LIST": 6, "STRUCT": 7}[name]
+    return {"VARCHAR": 1, "BIGINT": 2, "FLOAT": 3, "INTEGER": 4, "BOOLEAN": 5, "LIST": 6, "STRUCT": 7, "MAP": 8}[name]
 
 
 class Connection:

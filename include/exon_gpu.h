@@ -123,6 +123,15 @@ extern "C" {
 #define EXG_PE_BCF_DICT_INDEX 53      /* BCF: a FILTER / INFO / FORMAT key is not an index of the header's string dictionary */
 #define EXG_PE_BCF_NO_ALLELE 54       /* BCF: n_allele = 0 (a record has at least REF) */
 #define EXG_PE_BCF_SAMPLE_COUNT 55    /* BCF: n_sample differs from the header's sample count */
+/* (56 stays unassigned, like 29, 34, 43 and 46: callers probe it to see "unknown parse error") */
+#define EXG_PE_GTF_FIELD_COUNT 57     /* GTF: a line with fewer than 9 tab-separated fields (an empty line among them) */
+#define EXG_PE_GTF_EMPTY_FIELD 58     /* GTF: seqname or type is empty */
+#define EXG_PE_GTF_POSITION 59        /* GTF: start or end is not made of digits only, is 0 or above 2^63 - 1 */
+#define EXG_PE_GTF_SCORE 60           /* GTF: score is neither `.` nor a float literal */
+#define EXG_PE_GTF_STRAND 61          /* GTF: strand is not `+`, `-`, `?` or `.` */
+#define EXG_PE_GTF_FRAME 62           /* GTF: frame is not `0`, `1`, `2` or `.` */
+#define EXG_PE_GTF_ATTRIBUTES 63      /* GTF (exg_gtf_attributes): an entry without a value, an unterminated quote, a quote that does
+                                       * not begin a value, or bytes behind a closing quote other than spaces and `;` */
 
 /* ---- duckdb::string_t, bit-for-bit (v0.8.1 duckdb/common/types/string_type.hpp)
  * length <= 12: bytes inlined, zero padded.  Otherwise 4-byte prefix + pointer.
@@ -150,6 +159,7 @@ typedef union exg_string_t {
 #define EXG_FMT_SAM 6 /* reader level + exg_sam_scan; the chunk boundary only (new_reader refuses it) */
 #define EXG_FMT_BCF 7 /* reader level (file_format "bcf": records become VCF lines on the device, exg_bcf_to_vcf, and take the
                        * VCF path from there: both boundaries, the schema of the file's own header) */
+#define EXG_FMT_GTF 8 /* reader level + exg_gtf_scan / exg_gtf_attributes; the chunk boundary only (new_reader refuses it) */
 
 /* ---- scan flags ------------------------------------------------------------ */
 #define EXG_F_BOF 1u /* a line starts at d_input[0] (start of file, or a record-aligned batch) */
@@ -167,6 +177,7 @@ typedef union exg_string_t {
 #define EXG_RF_QUAL_RANGE 32u /* VCF: more QUAL literals of one launch needed the exact big-integer parser (> 19 digits astride a float
                                  rounding boundary) than its list holds (one per 32 bytes of input, at most 4096); the next was rejected */
 
+#define EXG_RF_ROWS_SKIPPED 128u /* GTF: at least one line of the buffer gave no row (a `#` line): d_keep says which rows are features */
 /* algorithm selector (exg_*_scan_args.algo) */
 #define EXG_RF_REDO 64u     /* the lean scan marked super-tiles — a record / line that begins more than 1 KiB in front of the 16 KiB
                              * half it ends in (long reads, multi-sample VCF), more lines in a half than its list holds (reads
@@ -381,6 +392,42 @@ typedef struct exg_sam_scan_args {
     void *stream;
 } exg_sam_scan_args;
 
+/* GTF (read_gtf): one row per feature line, nine columns (test_gtf_scan.test:6-16 pins a row; the value rules are
+ * INTEGRATION.md's):
+ *   0 seqname VARCHAR, 1 source VARCHAR, 2 type VARCHAR, 3 start BIGINT, 4 end BIGINT, 5 score FLOAT?, 6 strand VARCHAR?,
+ *   7 frame VARCHAR?, 8 attributes — here the RAW ninth field as one string_t per row (everything behind the eighth tab);
+ *   exg_gtf_attributes turns that column into the MAP(VARCHAR, VARCHAR) children.
+ * A line has nine tab-separated fields; a line whose first byte is `#` gives no row.  The scan numbers rows by LINES:
+ * n_records, capacity_records and the row indices of the columns count every line of the buffer, comment lines included (their
+ * slots are not written).  d_keep, one validity-style word array, says which rows are feature lines (bit r set); the result
+ * flag EXG_RF_ROWS_SKIPPED says that at least one is not.  With EXG_F_NO_STORE d_keep is not written (the flag still is).
+ * Strings are zero-copy slices of the input (payload_base + offset; up to 12 bytes inlined).  A NULL value holds zeros.
+ * score takes VCF QUAL's literal grammar and exact rounding (a literal of more than 19 digits astride a rounding boundary is
+ * decided by a fix-up kernel behind the scan; more than 1024 of them in one launch: EXG_PE_GTF_SCORE).
+ * lead, flags, algo and the result block are exg_bed_scan's: EXG_ALGO_MULTIPASS is the general path, EXG_ALGO_AUTO /
+ * EXG_ALGO_FUSED / EXG_ALGO_FUSED_FULL all run the single-pass any-shape scan, EXG_ALGO_FUSED_INDEX is EXG_E_INVALID_ARG.  The
+ * general path's line index is provisioned for a line per 16 bytes: a buffer of denser lines (runs of `#` lines) reports
+ * EXG_RF_INDEX_OVERFLOW there and wants a larger workspace; the single-pass scan takes any density. */
+#define EXG_GTF_COLUMNS 9
+typedef struct exg_gtf_scan_args {
+    const void *d_input; /* device pointer, 16-byte aligned, readable up to round_up(n_bytes,16) */
+    uint64_t n_bytes;
+    uint64_t lead;
+    uint64_t payload_base;
+    uint32_t flags;
+    uint32_t algo;
+    void *d_columns[EXG_GTF_COLUMNS];      /* device: exg_string_t[capacity_records] for columns 0, 1, 2, 6, 7, 8; int64_t[] for 3, 4;
+                                            * float[] for 5.  NULL = not produced, still validated */
+    uint64_t *d_validity[EXG_GTF_COLUMNS]; /* device: ceil(capacity / 64) words for columns 5, 6, 7 (when produced) */
+    uint64_t *d_keep;                      /* device: ceil(capacity / 64) words, bit r = row r is a feature line; required unless
+                                            * EXG_F_NO_STORE */
+    uint64_t capacity_records;
+    void *d_workspace; /* device, exg_scan_workspace_bytes(EXG_FMT_GTF, n_bytes), 256-byte aligned */
+    uint64_t workspace_bytes;
+    exg_scan_result *d_result; /* device, 64 bytes */
+    void *stream;
+} exg_gtf_scan_args;
+
 /* BCF 2.2 records -> the VCF data lines they stand for (VCF 4.3 spec section 6.3), on decoded bytes resident in HBM.
  * d_input begins at a record start (the caller has taken the header off).  The lines of all records that lie completely
  * inside the buffer are written to d_output in order, each ended by LF, closed up.  The two dictionaries of the file's header
@@ -449,6 +496,8 @@ int exg_bam_scan(const exg_bam_scan_args *args);
 int exg_bed_scan(const exg_bed_scan_args *args);
 /* Enqueue on args->stream; asynchronous (the result through exg_fetch_result). */
 int exg_sam_scan(const exg_sam_scan_args *args);
+/* Enqueue on args->stream; asynchronous (the result through exg_fetch_result). */
+int exg_gtf_scan(const exg_gtf_scan_args *args);
 /* BCF records -> VCF lines (see exg_bcf_to_vcf_args).  Synchronises args->stream. */
 uint64_t exg_bcf_workspace_bytes(uint64_t n_bytes, uint32_t n_samples);
 int exg_bcf_to_vcf(const exg_bcf_to_vcf_args *args);
@@ -744,6 +793,56 @@ int exg_cigar_op(const exg_cigar_op_args *args);
  * either way. */
 int exg_cigar_result(const struct exg_cigar_result *d_result, void *stream, struct exg_cigar_result *out);
 
+/* ---- GTF attributes on a device-resident column -------------------------------------------------------------
+ * The ninth field of GTF lines (column 8 of exg_gtf_scan, or any exg_string_t column) -> the children of a
+ * MAP(VARCHAR, VARCHAR): for row j of the call (row d_row_map[j] of the column when a row map is given) the entries
+ * `key value` of the field in file order, a repeated key being a second entry.  The grammar is INTEGRATION.md's (GTF):
+ * entries are separated by `;` outside quotes, a value is `"..."` (quotes not part of it, `;` and spaces allowed inside) or a
+ * run of bytes that are neither space, `;` nor `"`; blank segments are skipped.  Keys and values are zero-copy slices of the
+ * input's bytes under the same payload_base (up to 12 bytes inlined): there is no output payload.
+ * d_out_entries[j] = {entries in front of row j, entries of row j} — with chunk_rows != 0 the offset is relative to the
+ * first entry of the row's chunk of chunk_rows rows and d_out_chunk_base[c] (ceil(n_rows / chunk_rows) + 1 words) is where
+ * chunk c's entries begin in the children (the layout of exg_vector LIST children).  total_entries > entries_capacity:
+ * EXG_RF_CAPACITY, neither child is touched, total_entries is exact (when no row fails) and the rows are validated all the same;
+ * entries_capacity = 0 with NULL children is the counting call of a two-call protocol.
+ * Errors: the lowest failing row wins, in it the leftmost offset at which a left-to-right parser stops (an unterminated
+ * quote: the offset of the quote; an entry without a value at the end of the field: the field's length, byte 0).  With an
+ * error the result block is exact and the outputs are unspecified.  A wavefront takes a row, 64 bytes a step.
+ * Deterministic; no host round trip between the passes; n_rows = 0 is valid; n_rows < 2^32 - 1. */
+struct exg_gtf_attributes_result { /* 64 bytes, written by the device */
+    uint64_t total_entries; /* entries of all rows */
+    uint64_t error_row;     /* lowest failing row (an index of the call's rows) */
+    uint64_t error_offset;  /* byte offset in that row's field */
+    uint64_t n_rows;
+    uint32_t error_code;    /* 0 or EXG_PE_GTF_ATTRIBUTES */
+    uint32_t flags;         /* EXG_RF_CAPACITY: total_entries > entries_capacity, no child was written */
+    uint8_t error_byte;     /* the byte at error_offset (0 when that is the field's length) */
+    uint8_t pad[23];
+};
+typedef struct exg_gtf_attributes_args {
+    const exg_string_t *d_strings;   /* device, 16-byte aligned */
+    const void *d_payload;           /* device bytes the non-inlined strings point into */
+    uint64_t payload_base;           /* string_t.ptr - payload_base = byte offset in d_payload */
+    const uint32_t *d_row_map;       /* optional: device, n_rows row numbers of d_strings (NULL: rows 0 .. n_rows - 1) */
+    uint64_t n_rows;
+    uint64_t chunk_rows;             /* 0, or rows per chunk (list offsets relative to the chunk's first entry) */
+    exg_list_entry_t *d_out_entries; /* out: device, 8-byte aligned, n_rows entries (may be NULL in the counting call) */
+    uint64_t *d_out_chunk_base;      /* out: device, ceil(n_rows / chunk_rows) + 1 words; NULL when chunk_rows is 0 */
+    exg_string_t *d_out_keys;        /* out: device, 16-byte aligned, entries_capacity entries */
+    exg_string_t *d_out_values;      /* out: device, 16-byte aligned, entries_capacity entries */
+    uint64_t entries_capacity;
+    void *d_workspace;               /* device, 8-byte aligned, exg_gtf_attributes_workspace_bytes(n_rows) */
+    uint64_t workspace_bytes;
+    struct exg_gtf_attributes_result *d_result; /* device, 64 bytes, 8-byte aligned */
+    void *stream;
+} exg_gtf_attributes_args;
+uint64_t exg_gtf_attributes_workspace_bytes(uint64_t n_rows);
+/* Enqueue on args->stream; asynchronous. */
+int exg_gtf_attributes(const exg_gtf_attributes_args *args);
+/* Synchronising copy of the 64-byte result to the host.  error_code != 0: EXG_E_PARSE, and the thread's last error message is
+ * `Invalid GTF attributes in row <r> at byte <k>`; *out is filled either way. */
+int exg_gtf_attributes_result(const struct exg_gtf_attributes_result *d_result, void *stream, struct exg_gtf_attributes_result *out);
+
 /* ---- device inflate (gzip / BGZF members; replaces flate2 behind rust/src/arrow_reader.rs:60-91) ---- */
 typedef struct exg_inflate_member {
     uint64_t comp_off;  /* offset of the member's DEFLATE stream (after the gzip header) in d_comp */
@@ -850,7 +949,7 @@ typedef struct exg_reader exg_reader;
 
 typedef struct exg_open_args {
     const char *path;        /* local file or directory (the reference lists directories: test_fasta_scan.test:55-59) */
-    const char *file_format; /* "fasta" | "fastq" | "vcf" | "bam" | "bed" | "sam" (the reference's file_type strings,
+    const char *file_format; /* "fasta" | "fastq" | "vcf" | "bam" | "bed" | "sam" | "bcf" | "gtf" (the reference's file_type strings,
                               * exon_extension.cpp:47-58; any case).  A BAM file is always read as gzip members (BGZF), whatever
                               * `compression` says, and as ONE shard (shard_count > 1: EXG_E_UNSUPPORTED).  "bed": text without a
                               * header, every line a record; "sam": the leading '@' lines are skipped at open, every line behind
@@ -901,6 +1000,7 @@ typedef struct exg_open_args {
 #define EXG_TYPE_BOOLEAN 5 /* one byte per value (DuckDB BOOLEAN) */
 #define EXG_TYPE_LIST 6    /* data = exg_list_entry_t[] (DuckDB list_entry_t), children[0] = the elements */
 #define EXG_TYPE_STRUCT 7  /* no data of its own; children = the fields, each as long as the parent */
+#define EXG_TYPE_MAP 8     /* DuckDB MAP: LIST's layout — data = exg_list_entry_t[], children[0] = a STRUCT of `key` and `value` */
 
 /* The full type of a column.  The VCF columns carry the reference's schema (what DuckDB's Arrow conversion makes of
  * exon's Arrow schema, exon/src/exon/arrow_table_function/module.cpp:126-147; pinned by test_vcf_record_scan.test:10-19):
@@ -1053,7 +1153,7 @@ typedef struct ReaderResult {
  * the `filters` predicate and the Arrow buffers themselves (offsets, values, validity) are produced
  * on the device; the host only copies them back and wires the ArrowArray structs.
  *   compression: NULL = by extension (:60-75), else DataFusion's FileCompressionType names (:77-91)
- *   file_format: "fasta" | "fastq" | "vcf" ("bam", "bed" and "sam" are refused: they are served at the chunk boundary, exg_open, only)
+ *   file_format: "fasta" | "fastq" | "vcf" ("bam", "bed", "sam" and "gtf" are refused: they are served at the chunk boundary, exg_open, only)
  *   filters:     NULL / "" or the predicate text FilterToString renders (module.cpp:158-214):
  *                <column> (= | != | <> | < | <= | > | >=) <literal>, <column> IS [NOT] NULL, AND, OR
  *                with SQL precedence; it is applied as `SELECT * FROM exon_table WHERE <filters>` (:125-141). */
