@@ -20,6 +20,7 @@
 #include "exg_filter.hpp"
 #include "exg_rd_bam.hpp"
 #include "exg_rd_source.hpp"
+#include "exg_rd_stages.hpp"
 
 namespace exg_rd {
 
@@ -31,11 +32,10 @@ struct BamState {
     std::shared_ptr<PinnedBlock> names;  // the reference names on the host (pinned, pooled): kept alive by every batch
     void *d_names = nullptr, *d_offsets = nullptr;
     size_t d_names_bytes = 0, d_offsets_bytes = 0;
-    // the scan's buffers (the reader's dev_alloc: freed with the reader, or when a batch needs larger ones)
-    void *d_ws = nullptr, *d_side = nullptr, *d_cols[EXG_BAM_COLUMNS] = {}, *d_valid[EXG_BAM_COLUMNS] = {};
-    void *d_row_map = nullptr, *d_gather = nullptr, *d_filter_tmp = nullptr;
-    uint64_t in_cap = 0, side_cap = 0, cap_records = 0;
-    bool worst_case_rows = false;
+    // the scan's workspace and side buffer (the reader's dev_alloc: freed with the reader, or when a batch needs larger ones); the
+    // columns, validity words, row map and gather scratch are the reader's own fields, provisioned here with BAM's sizing
+    void *d_ws = nullptr, *d_side = nullptr;
+    uint64_t in_cap = 0, side_cap = 0;  // (in_cap = 0: provision again)
     uint64_t rows_before = 0;  // records of the current file in front of the current batch (a record error names its ordinal)
     std::atomic<uint64_t> tiles{0}, tiles_rewalked{0};
     void drop_tables() {
@@ -55,8 +55,6 @@ BamState *state_of(exg_reader *r) {
     return (BamState *)r->bam_state.get();
 }
 
-const FormatDesc &kBam = format_desc(EXG_FMT_BAM);  // (the columns' widths and which are nullable: exg_rd_format.hpp)
-
 int ensure_buffers(exg_reader *r, BamState *s, uint64_t n, uint64_t side_bytes) {
     if (s->d_ws && n <= s->in_cap && side_bytes <= s->side_cap) return EXG_OK;
     if (s->d_ws) {
@@ -67,24 +65,15 @@ int ensure_buffers(exg_reader *r, BamState *s, uint64_t n, uint64_t side_bytes) 
     s->in_cap = std::max<uint64_t>(n, r->device_batch_bytes + r->device_batch_bytes / 4 + (r->src ? r->src->reserve() : 0) + 4096);
     // rows: a 150 bp read is ~350 bytes, one per 64 bytes is dense; the smallest record there can be is 37 bytes — a batch
     // that holds more rows than provisioned is found out before a column is written and provisioned for the worst case
-    s->cap_records = s->worst_case_rows ? s->in_cap / exg::bam::kMinRecordBytes + 2 : s->in_cap / 64 + 4096;
+    r->cap_records = r->worst_case_rows ? s->in_cap / exg::bam::kMinRecordBytes + 2 : s->in_cap / 64 + 4096;
     // side buffer: name + CIGAR text + sequence + qualities of a 150 bp read are about its own bytes (the sequence doubles,
     // the aux fields are dropped); a batch that needs more says so before anything is written
     s->side_cap = std::max<uint64_t>(side_bytes, s->in_cap + s->in_cap / 4);
     int rc;
     if ((rc = r->dev_alloc(&s->d_ws, exg_scan_workspace_bytes(EXG_FMT_BAM, s->in_cap)))) return rc;
     if ((rc = r->dev_alloc(&s->d_side, s->side_cap + 64))) return rc;
-    const uint64_t produce = r->want_cols | r->filter_cols;
-    for (int c = 0; c < EXG_BAM_COLUMNS; c++) {
-        if (!((produce >> c) & 1)) continue;
-        if ((rc = r->dev_alloc(&s->d_cols[c], s->cap_records * kBam.col[c].elem))) return rc;
-        if (kBam.col[c].validity && (rc = r->dev_alloc(&s->d_valid[c], (s->cap_records + 63) / 64 * 8))) return rc;
-    }
-    if (r->has_filter) {
-        if ((rc = r->dev_alloc(&s->d_row_map, s->cap_records * 4 + 64))) return rc;
-        if ((rc = r->dev_alloc(&s->d_gather, std::max<uint64_t>(s->cap_records * 16, sizeof(ea::FilterCols))))) return rc;
-        if ((rc = r->dev_alloc(&s->d_filter_tmp, (s->cap_records + 1 + ea::scan_tmp_entries(s->cap_records)) * 8))) return rc;
-    }
+    if ((rc = alloc_columns(r, r->want_cols | r->filter_cols))) return rc;  // (only what is selected or the predicate reads)
+    if (r->has_filter && (rc = alloc_row_selection(r))) return rc;
     if (!r->d_res && !(r->d_res = dev_pool()->take(r->device, 4096))) return fail(r, EXG_E_HIP, "out of device memory");
     return EXG_OK;
 }
@@ -98,24 +87,24 @@ int bam_open_file(exg_reader *r) {
     RD_HIP(r, hipStreamSynchronize(r->stream));  // (a batch of the file before may still read the tables)
     s->drop_tables();
     PinBuf host;
-    for (uint64_t want = 64u << 10;;) {
+    auto front = [&](uint64_t want, uint64_t *avail, bool *eof) {
         const uint8_t *d_at = nullptr;
-        uint64_t avail = 0;
-        bool eof = false;
         std::string msg;
-        int rc = r->src->acquire(0, want, &d_at, &avail, &eof, &msg);
+        int rc = r->src->acquire(0, want, &d_at, avail, eof, &msg);
         if (rc) return fail(r, rc, msg + (msg.find(path) == std::string::npos ? in_file(path) : ""));
-        const uint64_t len = std::min<uint64_t>(want, avail);
+        const uint64_t len = std::min<uint64_t>(want, *avail);
         if (!host.ensure((size_t)len + 64)) return fail(r, EXG_E_HIP, "out of pinned host memory for the BAM header");
         if (len) RD_HIP(r, hipMemcpyAsync(host.p, d_at, len, hipMemcpyDeviceToHost, r->stream));
         RD_HIP(r, hipStreamSynchronize(r->stream));
-        uint64_t need = 0;
+        return (int)EXG_OK;
+    };
+    auto inspect = [&](uint64_t len, bool ended, uint64_t *need) {
         std::string why;
-        const int prc = bam_parse_header((const uint8_t *)host.p, len, eof && len == avail, &s->header, &need, &why);
+        const int prc = bam_parse_header((const uint8_t *)host.p, len, ended, &s->header, need, &why);
         if (prc == kBamHeaderBad) return fail(r, EXG_E_PARSE, why + in_file(path));
-        if (prc == kBamHeaderOk) break;
-        want = std::max<uint64_t>(need, want * 2);
-    }
+        return prc == kBamHeaderOk ? (int)kPrefixDone : (int)kPrefixMore;
+    };
+    if (int rc = read_prefix(64u << 10, front, inspect, prefix_grow_need_or_double)) return rc;
     // the reference names: a pinned table of the reader's (the batches keep it alive), and a copy on the device
     const BamHeader &h = s->header;
     auto blk = std::make_shared<PinnedBlock>();
@@ -146,9 +135,9 @@ namespace {
 
 // what discover() found, against what is provisioned (nothing has been written yet)
 enum BamVerdict { kBamAccept, kBamWiden, kBamWorstCaseRows, kBamFailRows, kBamGrowSide };
-BamVerdict bam_judge(const exg_bam_scan_result &res, const BamState *s, bool eof, bool no_store) {
+BamVerdict bam_judge(const exg_bam_scan_result &res, const exg_reader *r, const BamState *s, bool eof, bool no_store) {
     if (res.n_records == 0 && !res.error_code && !eof) return kBamWiden;  // one record larger than the batch
-    if (!no_store && res.n_records > s->cap_records) return s->worst_case_rows ? kBamFailRows : kBamWorstCaseRows;
+    if (!no_store && res.n_records > r->cap_records) return r->worst_case_rows ? kBamFailRows : kBamWorstCaseRows;
     if (!no_store && res.side_bytes > s->side_cap) return kBamGrowSide;
     return kBamAccept;
 }
@@ -158,44 +147,26 @@ BamVerdict bam_judge(const exg_bam_scan_result &res, const BamState *s, bool eof
 int bam_select_rows(exg_reader *r, BamState *s, const exg_bam_scan_args &a, uint64_t *k, const uint32_t **row_map) {
     ea::FilterCols fc;
     memset(&fc, 0, sizeof fc);
-    for (int c = 0; c < EXG_BAM_COLUMNS; c++) {
-        fc.kind[c] = filter_col_kind(kBam.col[c]);
-        fc.data[c] = s->d_cols[c];
-        fc.validity[c] = (const uint64_t *)s->d_valid[c];
+    for (int c = 0; c < EXG_BAM_COLUMNS; c++) {  // reference and mate_reference point into the name table, the rest into the side buffer
         const bool ref = c == 2 || c == 7;
         fc.d_base[c] = ref ? (const uint8_t *)s->d_names : (const uint8_t *)s->d_side;
         fc.payload_base[c] = ref ? a.ref_names_base : a.side_base;
     }
-    uint64_t *d_goff = (uint64_t *)s->d_filter_tmp, *d_tmp = d_goff + s->cap_records + 1;
-    ea::FilterCols *d_fc = (ea::FilterCols *)s->d_gather;  // (the scratch column is free until the gathers)
-    RD_HIP(r, ea::select_rows(fc, (const ea::FilterProgram *)r->d_filter_prog, (const uint8_t *)r->d_filter_consts, *k, d_goff, d_tmp,
-                              (uint32_t *)s->d_row_map, d_fc, r->stream, k));
-    *row_map = (const uint32_t *)s->d_row_map;
-    return EXG_OK;
+    return select_rows(r, &fc, nullptr, k, row_map);
 }
 
+// the vectors on the scan's stream, and the side buffer whole behind them
 int bam_columns_to_host(exg_reader *r, BamState *s, const std::shared_ptr<Batch> &b, const exg_bam_scan_result &res, uint8_t *h_side, uint64_t k,
                         const uint32_t *row_map) {
     TraceRange d2h_range("exg: columns -> host");
-    b->n_rows = k;
-    b->n_cols = EXG_BAM_COLUMNS;
-    bool any_side = false;
-    for (int c = 0; c < EXG_BAM_COLUMNS; c++) {
-        b->elem[c] = 0, b->cols[c] = nullptr;
-        if (!r->want(c)) continue;
-        b->elem[c] = kBam.col[c].elem;
-        if (int rc = column_to_host(r, b.get(), c, s->d_cols[c], b->elem[c], kBam.col[c].validity ? s->d_valid[c] : nullptr, k, row_map, s->d_gather, r->stream))
-            return rc;
-        any_side |= c == 0 || c == 6 || c == 8 || c == 9;
-    }
-    if (any_side && res.side_bytes) {
+    if (int rc = flat_columns_to_host(r, b.get(), k, row_map, r->stream, nullptr)) return rc;
+    const uint64_t side_cols = 1ull << 0 | 1ull << 6 | 1ull << 8 | 1ull << 9;  // name, cigar, sequence, quality_score
+    if ((r->want_cols & side_cols) && res.side_bytes) {
         RD_HIP(r, hipMemcpyAsync(h_side, s->d_side, res.side_bytes, hipMemcpyDeviceToHost, r->stream));
         r->host_vector_bytes += res.side_bytes;  // (the strings' payload is made on the device: it is part of the vectors)
     }
     RD_HIP(r, hipStreamSynchronize(r->stream));
-    r->host_hint = b->host.total + b->host.total / 8 + (1u << 20);
-    b->seq = r->batch_seq++;
-    r->batch = b;
+    publish_batch(r, b);
     return EXG_OK;
 }
 
@@ -242,12 +213,12 @@ int bam_next_batch(exg_reader *r, bool count_only, uint64_t *n_records_out) {
         if ((rc = exg::bam::discover(&a, &res))) return fail(r, rc, exg_last_error_message());
         r->n_batches++;
         s->tiles += res.tiles, s->tiles_rewalked += res.tiles_rewalked;
-        switch (bam_judge(res, s, eof, no_store)) {  // (the only place that scans the batch again)
+        switch (bam_judge(res, r, s, eof, no_store)) {  // (the only place that scans the batch again)
             case kBamAccept: break;
             case kBamWiden: want = std::max<uint64_t>(want, n) * 2; continue;
             case kBamFailRows: return fail(r, EXG_E_CAPACITY, "more BAM records than bytes allow: internal error");
             case kBamWorstCaseRows:  // denser rows than provisioned: worst-case vectors, same batch again
-                s->worst_case_rows = true;
+                r->worst_case_rows = true;
                 s->in_cap = 0;
                 continue;
             case kBamGrowSide:
@@ -269,11 +240,11 @@ int bam_next_batch(exg_reader *r, bool count_only, uint64_t *n_records_out) {
             b->file = s->names;
             uint8_t *h_side = nullptr;
             if (res.side_bytes && !(h_side = (uint8_t *)b->host.alloc(res.side_bytes + 64))) return fail(r, EXG_E_HIP, "out of pinned host memory");
-            for (int c = 0; c < EXG_BAM_COLUMNS; c++) a.d_columns[c] = s->d_cols[c], a.d_validity[c] = (uint64_t *)s->d_valid[c];
+            for (int c = 0; c < EXG_BAM_COLUMNS; c++) a.d_columns[c] = r->d_cols[c], a.d_validity[c] = (uint64_t *)r->d_col_valid[c];
             a.d_side = (uint8_t *)s->d_side;
             a.side_capacity = s->side_cap;
             a.side_base = (uint64_t)(uintptr_t)h_side;
-            a.capacity_records = s->cap_records;
+            a.capacity_records = r->cap_records;
             if ((rc = exg::bam::emit(&a, &res))) return fail(r, rc, exg_last_error_message());
             const uint32_t *row_map = nullptr;
             if (r->has_filter && (rc = bam_select_rows(r, s, a, &k, &row_map))) return rc;

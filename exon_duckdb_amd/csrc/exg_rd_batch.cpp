@@ -1,5 +1,6 @@
-// exg_rd_batch.cpp — reader level: a file is opened (mapped, or handed to a decoder), then scanned one device batch at a
-// time: bytes -> HBM (prefetched slot / decoded segment / synchronous upload) -> scan kernels -> the batch's host vectors.
+// exg_rd_batch.cpp — reader level: an open file (exg_rd_open.cpp) is scanned one device batch at a time: bytes -> HBM
+// (prefetched slot / decoded segment / synchronous upload) -> scan kernels -> what the result means for the attempt; the rows
+// that leave take exg_rd_rows_out.cpp's way to the batch's host vectors, or the Arrow emitter's.
 // Replaces exon's BatchReader::read_batch loop behind the stream `new_reader` returns (rust/src/arrow_reader.rs:116-153)
 // and the per-batch pull in WTArrowTableFunction::Scan (exon/src/exon/arrow_table_function/module.cpp:257-294).
 //
@@ -8,16 +9,11 @@
 // receives a decoded batch), i.e. the DataChunk payload is zero-copy and only 64 B/record of string_t + validity cross
 // PCIe on the way back.  Chunks are 2048-row slices of the batch's host vectors, reference counted until
 // exg_release_chunk.
-#include <errno.h>
-#include <fcntl.h>
 #include <string.h>
-#include <sys/mman.h>
-#include <sys/stat.h>
-#include <unistd.h>
 
 #include <algorithm>
 #include <memory>
-#include <thread>
+#include <type_traits>
 
 #include "exg_fastq_ws.hpp"
 #include "exg_filter.hpp"
@@ -25,499 +21,8 @@
 #include "exg_rd_bam.hpp"
 #include "exg_rd_source.hpp"
 #include "exg_rd_stages.hpp"
-#include "exg_sam_header.hpp"
 
 namespace exg_rd {
-
-// The A/B switches of this file, read once per process.  (EXG_NO_VCF_INDEX and EXG_VCF_ONE_STREAM are not here: they are read per
-// batch, where they are used — the tests switch them inside one process.)
-namespace {
-struct Switches {
-    const bool fasta_whole_text = getenv("EXG_FASTA_WHOLE_TEXT") != nullptr;      // a decoded FASTA: the decoded text behind the scan, no side buffer
-    const bool no_payload_compact = getenv("EXG_NO_PAYLOAD_COMPACT") != nullptr;  // a projection of a decoded input: no side buffer
-    const bool no_host_mirror = getenv("EXG_NO_HOST_MIRROR") != nullptr;          // (and tests) a decoded input: the copy behind the scan
-    const bool no_ramp = getenv("EXG_NO_RAMP") != nullptr;                        // a text file's first batch is a full one
-    const bool no_fasta_prefetch = getenv("EXG_NO_FASTA_PREFETCH") != nullptr;    // FASTA: one input slot, no upload beside the way back
-    const bool no_prefetch = getenv("EXG_NO_PREFETCH") != nullptr;                // no upload ahead of the scan
-    const bool fastq_one_stream = getenv("EXG_FASTQ_ONE_STREAM") != nullptr;      // a text FASTQ's vectors on the scan's stream
-    const bool vcf_eager_landing = getenv("EXG_VCF_EAGER_LANDING") != nullptr;    // read_vcf waits for its vectors inside next_batch
-    const bool fasta_d2h_engine = getenv("EXG_FASTA_D2H_ENGINE") != nullptr;      // FASTA: the joined sequences by a copy engine
-};
-const Switches &switches() {
-    static const Switches s;
-    return s;
-}
-}  // namespace
-
-// ---- compressed inputs: the file becomes a stream of decoded segments (exg_rd_source.hpp) --------------------------------
-
-// room every segment leaves in front of its bytes for the tail the scan carries over (a longer tail moves into a block of its own)
-static uint64_t source_reserve(const exg_reader *r) { return std::min<uint64_t>(std::max<uint64_t>(r->device_batch_bytes / 8, 64u << 10), 8u << 20); }
-
-// the formats whose text begins with a header, and the byte its lines begin with (VCF: parsed; SAM: only skipped)
-static bool has_text_header(const exg_reader *r) { return r->format == EXG_FMT_VCF || r->format == EXG_FMT_SAM; }
-static char header_marker(const exg_reader *r) { return r->format == EXG_FMT_SAM ? '@' : '#'; }
-
-// The leading '#' lines of a decoded VCF ('@' lines of a SAM) come back to the host for the header parse (blk->p holds a prefix
-// of the decoded stream; the DataChunk payload travels per batch): `src` is read from its first byte until a line that does
-// not start with the marker begins inside the prefix, or the stream ends.
-static int source_header_prefix(exg_reader *r, DecodedSource *src, PinnedBlock &b) {
-    // (not more than a device batch at first: what is acquired here is the first batch's size, which sizes the scan's buffers)
-    for (uint64_t want = std::min<uint64_t>(4u << 20, r->device_batch_bytes);; want *= 8) {
-        const uint8_t *d_at = nullptr;
-        uint64_t avail = 0;
-        bool eof = false;
-        std::string msg;
-        int rc = src->acquire(0, want, &d_at, &avail, &eof, &msg);
-        if (rc) return fail(r, rc, msg);
-        const size_t len = (size_t)std::min<uint64_t>(want, avail);
-        if (b.p) global_pool()->give((char *)b.p, b.cap), b.p = nullptr;
-        size_t cap = len + 64;
-        b.p = global_pool()->take(&cap);
-        if (!b.p) return fail(r, EXG_E_HIP, "out of pinned host memory for the VCF header");
-        b.cap = cap;
-        b.pooled = true;
-        if (len) RD_HIP(r, hipMemcpyAsync(b.p, d_at, len, hipMemcpyDeviceToHost, r->stream));
-        RD_HIP(r, hipStreamSynchronize(r->stream));
-        const size_t pos = leading_lines_end((const char *)b.p, len, header_marker(r));
-        if (pos < len || (eof && len == avail)) {
-            r->gz_header_prefix = len;
-            return EXG_OK;
-        }
-    }
-}
-
-// The first FASTA record start ('>' at the beginning of a line) of a decoded stream at or behind `from` (~0: none before the
-// stream ends).  Everything from `from` on stays resident: the record that begins there is the next batch.
-static int source_find_record(exg_reader *r, uint64_t from, uint64_t *found) {
-    *found = ~0ull;
-    if (!r->d_phase && !(r->d_phase = dev_pool()->take(r->device, 4096))) return fail(r, EXG_E_HIP, "out of device memory");
-    const uint64_t base = from ? from - 1 : 0;  // (the byte in front says whether `from` begins a line)
-    for (uint64_t want = r->device_batch_bytes;; want *= 2) {
-        const uint8_t *d_at = nullptr;
-        uint64_t avail = 0;
-        bool eof = false;
-        std::string msg;
-        int rc = r->src->acquire(base, want, &d_at, &avail, &eof, &msg);
-        if (rc) return fail(r, rc, msg);
-        if (base + avail > from) {
-            unsigned long long pos = ~0ull;
-            rc = exg_fasta_find_record(d_at, from - base, avail, base == 0 && r->data0_is_line_start, (uint64_t *)r->d_phase, r->stream);
-            if (rc) return fail(r, rc, exg_last_error_message());
-            RD_HIP(r, hipMemcpyAsync(&pos, r->d_phase, 8, hipMemcpyDeviceToHost, r->stream));
-            RD_HIP(r, hipStreamSynchronize(r->stream));
-            if (pos != ~0ull) {
-                *found = base + pos;
-                return EXG_OK;
-            }
-        }
-        if (eof || avail < want) return EXG_OK;
-    }
-}
-
-// Shard `shard_index` of `shard_count` of a BGZF file: a member belongs to the shard in whose 1/shard_count of the FILE's
-// bytes its header begins.  The reader finds its members without indexing the file (a search for a header whose chain holds
-// near each cut: the pointer chase over a whole file costs 110 ms per 10 GB and every rank would pay it) and streams
-// [c_begin, c_end): ~1 MiB (inflated) of members in front of its own — the halo that holds the beginning of the record that
-// ends behind the cut — then its own.  Positions of the reader are offsets in THAT stream.
-static int plan_bgzf_shard(exg_reader *r, const std::string &path, uint64_t n, uint64_t *c_begin, uint64_t *c_end, uint64_t header_bytes) {
-    const int fd = r->fd_keep->fd;
-    Peek peek(nullptr, fd, n);
-    exg_inflate_member probe;
-    if (!bgzf_member_at(peek, 0, &probe))
-        return fail(r, EXG_E_UNSUPPORTED, "shards of a gzip input need BGZF framing (every member carries its size): '" + path + "'");
-    const uint64_t lo = (uint64_t)((unsigned __int128)n * r->shard_index / r->shard_count);
-    const uint64_t hi = r->shard_index + 1 == r->shard_count ? n : (uint64_t)((unsigned __int128)n * (r->shard_index + 1) / r->shard_count);
-    const uint64_t first_own = lo == 0 ? 0 : bgzf_find(nullptr, fd, n, lo);
-    *c_end = hi >= n ? n : std::max<uint64_t>(first_own, bgzf_find(nullptr, fd, n, hi));
-    // candidates for the halo: members that begin in the ~1.5 MiB of file in front of the cut (BGZF does not expand)
-    std::vector<uint64_t> hdr, out;
-    const uint64_t halo_want = r->halo_want;
-    const uint64_t back = halo_want > n ? n : halo_want + (halo_want >> 1) + (128u << 10);
-    for (uint64_t pos = first_own == 0 ? 0 : bgzf_find(nullptr, fd, n, lo > back ? lo - back : 0); pos < first_own;) {
-        exg_inflate_member m;
-        const uint64_t nx = bgzf_member_at(peek, pos, &m);
-        if (!nx) return fail(r, EXG_E_PARSE, "not a BGZF member at byte " + std::to_string(pos) + " of '" + path + "'");
-        hdr.push_back(pos);
-        out.push_back(m.out_cap);
-        pos = nx;
-    }
-    size_t h0 = hdr.size();
-    uint64_t halo_bytes = 0;
-    while (h0 > 0 && halo_bytes < halo_want) halo_bytes += out[--h0];
-    *c_begin = h0 < hdr.size() ? hdr[h0] : first_own;
-    // VCF: where do the members that hold the header end?  A halo that would begin among them is taken from the start of
-    // the file instead, so that the end of the header is a known offset of this reader's stream
-    if (header_bytes && *c_begin != 0) {
-        uint64_t q = 0, sum = 0;
-        while (q < n && sum < header_bytes) {
-            exg_inflate_member m;
-            const uint64_t nx = bgzf_member_at(peek, q, &m);
-            if (!nx) return fail(r, EXG_E_PARSE, "not a BGZF member at byte " + std::to_string(q) + " of '" + path + "'");
-            sum += m.out_cap;
-            q = nx;
-        }
-        if (*c_begin < q) {  // q: compressed offset behind the header's members
-            for (uint64_t pos = 0; pos < *c_begin;) {
-                exg_inflate_member m;
-                const uint64_t nx = bgzf_member_at(peek, pos, &m);
-                if (!nx) return fail(r, EXG_E_PARSE, "not a BGZF member at byte " + std::to_string(pos) + " of '" + path + "'");
-                halo_bytes += m.out_cap;
-                pos = nx;
-            }
-            *c_begin = 0;
-        }
-    }
-    if (*c_begin > *c_end) *c_begin = *c_end;
-    // does any inflated byte follow this reader's members?  (the empty BGZF end marker — or a later shard that owns nothing
-    // else — must not keep the shard with the file's last record from seeing the end of the file)
-    bool bytes_follow = false;
-    for (uint64_t q = *c_end; q < n && !bytes_follow;) {
-        exg_inflate_member m;
-        const uint64_t nx = bgzf_member_at(peek, q, &m);
-        if (!nx) return fail(r, EXG_E_PARSE, "not a BGZF member at byte " + std::to_string(q) + " of '" + path + "'");
-        bytes_follow = m.out_cap != 0;
-        q = nx;
-    }
-    r->own_c_begin = first_own;
-    r->range_preset = true;
-    r->preset_pos = halo_bytes;  // inflated bytes of the members in front of its own
-    r->range_eof = !bytes_follow;
-    r->data0_is_line_start = *c_begin == 0;  // byte 0 of the stream begins a line only when the stream begins with the file
-    return EXG_OK;
-}
-
-// How the bytes a decoded input's strings point into reach the host when chunks are handed out (never for COUNT(*) or the Arrow
-// stream): kPayloadCompact — a projection that leaves payload-bearing columns out: the selected columns' out-of-line strings are
-// closed up into a side buffer behind the scan; kPayloadMirror — the decoded segments themselves, sent ahead by the producer
-// (HostMirror; a segment without one is copied behind its scan); kPayloadNone — no string column is selected.  FASTA (round 6):
-// always the side buffer for id / description — its sequences are joined on the device and travel as that, so the decoded text is
-// needed for the definition lines' strings alone, 2 % of it (the whole text went along until then: a bgzip FASTA into DataChunks
-// sent every byte back twice, 92 ms for 1.96 GB).
-enum PayloadRoute { kPayloadNone, kPayloadCompact, kPayloadMirror };
-static PayloadRoute payload_route(const exg_reader *r) {
-    if (r->format == EXG_FMT_BAM) return kPayloadNone;  // (a BAM segment is never mirrored: its strings are produced into a side buffer)
-    const FormatDesc &f = format_desc(r->format);
-    const uint64_t strs = f.payload_mask(), sel = r->want_cols & strs;  // the columns whose strings point into the input
-    if (r->format == EXG_FMT_FASTA) return sel && !switches().fasta_whole_text ? kPayloadCompact : kPayloadNone;
-    if (!sel) return kPayloadNone;
-    if (!switches().no_payload_compact && sel != strs && !(sel & f.nested_mask())) return kPayloadCompact;
-    return switches().no_host_mirror ? kPayloadNone : kPayloadMirror;
-}
-
-static int open_source(exg_reader *r, std::shared_ptr<PinnedBlock> &blk, const std::string &path, uint64_t n) {
-    const int fd = r->fd_keep->fd;
-    const uint64_t reserve = source_reserve(r), target = r->device_batch_bytes;
-    auto out_blk = std::make_shared<PinnedBlock>();  // (n = 0: the decoded size is not known; p: the VCF header prefix)
-    r->gz_header_prefix = 0;
-    const size_t queued = getenv("EXG_SOURCE_QUEUE") ? (size_t)std::max(1, atoi(getenv("EXG_SOURCE_QUEUE"))) : r->mem_cap ? 1 : 2;
-    auto make = [&](uint64_t c_begin, uint64_t c_end, bool bgzf_only, const uint64_t *marks) {
-        std::unique_ptr<SegmentProducer> prod = r->bcf ? make_bcf_producer(r, make_gzip_producer(r, fd, c_begin, c_end, bcf_input_target(target), path, true, bcf_input_reserve(target), nullptr),
-                                                                           bcf_input_reserve(target), target, path, reserve)  // (BGZF -> BCF records -> VCF text)
-                                                : r->compression == kGzip  ? make_gzip_producer(r, fd, c_begin, c_end, target, path, bgzf_only, reserve, marks)
-                                                : r->compression == kBzip2 ? make_bzip2_producer(r, fd, n, target, path, reserve)
-                                                                           : make_zstd_producer(r, fd, n, c_begin, c_end, target, path, reserve, marks);
-        // (EXG_OPEN_CHUNKS: the caller said it will pull chunks — the segments travel to the host from the first one on)
-        const bool mirror0 = r->expect_chunks && !r->arrow_emit && payload_route(r) == kPayloadMirror;
-        return std::unique_ptr<DecodedSource>(new DecodedSource(r->device, r->stream, std::move(prod), reserve, queued, &r->meter, mirror0));
-    };
-    if (r->compression == kGzip && n == 0) return fail(r, EXG_E_PARSE, "empty gzip file '" + path + "'");
-    r->fa_shard = false;
-    r->fa_end = ~0ull;
-    if (r->shard_count > 1 && r->compression == kBzip2)
-        return fail(r, EXG_E_UNSUPPORTED, "shards of a bzip2 input are not supported (one file is one shard): '" + path + "'");
-    if (r->shard_count > 1) {
-        // VCF: every rank needs the header (schema, and where the data begins): read from the start of the file by a
-        // source of its own, kept on the host like in the unsharded case
-        uint64_t header_bytes = 0;
-        if (has_text_header(r)) {
-            std::unique_ptr<DecodedSource> head = make(0, n, r->compression == kGzip, nullptr);
-            int rc = source_header_prefix(r, head.get(), *out_blk);
-            if (rc) return rc;
-            header_bytes = leading_lines_end((const char *)out_blk->p, (size_t)r->gz_header_prefix, header_marker(r));
-        }
-        const bool fasta = r->format == EXG_FMT_FASTA;
-        uint64_t c_begin = 0, c_end = n, marks[2] = {~0ull, ~0ull};
-        bool wait_own = false;  // where the shard's own bytes begin is told by the decoder (mark 0)
-        if (r->compression == kGzip && !fasta) {
-            int rc = plan_bgzf_shard(r, path, n, &c_begin, &c_end, header_bytes);
-            if (rc) return rc;
-        } else if (r->compression == kGzip) {
-            // bgzip FASTA: a record belongs to the shard in whose members' bytes its '>' line begins.  The stream starts one
-            // member in front of the shard's own (is their first byte a line start?) and runs on behind them until the next
-            // record start is found
-            Peek peek(nullptr, fd, n);
-            exg_inflate_member probe;
-            if (!bgzf_member_at(peek, 0, &probe))
-                return fail(r, EXG_E_UNSUPPORTED, "shards of a gzip input need BGZF framing (every member carries its size): '" + path + "'");
-            const uint64_t lo = (uint64_t)((unsigned __int128)n * r->shard_index / r->shard_count);
-            const uint64_t hi = r->shard_index + 1 == r->shard_count ? n : (uint64_t)((unsigned __int128)n * (r->shard_index + 1) / r->shard_count);
-            const uint64_t own_lo = lo == 0 ? 0 : bgzf_find(nullptr, fd, n, lo);
-            const uint64_t own_hi = hi >= n ? n : std::max<uint64_t>(own_lo, bgzf_find(nullptr, fd, n, hi));
-            c_begin = own_lo;
-            for (uint64_t pos = own_lo == 0 ? 0 : bgzf_find(nullptr, fd, n, own_lo > (192u << 10) ? own_lo - (192u << 10) : 0); pos < own_lo;) {
-                exg_inflate_member m;
-                const uint64_t nx = bgzf_member_at(peek, pos, &m);
-                if (!nx) return fail(r, EXG_E_PARSE, "not a BGZF member at byte " + std::to_string(pos) + " of '" + path + "'");
-                c_begin = pos;  // (the last member in front of the shard's own)
-                pos = nx;
-            }
-            marks[0] = own_lo;
-            marks[1] = own_hi >= n ? ~0ull : own_hi;
-            wait_own = true;
-        } else {
-            uint64_t own_lo = 0, own_hi = n;
-            bool bytes_follow = false;
-            int rc = plan_zstd_shard(r, fd, n, path, fasta ? 1 : r->halo_want, header_bytes, &c_begin, &c_end, &own_lo, &own_hi, &bytes_follow);
-            if (rc) return rc;
-            marks[0] = own_lo;
-            r->own_c_begin = own_lo;
-            if (fasta) {
-                c_end = n;
-                marks[1] = own_hi >= n ? ~0ull : own_hi;
-            }
-            r->range_eof = !bytes_follow;
-            wait_own = true;
-        }
-        r->src = make(c_begin, c_end, true, marks);
-        if (wait_own) {
-            // The decoder tells where the shard's own bytes begin (mark 0) when it gets there; until then the halo's segments
-            // are taken one by one — never a blocking wait for the mark: the decoder cannot run further ahead than its queue —
-            // and only the newest `keep` bytes of them stay: a halo is made of whole frames / members, and with few large
-            // frames in front of the shard everything from the stream's first byte would otherwise be resident (and copied
-            // again for every segment more) before the shard's first row
-            uint64_t own = 0;
-            const uint64_t keep = std::max<uint64_t>(fasta ? 0 : r->halo_want, 256u << 10) + (64u << 10);
-            for (uint64_t pos = 0, end = 0; !r->src->peek_mark(0, &own);) {
-                if (end - pos > keep) pos = (end - keep) & ~15ull;  // (what lies in front of it is dropped by the acquire)
-                const uint8_t *d_at = nullptr;
-                uint64_t avail = 0;
-                bool eof = false;
-                std::string msg;
-                int rc = r->src->acquire(pos, end - pos + 1, &d_at, &avail, &eof, &msg);  // one segment more
-                if (rc) return fail(r, rc, msg);
-                if (r->src->peek_mark(0, &own)) break;
-                if (eof) {
-                    own = ~0ull >> 1;  // (behind everything: the stream holds nothing of this shard's)
-                    break;
-                }
-                end = pos + avail;
-            }
-            r->range_preset = true;
-            r->preset_pos = own;
-            r->data0_is_line_start = c_begin == 0;
-        }
-        if (fasta) {
-            r->fa_shard = true;
-            r->range_eof = true;  // (a shard of a FASTA is a FASTA file of its own)
-        }
-    } else {
-        r->src = make(0, n, r->format == EXG_FMT_BAM, nullptr);  // (a BAM file is BGZF, SAM spec 4.1: any other gzip member in it is refused, like in a BCF)
-        if (has_text_header(r)) {
-            int rc = source_header_prefix(r, r->src.get(), *out_blk);
-            if (rc) return rc;
-        }
-    }
-    blk = out_blk;
-    return EXG_OK;
-}
-
-// Newlines in the decoded bytes of the members / frames in front of a shard's own (file bytes [0, own_c_begin)), by a decoder
-// of their own: a segment is counted on the device and dropped, nothing but it is resident (the phase of a shard of a
-// compressed FASTQ when the bytes around the cut do not tell it: a memchr over the page cache in the text case).
-static int count_newlines_in_front(exg_reader *r, uint64_t *out) {
-    *out = 0;
-    if (!r->own_c_begin) return EXG_OK;
-    const std::string &path = r->files[r->file_idx - 1];
-    const int fd = r->fd_keep->fd;
-    struct stat st;
-    if (fstat(fd, &st)) return fail(r, EXG_E_IO, "cannot stat '" + path + "'");
-    const uint64_t reserve = source_reserve(r), target = r->device_batch_bytes;
-    if (r->compression == kBzip2) return fail(r, EXG_E_UNSUPPORTED, "shards of a bzip2 input are not supported: '" + path + "'");
-    std::unique_ptr<SegmentProducer> prod = r->compression == kGzip
-                                                ? make_gzip_producer(r, fd, 0, r->own_c_begin, target, path, true, reserve, nullptr)
-                                                : make_zstd_producer(r, fd, (uint64_t)st.st_size, 0, r->own_c_begin, target, path, reserve, nullptr);
-    DecodedSource head(r->device, r->stream, std::move(prod), reserve, 1, &r->meter);
-    if (!r->d_phase && !(r->d_phase = exg_rd::dev_pool()->take(r->device, 4096))) return fail(r, EXG_E_HIP, "out of device memory");
-    for (uint64_t pos = 0;;) {
-        const uint8_t *d_at = nullptr;
-        uint64_t avail = 0;
-        bool eof = false;
-        std::string msg;
-        int rc = head.acquire(pos, 1, &d_at, &avail, &eof, &msg);
-        if (rc) return fail(r, rc, msg);
-        if (avail) {
-            unsigned long long nl = 0;
-            const uint64_t skew = pos & 15;  // (an address is congruent to its stream offset mod 16)
-            rc = exg_count_newlines(d_at - skew, skew, skew + avail, (uint64_t *)r->d_phase, r->stream);
-            if (rc) return fail(r, rc, exg_last_error_message());
-            RD_HIP(r, hipMemcpyAsync(&nl, r->d_phase, 8, hipMemcpyDeviceToHost, r->stream));
-            RD_HIP(r, hipStreamSynchronize(r->stream));
-            *out += nl;
-            pos += avail;
-        }
-        if (eof) break;
-        if (!avail) return fail(r, EXG_E_HIP, "internal: a decoded source returned nothing before its end");
-    }
-    std::string e;
-    const int frc = head.finish(&e);
-    return frc ? fail(r, frc, e) : EXG_OK;
-}
-
-// Where this reader's bytes of the file just opened begin and end (file_pos, range_hi), and whether its first batch takes a halo
-static int place_shard(exg_reader *r, const PinnedBlock &blk) {
-    if (r->fa_shard) {
-        // a shard of a compressed FASTA: the run of whole records from the first '>' line that begins in its own bytes to the
-        // first that begins behind them (found while scanning: next_batch), like a text shard's run
-        r->shard_first = false;
-        if (r->preset_pos == 0 && r->data0_is_line_start) {
-            r->file_pos = 0;
-        } else {
-            uint64_t at = ~0ull;
-            int rc = source_find_record(r, r->preset_pos, &at);
-            if (rc) return rc;
-            if (at == ~0ull) r->file_done = true;  // no record begins in this shard's bytes (or behind them)
-            else r->file_pos = at;
-        }
-    } else if (r->range_preset) {  // BGZF / zstd shard: the members / frames were chosen in open_source
-        // its stream begins with the file (header and all) or somewhere behind the header
-        r->data_base = r->data0_is_line_start ? r->data_base : 0;
-        r->file_pos = std::max<uint64_t>(r->preset_pos, r->data_base);
-        r->shard_first = r->file_pos > r->data_base;
-    } else if (r->shard_count > 1 && r->format == EXG_FMT_FASTA) {
-        // FASTA: a record belongs to the shard in whose bytes its '>' line BEGINS, and a shard is the run of whole
-        // records from its first such line to the next shard's — scanned like a file of its own (a record is never
-        // cut, however long its sequence: the run simply reaches as far as it has to)
-        const char *d = (const char *)blk.p;
-        const uint64_t N = blk.n;
-        auto first_record_at_or_after = [&](uint64_t pos) -> uint64_t {
-            if (pos == 0) return 0;
-            for (uint64_t q = pos - 1; q + 1 < N;) {  // a line start is the byte behind a newline
-                const void *hit = memchr(d + q, '\n', (size_t)(N - q));
-                if (!hit) return N;
-                q = (uint64_t)((const char *)hit - d) + 1;
-                if (q < N && d[q] == '>') return q;
-            }
-            return N;
-        };
-        const uint64_t lo = (uint64_t)((unsigned __int128)N * r->shard_index / r->shard_count);
-        const uint64_t hi = r->shard_index + 1 == r->shard_count ? N : (uint64_t)((unsigned __int128)N * (r->shard_index + 1) / r->shard_count);
-        r->file_pos = first_record_at_or_after(lo);
-        r->range_hi = hi == N ? N : first_record_at_or_after(hi);
-        if (r->range_hi < r->file_pos) r->range_hi = r->file_pos;
-        r->range_eof = true;  // the run is a FASTA file of its own
-    } else if (r->shard_count > 1) {
-        const uint64_t base = r->file_pos, span = blk.n - base;
-        const uint64_t lo = base + (uint64_t)((unsigned __int128)span * r->shard_index / r->shard_count);
-        const uint64_t hi = r->shard_index + 1 == r->shard_count
-                                ? blk.n
-                                : base + (uint64_t)((unsigned __int128)span * (r->shard_index + 1) / r->shard_count);
-        r->file_pos = lo;
-        r->range_hi = hi;
-        r->shard_first = lo > base;
-        r->range_eof = hi == blk.n;
-    }
-    return EXG_OK;
-}
-
-int open_next_file(exg_reader *r) {
-    if (int jrc = r->finish_source()) return jrc;
-    r->src.reset();  // (its thread reads the previous file's descriptor)
-    const std::string &p = r->files[r->file_idx++];
-    int fd = open(p.c_str(), O_RDONLY);
-    if (fd < 0) return fail(r, EXG_E_IO, "cannot open '" + p + "': " + strerror(errno));
-    struct stat st;
-    if (fstat(fd, &st) != 0) {
-        const std::string why = strerror(errno);
-        close(fd);
-        return fail(r, EXG_E_IO, "cannot stat '" + p + "': " + why);
-    }
-    if (!S_ISREG(st.st_mode)) {
-        close(fd);
-        return fail(r, EXG_E_IO, "'" + p + "' is not a regular file");
-    }
-    auto blk = std::make_shared<PinnedBlock>();
-    blk->n = (size_t)st.st_size;
-    double t0 = now_s();
-    if (r->compression != kNone) {
-        // decoded by a producer thread that reads the file with pread: nothing is mapped
-    } else if (blk->n) {
-        // The file is mapped, not copied: DataChunk strings point straight into the page cache mapping
-        // (kept alive by the chunks); bytes travel to the device through a pinned bounce buffer.
-        void *m = mmap(nullptr, blk->n, PROT_READ, MAP_PRIVATE, fd, 0);
-        if (m == MAP_FAILED) {
-            close(fd);
-            return fail(r, EXG_E_IO, "cannot map '" + p + "': " + strerror(errno));
-        }
-        blk->p = m;
-        blk->mapped = blk->n;
-        // (another process may truncate the file while its rows are out: zeros + EXG_E_IO at the next call, not a SIGBUS that
-        // ends the DuckDB process — exg_map_guard.hpp)
-        blk->guard = MapGuard::add(m, blk->n);
-        if (blk->guard < 0) {  // (the table holds 4096 mappings: chunks of thousands of files are still out)
-            blk.reset();       // (unmaps)
-            close(fd);
-            return fail(r, EXG_E_NOMEM, "too many text files mapped at once (4096): release chunks or close readers before opening '" + p + "'");
-        }
-    } else {
-        hipError_t he = hipHostMalloc(&blk->p, 64, hipHostMallocDefault);
-        if (he != hipSuccess) {
-            close(fd);
-            return fail(r, EXG_E_HIP, std::string("hipHostMalloc failed: ") + hipGetErrorString(he));
-        }
-        memset(blk->p, 0, 64);
-    }
-    r->fd_keep.reset(new exg_reader::FdCloser{fd});
-    TRACE("mmap(file)", t0);
-    r->range_preset = false;
-    r->range_eof = true;
-    r->data0_is_line_start = true;
-    r->own_c_begin = 0;
-    r->exact_nl_known = false;
-    (void)r->join_prefetch();
-    r->drop_prefetch2();
-    if (r->pf.valid && r->up_stream) (void)hipStreamSynchronize(r->up_stream);  // a prefetch of the previous file
-    r->pf.valid = false;
-    if (r->compression != kNone) {
-        int rc = open_source(r, blk, p, (uint64_t)st.st_size);  // replaces blk (decoded size unknown; VCF: the header prefix on the host)
-        if (rc) return rc;
-    }
-    r->file = blk;
-    r->file_pos = 0;
-    r->file_done = false;
-    if (r->format == EXG_FMT_VCF) {
-        // header = the leading '#' lines (noodles-vcf read_header); it must hold the #CHROM line
-        const char *d = (const char *)blk->p;
-        const size_t hn = r->compression != kNone ? (size_t)r->gz_header_prefix : blk->n;  // gzip / zstd: only the header prefix is on the host
-        size_t pos = 0;
-        bool chrom = false;
-        while (pos < hn && d[pos] == '#') {
-            if (hn - pos >= 6 && memcmp(d + pos, "#CHROM", 6) == 0) chrom = true;
-            const void *nl = memchr(d + pos, '\n', hn - pos);
-            pos = nl ? (size_t)((const char *)nl - d) + 1 : hn;
-        }
-        if (!chrom) return fail(r, EXG_E_PARSE, std::string(exg_parse_error_string(EXG_PE_VCF_NO_HEADER)) + " in '" + p + "'");
-        r->vcf_header_bytes = pos;
-        r->file_pos = pos;
-    } else if (r->format == EXG_FMT_SAM) {
-        // header = the leading '@' lines, skipped unread (a header-only or empty file has no rows); a decoded stream has the
-        // prefix that holds them on the host, however long they are (source_header_prefix)
-        r->file_pos = sam_header_end((const char *)blk->p, r->compression != kNone ? (size_t)r->gz_header_prefix : blk->n);
-    }
-    // byte-range shard of this file: [lo, hi) of the bytes behind the header; records / lines belong to the shard they END in
-    r->range_hi = r->src ? ~0ull : blk->n;  // (a decoded stream ends where its source says so)
-    r->shard_first = false;
-    r->data_base = r->file_pos;  // 0, or the end of the VCF header
-    if (r->format == EXG_FMT_BAM) return bam_open_file(r);  // (the header, from the front of the decoded stream; one shard)
-    // Which scan first: from the first MiB behind the header, which is mapped anyway (a decoded stream has no bytes on the host: its
-    // first batches' results decide, as before).  The batches' result flags correct the choice either way.
-    if (!r->src && blk->p && blk->n > r->file_pos && !getenv("EXG_NO_ALGO_HINT"))
-        r->fused_algo = (uint32_t)exg_scan_algo_hint(r->format, (const uint8_t *)blk->p + r->file_pos, blk->n - r->file_pos);
-    r->ramp_bytes = (!r->src && r->format != EXG_FMT_FASTA && !switches().no_ramp && r->device_batch_bytes > kRampFirstBytes) ? kRampFirstBytes : 0;
-    return r->fa_shard || r->range_preset || r->shard_count > 1 ? place_shard(r, *blk) : EXG_OK;
-}
-
-int next_batch(exg_reader *r, bool count_only, uint64_t *n_records_out);
 
 int advance_batch(exg_reader *r, bool *end) {
     *end = false;
@@ -546,6 +51,21 @@ int advance_batch(exg_reader *r, bool *end) {
         int rc = next_batch(r, false, &k);
         if (rc) return rc;
     }
+}
+
+int alloc_columns(exg_reader *r, uint64_t produce) {
+    // per column: what the scan writes, the validity words of a nullable one, the vector of a number parsed beside its text
+    const FormatDesc &f = format_desc(r->format);
+    int rc;
+    for (int c = 0; c < f.n_columns; c++) {
+        const ColumnDesc &d = f.col[c];
+        if (!((produce >> c) & 1ull)) continue;
+        if ((rc = r->dev_alloc(&r->d_cols[c], r->cap_records * f.scan_elem(c)))) return rc;
+        if (d.validity && (rc = r->dev_alloc(&r->d_col_valid[c], (r->cap_records + 63) / 64 * 8))) return rc;
+        if (void **parsed = r->parsed_vector(d.parsed))
+            if ((rc = r->dev_alloc(parsed, r->cap_records * d.elem))) return rc;
+    }
+    return EXG_OK;
 }
 
 int ensure_device(exg_reader *r, uint64_t need_bytes) {
@@ -589,25 +109,14 @@ int ensure_device(exg_reader *r, uint64_t need_bytes) {
         for (int k = 0; k < 2; k++) RD_HIP(r, hipEventCreateWithFlags(&r->up_done_of[k], hipEventDisableTiming));
     }
     if ((arc = r->dev_alloc(&r->d_ws, r->ws_bytes))) return arc;
-    // per column: what the scan writes, the validity words of a nullable one, the vector of a number parsed beside its text
+    if ((arc = alloc_columns(r, ~0ull))) return arc;
     const uint64_t validity_bytes = (r->cap_records + 63) / 64 * 8;
-    for (int c = 0; c < f.n_columns; c++) {
-        const ColumnDesc &d = f.col[c];
-        if ((arc = r->dev_alloc(&r->d_cols[c], r->cap_records * f.scan_elem(c)))) return arc;
-        if (d.validity && (arc = r->dev_alloc(&r->d_col_valid[c], validity_bytes))) return arc;
-        if (void **parsed = r->parsed_vector(d.parsed))
-            if ((arc = r->dev_alloc(parsed, r->cap_records * d.elem))) return arc;
-    }
     for (uint32_t k = 0; k < f.spare_validity; k++)
         if ((arc = r->dev_alloc(&r->d_valid_spare[k], validity_bytes))) return arc;
     if (r->format == EXG_FMT_FASTA && (arc = r->dev_alloc(&r->d_payload, cap + 64))) return arc;
     // GTF: which rows are feature lines, and — a batch with `#` lines is gathered like a filtered one — the row map's buffers
     if (r->format == EXG_FMT_GTF && (arc = r->dev_alloc(&r->d_keep, validity_bytes))) return arc;
-    if (r->has_filter || r->format == EXG_FMT_GTF) {
-        if ((arc = r->dev_alloc(&r->d_row_map, r->cap_records * 4 + 64))) return arc;
-        if ((arc = r->dev_alloc(&r->d_gather, std::max<uint64_t>(r->cap_records * 16, sizeof(exg::arrow::FilterCols))))) return arc;
-        if ((arc = r->dev_alloc(&r->d_filter_tmp, (r->cap_records + 1 + exg::arrow::scan_tmp_entries(r->cap_records)) * 8))) return arc;
-    }
+    if ((r->has_filter || r->format == EXG_FMT_GTF) && (arc = alloc_row_selection(r))) return arc;
     if (!r->d_res && !(r->d_res = exg_rd::dev_pool()->take(r->device, 4096))) return fail(r, EXG_E_HIP, "out of device memory");
     return EXG_OK;
 }
@@ -619,34 +128,19 @@ int truncated_while_read(exg_reader *r) {
 
 namespace {
 
-// What one attempt at a batch scans.  Re-made at the top of every attempt: a retry cannot read a field of the attempt before.
-struct BatchIn {
-    uint64_t n = 0;           // bytes of the attempt: behind file_pos until the input is bound, then all the scan is given (`lead` included)
+// What one attempt at a batch scans (BatchOut: what the rows' way out reads of it).  Re-made at the top of every attempt: a retry
+// cannot read a field of the attempt before.
+struct BatchIn : BatchOut {
     uint64_t lead = 0;        // bytes of d_input in front of file_pos (the halo, and what a 16-byte boundary brings along)
     uint64_t shard_halo = 0;  // first batch of a shard that begins inside the file: bytes in front of it that travel along
     bool range_end = false;   // the batch reaches the end of this reader's bytes ...
     bool eof = false;         // ... which is the end of the file unless a later shard follows
     const void *d_input = nullptr;
     const uint8_t *h = nullptr;  // host address of the byte at d_input[0] (the strings' payload_base)
-    uint64_t batch_end = 0;      // file offset one past the bytes of this batch
     // a decoded stream: the bytes from file_pos on (and the halo in front) made contiguous in HBM — everything up to the end of
     // the segment that holds them is this batch
     const uint8_t *src_at = nullptr;  // device address of stream byte src_pos
     uint64_t src_pos = 0;
-    std::shared_ptr<PinnedBlock> gz_payload;  // gzip: this batch's inflated bytes on the host (string_t payload)
-    std::shared_ptr<HostMirror> gz_mirror;    // ... when the producer sent them ahead (exg_rd_source.hpp); then only
-    uint64_t gz_front = 0;                    // ... the first gz_front bytes of the batch (the carried tail) are copied here
-    bool compact = false;                     // ... or: only the selected columns' out-of-line strings travel (a side buffer)
-    std::shared_ptr<Batch> b;  // FASTA: made in front of the scan (its pinned block takes the joined sequences); else by columns_to_host
-};
-
-// compact: the selected string columns' out-of-line bytes, closed up per column into ONE side buffer
-struct SideBuf {
-    struct Col {
-        uint64_t *d_goff = nullptr;
-        uint64_t total = 0, off = 0;
-    } col[12];
-    uint8_t *h = nullptr;
 };
 
 // The state of one next_batch call: its stages in the order the driver (next_batch, below) runs them.  A stage returns an error
@@ -712,12 +206,11 @@ struct BatchRun {
             if (own_end <= r->file_pos) {
                 r->fa_end = r->file_pos;
             } else if (own_end < in.src_pos + avail) {
-                unsigned long long pos = ~0ull;
-                if (!r->d_phase && !(r->d_phase = dev_pool()->take(r->device, 4096))) return fail(r, EXG_E_HIP, "out of device memory");
-                int arc = exg_fasta_find_record(in.src_at, own_end - in.src_pos, avail, 0, (uint64_t *)r->d_phase, r->stream);
-                if (arc) return fail(r, arc, exg_last_error_message());
-                RD_HIP(r, hipMemcpyAsync(&pos, r->d_phase, 8, hipMemcpyDeviceToHost, r->stream));
-                RD_HIP(r, hipStreamSynchronize(r->stream));
+                uint64_t pos = ~0ull;
+                if (int arc = fetch_word(r, &pos, [&](void *d_word) {
+                        return exg_fasta_find_record(in.src_at, own_end - in.src_pos, avail, 0, (uint64_t *)d_word, r->stream);
+                    }))
+                    return arc;
                 if (pos != ~0ull) r->fa_end = in.src_pos + pos;
             }
         }
@@ -882,12 +375,9 @@ struct BatchRun {
     int fastq_first_line_phase() {
         first_line_index = 0;
         if (!in.lead || !r->shard_first || r->format != EXG_FMT_FASTQ) return EXG_OK;
-        if (!r->d_phase && !(r->d_phase = exg_rd::dev_pool()->take(r->device, 4096))) return fail(r, EXG_E_HIP, "out of device memory");
         uint32_t guess = 0xFFFFFFFFu;
-        int rc = exg_fastq_guess_phase(in.d_input, in.n, in.lead, (uint32_t *)r->d_phase, r->stream);
-        if (rc) return fail(r, rc, exg_last_error_message());
-        RD_HIP(r, hipMemcpyAsync(&guess, r->d_phase, 4, hipMemcpyDeviceToHost, r->stream));
-        RD_HIP(r, hipStreamSynchronize(r->stream));
+        int rc = fetch_word(r, &guess, [&](void *d_word) { return exg_fastq_guess_phase(in.d_input, in.n, in.lead, (uint32_t *)d_word, r->stream); });
+        if (rc) return rc;
         if (guess <= 3) {
             uint8_t prev = 0;
             if (r->src) {
@@ -901,12 +391,9 @@ struct BatchRun {
             // a shard of a compressed input: exact when the halo begins with the file (the newlines in front are then all
             // in HBM); else (few lines in view — records far longer than the halo — or several phases fit) the newlines in
             // front of the shard's own bytes are counted by a decoder of their own, segment by segment
-            unsigned long long nl = 0;
+            uint64_t nl = 0;
             if (r->data0_is_line_start && in.lead == r->file_pos) {
-                rc = exg_count_newlines(in.d_input, 0, in.lead, (uint64_t *)r->d_phase, r->stream);
-                if (rc) return fail(r, rc, exg_last_error_message());
-                RD_HIP(r, hipMemcpyAsync(&nl, r->d_phase, 8, hipMemcpyDeviceToHost, r->stream));
-                RD_HIP(r, hipStreamSynchronize(r->stream));
+                if ((rc = fetch_word(r, &nl, [&](void *d_word) { return exg_count_newlines(in.d_input, 0, in.lead, (uint64_t *)d_word, r->stream); }))) return rc;
             } else {
                 if (!r->exact_nl_known) {
                     if ((rc = count_newlines_in_front(r, &r->exact_nl))) return rc;
@@ -991,47 +478,21 @@ struct BatchRun {
         }
         return scan_rc(exg_vcf_scan(&a));
     }
-    int launch_bed(uint32_t algo) {
-        exg_bed_scan_args a;
+    // BED, SAM, GTF: a line is a row of n_columns fields.  The projection reaches the kernel (a NULL column is validated, not
+    // written): `produce` has a bit for every column that is selected or that the predicate reads
+    template <class Args>
+    int launch_line_rows(uint32_t algo, int n_columns, uint64_t produce, int (*entry)(const Args *)) {
+        Args a;
         fill_common(&a);
         a.lead = in.lead;
         a.algo = algo;
-        // the projection reaches the kernel (a NULL column is validated, not written): a column is produced when it is selected or
-        // the predicate reads it
-        for (int c = 0; c < EXG_BED_COLUMNS; c++) {
-            if (!r->want(c) && !((r->filter_cols >> c) & 1ull)) continue;
+        for (int c = 0; c < n_columns; c++) {
+            if (!((produce >> c) & 1ull)) continue;
             a.d_columns[c] = r->d_cols[c];
             a.d_validity[c] = (uint64_t *)r->d_col_valid[c];
         }
-        return scan_rc(exg_bed_scan(&a));
-    }
-    int launch_sam(uint32_t algo) {
-        exg_sam_scan_args a;
-        fill_common(&a);
-        a.lead = in.lead;
-        a.algo = algo;
-        // (the projection reaches the kernel, as for BED)
-        for (int c = 0; c < EXG_SAM_COLUMNS; c++) {
-            if (!r->want(c) && !((r->filter_cols >> c) & 1ull)) continue;
-            a.d_columns[c] = r->d_cols[c];
-            a.d_validity[c] = (uint64_t *)r->d_col_valid[c];
-        }
-        return scan_rc(exg_sam_scan(&a));
-    }
-    int launch_gtf(uint32_t algo) {
-        exg_gtf_scan_args a;
-        fill_common(&a);
-        a.lead = in.lead;
-        a.algo = algo;
-        // (the projection reaches the kernel, as for BED; COUNT(*) without a predicate: no column at all.  Column 8 is the raw
-        // ninth field, what `attributes` is built from)
-        for (int c = 0; c < EXG_GTF_COLUMNS; c++) {
-            if (!(!count_only && r->want(c)) && !((r->filter_cols >> c) & 1ull)) continue;
-            a.d_columns[c] = r->d_cols[c];
-            a.d_validity[c] = (uint64_t *)r->d_col_valid[c];
-        }
-        a.d_keep = (uint64_t *)r->d_keep;
-        return scan_rc(exg_gtf_scan(&a));
+        if constexpr (std::is_same<Args, exg_gtf_scan_args>::value) a.d_keep = (uint64_t *)r->d_keep;
+        return scan_rc(entry(&a));
     }
     int launch_fasta() {
         in.b = std::make_shared<Batch>();
@@ -1051,12 +512,14 @@ struct BatchRun {
     }
     int scan_rc(int rc) { return rc ? fail(r, rc, exg_last_error_message()) : EXG_OK; }
     int launch_scan(uint32_t algo) {
+        const uint64_t produce = r->want_cols | r->filter_cols;
         switch (r->format) {
             case EXG_FMT_FASTQ: return launch_fastq(algo);
             case EXG_FMT_VCF: return launch_vcf(algo);
-            case EXG_FMT_BED: return launch_bed(algo);
-            case EXG_FMT_SAM: return launch_sam(algo);
-            case EXG_FMT_GTF: return launch_gtf(algo);
+            case EXG_FMT_BED: return launch_line_rows<exg_bed_scan_args>(algo, EXG_BED_COLUMNS, produce, exg_bed_scan);
+            case EXG_FMT_SAM: return launch_line_rows<exg_sam_scan_args>(algo, EXG_SAM_COLUMNS, produce, exg_sam_scan);
+            // (COUNT(*) without a predicate: no column at all.  Column 8 is the raw ninth field, what `attributes` is built from)
+            case EXG_FMT_GTF: return launch_line_rows<exg_gtf_scan_args>(algo, EXG_GTF_COLUMNS, count_only ? r->filter_cols : produce, exg_gtf_scan);
             default: return launch_fasta();
         }
     }
@@ -1114,14 +577,9 @@ struct BatchRun {
     // that are feature lines (d_keep), ANDed with the predicate when there is one
     bool rows_skipped() const { return r->format == EXG_FMT_GTF && (res.flags & EXG_RF_ROWS_SKIPPED); }
     int select_rows() {
-        namespace ea = exg::arrow;
-        ea::FilterCols fc;
+        exg::arrow::FilterCols fc;
         memset(&fc, 0, sizeof fc);
-        const FormatDesc &f = format_desc(r->format);
-        for (int c = 0; c < f.n_columns && r->has_filter; c++) {
-            fc.kind[c] = filter_col_kind(f.col[c]);
-            fc.data[c] = r->column_data(c).data;
-            fc.validity[c] = (const uint64_t *)r->d_col_valid[c];
+        for (int c = 0; c < format_desc(r->format).n_columns; c++) {  // a text format's strings point into the input
             fc.d_base[c] = (const uint8_t *)in.d_input;
             fc.payload_base[c] = (uint64_t)(uintptr_t)in.h;
         }
@@ -1129,12 +587,7 @@ struct BatchRun {
             fc.d_base[2] = (const uint8_t *)r->d_payload;
             fc.payload_base[2] = (uint64_t)(uintptr_t)(in.b ? in.b->payload : nullptr);
         }
-        uint64_t *d_goff = (uint64_t *)r->d_filter_tmp, *d_tmp = d_goff + r->cap_records + 1;
-        ea::FilterCols *d_fc = (ea::FilterCols *)r->d_gather;  // the scratch column is free until the gathers
-        RD_HIP(r, ea::select_rows(fc, r->has_filter ? (const ea::FilterProgram *)r->d_filter_prog : nullptr, (const uint8_t *)r->d_filter_consts, k, d_goff,
-                                  d_tmp, (uint32_t *)r->d_row_map, d_fc, r->stream, &k, rows_skipped() ? (const uint64_t *)r->d_keep : nullptr));
-        row_map = (const uint32_t *)r->d_row_map;
-        return EXG_OK;
+        return exg_rd::select_rows(r, &fc, rows_skipped() ? (const uint64_t *)r->d_keep : nullptr, &k, &row_map);
     }
 
     // ---- 8: the rows leave.  new_reader: the columns stay in HBM and become Arrow buffers there (exg_arrow_stream.cpp)
@@ -1146,239 +599,8 @@ struct BatchRun {
         TRACE("arrow emit", t_emit);
         return EXG_OK;
     }
-    // ... or the batch's host vectors: columns -> host
-    int columns_to_host() {
-        TraceRange d2h_range("exg: columns -> host");
-        if (!in.b) in.b = std::make_shared<Batch>();
-        Batch *b = in.b.get();
-        b->host.reserve(r->host_hint);
-        b->file = in.gz_payload ? in.gz_payload : r->file;
-        // the projection (exg_open_args.columns): every column was parsed and validated above, only the wanted ones travel.
-        // A decoded input's bytes are what its strings point into: they travel when any string column does
-        const FormatDesc &f = format_desc(r->format);
-        const bool any_strings = (r->want_cols & (f.string_mask() | f.nested_mask())) != 0;  // (a nested column's elements are strings too)
-        if (in.gz_payload && any_strings && !in.gz_mirror) RD_HIP(r, hipMemcpyAsync(in.gz_payload->p, in.d_input, in.n, hipMemcpyDeviceToHost, r->stream));
-        if (in.gz_mirror && in.gz_front) RD_HIP(r, hipMemcpyAsync(const_cast<uint8_t *>(in.h), in.d_input, in.gz_front, hipMemcpyDeviceToHost, r->stream));
-        b->n_rows = k;
-        SideBuf side;
-        SideScratch side_scratch{r->device, r->stream, {}};
-        int rc;
-        if (in.compact && (rc = side_buffer(&side, &side_scratch))) return rc;
-        b->n_cols = f.n_columns;  // schema order (exg_schema_of): VCF exposes parsed POS / QUAL in place of their raw text
-        ColDrain col_drain;
-        hipStream_t cs = r->stream;
-        if ((rc = columns_stream(&cs, &col_drain))) return rc;
-        if ((rc = flat_columns(side, cs))) return rc;
-        // the validity words of every wanted nullable flat column (a nested column's validity is the emitter's)
-        for (int c = 0; c < f.n_columns; c++)
-            if (f.col[c].validity && !f.col[c].nested && r->want(c) &&
-                (rc = column_to_host(r, b, c, nullptr, 0, r->d_col_valid[c], k, row_map, r->d_gather, cs)))
-                return rc;
-        if (r->format == EXG_FMT_VCF && (rc = vcf_nested_columns(cs, &col_drain))) return rc;
-        if (r->format == EXG_FMT_GTF && r->want(8) && (rc = gtf_attributes(&side_scratch))) return rc;
-        if (r->format == EXG_FMT_FASTA && res.payload_bytes && r->want(2) && (rc = fasta_sequences(cs))) return rc;
-        const double t_cols = now_s();
-        RD_HIP(r, hipStreamSynchronize(r->stream));
-        if (r->col_stream && !b->landed) RD_HIP(r, hipStreamSynchronize(r->col_stream));
-        col_drain.cs = nullptr;
-        TRACE("wait(columns -> host)", t_cols);
-        const double t_mir = now_s();
-        if (in.gz_mirror) RD_HIP(r, hipEventSynchronize(in.gz_mirror->ev));  // the segment's own bytes have arrived
-        if (in.gz_mirror) TRACE("wait(host mirror of the segment)", t_mir);
-        trace_at("C batch-done", r->n_batches);
-        r->host_hint = b->host.total + b->host.total / 8 + (1u << 20);
-        b->seq = r->batch_seq++;
-        r->batch = in.b;
-        return EXG_OK;
-    }
-    // compact: the selected string columns' out-of-line bytes, closed up per column into ONE side buffer
-    int side_buffer(SideBuf *side, SideScratch *scratch) {
-        namespace ea = exg::arrow;
-        const FormatDesc &f = format_desc(r->format);
-        const int ns = f.n_columns;
-        const uint64_t compact = f.string_mask() & f.payload_mask();  // the flat strings that point into the input
-        uint64_t *d_tmp = (uint64_t *)scratch->take((ea::scan_tmp_entries(k) + 2) * 8);
-        if (!d_tmp) return fail(r, EXG_E_HIP, "out of device memory");
-        for (int c = 0; c < ns; c++) {
-            if (!r->want(c) || !((compact >> c) & 1ull)) continue;
-            if (!(side->col[c].d_goff = (uint64_t *)scratch->take((k + 2) * 8))) return fail(r, EXG_E_HIP, "out of device memory");
-            const ea::StrCol sc{(const exg_string_t *)r->d_cols[c], (const uint8_t *)in.d_input, (uint64_t)(uintptr_t)in.h};
-            ea::payload_goff_from_col(sc, row_map, k, side->col[c].d_goff, d_tmp, r->stream);
-            RD_HIP(r, hipMemcpyAsync(&side->col[c].total, side->col[c].d_goff + k, 8, hipMemcpyDeviceToHost, r->stream));
-        }
-        RD_HIP(r, hipStreamSynchronize(r->stream));
-        uint64_t side_total = 0;
-        for (int c = 0; c < ns; c++) side->col[c].off = side_total, side_total += (side->col[c].total + 15) & ~15ull;
-        if (!side_total) return EXG_OK;
-        if (!(side->h = (uint8_t *)in.b->host.alloc(side_total + 64))) return fail(r, EXG_E_HIP, "out of pinned host memory");
-        const uint32_t big_cap = (uint32_t)(side_total / 8192 + 1);
-        uint32_t *d_big = (uint32_t *)scratch->take(4 * ((size_t)big_cap + 1));
-        uint8_t *d_side = (uint8_t *)scratch->take(side_total + 64);
-        if (!d_side || !d_big) return fail(r, EXG_E_HIP, "out of device memory");
-        for (int c = 0; c < ns; c++) {
-            if (!side->col[c].d_goff || !side->col[c].total) continue;
-            const ea::StrCol sc{(const exg_string_t *)r->d_cols[c], (const uint8_t *)in.d_input, (uint64_t)(uintptr_t)in.h};
-            ea::payload_copy_from_col(sc, row_map, k, side->col[c].d_goff, d_side + side->col[c].off, d_big, big_cap, r->stream);
-        }
-        RD_HIP(r, hipMemcpyAsync(side->h, d_side, side_total, hipMemcpyDeviceToHost, r->stream));
-        return EXG_OK;
-    }
-    // the stream the vectors travel on (*cs: the scan's when this returns without a word), and whether the batch is handed on while
-    // they still do (r->lazy_landing)
-    int columns_stream(hipStream_t *cs, ColDrain *col_drain) {
-        // read_vcf: behind the flat columns come the nested ones' kernels (nested_emit: dozens of small launches that build — or,
-        // for columns the projection leaves out, only validate — id / alt / filter / info / formats).  In one stream the
-        // 200 MB of flat vectors (3.7 ms of the link) stood in front of them; on a stream of their own the copies run beside
-        // them (chrom, pos, ref of a 2 GB file: 70.6 -> 49.4 ms = 42 GB/s, COUNT(*) 47 ms: A/B in one box, EXG_VCF_ONE_STREAM)
-        // (FASTA, round 6: its joined sequences are as many bytes as the batch itself — on the scan's stream they shared a copy
-        // engine with the next batch's upload, which landed 5 ms behind them: 9.7 ms per 256 MiB batch where the two directions
-        // should overlap)
-        // (EXG_VCF_ONE_STREAM is read per batch: the tests switch it inside one process)
-        if ((r->format == EXG_FMT_VCF || r->format == EXG_FMT_FASTA || (!r->src && !switches().fastq_one_stream)) && !in.compact &&
-            !getenv("EXG_VCF_ONE_STREAM")) {
-            if (!r->col_stream) {
-                RD_HIP(r, stream_pool()->take_d2h(r->device, &r->col_stream, /*calibrate=*/r->file && r->file->n >= (512ull << 20) && !r->mem_cap));
-                RD_HIP(r, hipEventCreateWithFlags(&r->col_ev, hipEventDisableTiming));
-                RD_HIP(r, hipEventCreateWithFlags(&r->flat_ev, hipEventDisableTiming));
-            }
-            RD_HIP(r, hipEventRecord(r->col_ev, r->stream));  // (the scan, the predicate's row map)
-            RD_HIP(r, hipStreamWaitEvent(r->col_stream, r->col_ev, 0));
-            *cs = col_drain->cs = r->col_stream;
-        }
-        // read_vcf hands its batch on while the vectors are still travelling (Batch::landed): the batch behind it — upload wait,
-        // scan, the nested columns' kernels — is made beside them, and the link back to the host does not idle between batches
-        r->lazy_landing = r->format == EXG_FMT_VCF && *cs == r->col_stream && *cs != r->stream && !switches().vcf_eager_landing;
-        return EXG_OK;
-    }
-    // the flat columns the projection wants, each gathered through the row map and copied back
-    int flat_columns(const SideBuf &side, hipStream_t cs) {
-        Batch *b = in.b.get();
-        const FormatDesc &f = format_desc(r->format);
-        for (int c = 0; c < b->n_cols; c++) {
-            b->elem[c] = 0;
-            b->cols[c] = nullptr;
-            if (f.col[c].nested || !r->want(c)) continue;  // (VCF id, alt, filter, info, formats: built by nested_emit — vcf_nested_columns)
-            const void *src = r->column_data(c).data;
-            const uint32_t es = r->column_data(c).elem;
-            b->elem[c] = es;
-            int rc;
-            if (in.compact && es == 16 && side.col[c].d_goff) {
-                // (gathers through the row map itself; in place without one: the column is the scan's scratch from here on)
-                void *dst = row_map ? r->d_gather : r->d_cols[c];
-                exg::arrow::repoint_strings((const exg_string_t *)r->d_cols[c], row_map, k, side.col[c].d_goff, (uint64_t)(uintptr_t)(side.h + side.col[c].off),
-                                            (exg_string_t *)dst, r->stream);
-                rc = column_to_host(r, b, c, dst, es, nullptr, k, nullptr, nullptr, r->stream);
-            } else {
-                rc = column_to_host(r, b, c, src, es, nullptr, k, row_map, r->d_gather, cs);
-            }
-            if (rc) return rc;
-        }
-        return EXG_OK;
-    }
-    // read_vcf: behind the flat columns (QUAL's validity the last of them), the hand-over to the nested columns' emitter (id, alt,
-    // filter, info, formats)
-    int vcf_nested_columns(hipStream_t cs, ColDrain *col_drain) {
-        Batch *b = in.b.get();
-        int rc;
-        if (r->lazy_landing) {
-            RD_HIP(r, hipEventRecord(r->flat_ev, cs));  // (the scan's columns are free again behind this)
-            r->flat_pending = true;
-        }
-        if (!r->nested_state && (rc = nested_prepare(r))) return rc;
-        const ScanCtx ctx = scan_ctx();
-        uint64_t deliver = k;
-        const double t_ne = now_s();
-        trace_at("N nested begins", r->n_batches);
-        if ((rc = nested_emit(r, ctx, b, row_map, &deliver))) return rc;
-        trace_at("N nested landed", r->n_batches);
-        TRACE("nested columns (kernels + their way back)", t_ne);
-        b->n_rows = deliver;
-        if (r->lazy_landing) {
-            RD_HIP(r, hipEventCreateWithFlags(&b->landed, hipEventDisableTiming));
-            RD_HIP(r, hipEventRecord(b->landed, cs));
-            col_drain->cs = nullptr;
-        }
-        return EXG_OK;
-    }
-    // read_gtf: `attributes` — the ninth field of the rows that leave (through the row map) -> list entries relative to their
-    // DataChunk + key / value strings that point into the input's bytes (exg_gtf_attributes), on the scan's stream.  The children
-    // are provisioned for an entry per 16 bytes of the batch; a batch of denser entries is counted first and emitted again.
-    int gtf_attributes(SideScratch *scratch) {
-        Batch *b = in.b.get();
-        const uint64_t n_chunks = (k + r->batch_rows - 1) / r->batch_rows;
-        const uint64_t ws_bytes = exg_gtf_attributes_workspace_bytes(k);
-        void *d_ws = scratch->take(ws_bytes), *d_entries = scratch->take(k * 16), *d_bases = scratch->take((n_chunks + 1) * 8);
-        void *d_res = scratch->take(64);
-        if (!d_ws || !d_entries || !d_bases || !d_res) return fail(r, EXG_E_HIP, "out of device memory");
-        exg_gtf_attributes_args a;
-        memset(&a, 0, sizeof a);
-        a.d_strings = (const exg_string_t *)r->d_cols[8];
-        a.d_payload = in.d_input;
-        a.payload_base = (uint64_t)(uintptr_t)in.h;
-        a.d_row_map = row_map;
-        a.n_rows = k;
-        a.chunk_rows = r->batch_rows;
-        a.d_out_entries = (exg_list_entry_t *)d_entries;
-        a.d_out_chunk_base = (uint64_t *)d_bases;
-        a.d_workspace = d_ws, a.workspace_bytes = ws_bytes;
-        a.d_result = (struct exg_gtf_attributes_result *)d_res;
-        a.stream = r->stream;
-        struct exg_gtf_attributes_result ar;
-        uint64_t cap = in.n / 16 + k + 1024;
-        for (int attempt = 0;; attempt++) {
-            a.entries_capacity = cap;
-            if (!(a.d_out_keys = (exg_string_t *)scratch->take(cap * 16)) || !(a.d_out_values = (exg_string_t *)scratch->take(cap * 16)))
-                return fail(r, EXG_E_HIP, "out of device memory");
-            int rc = exg_gtf_attributes(&a);
-            if (rc) return fail(r, rc, exg_last_error_message());
-            rc = exg_gtf_attributes_result(a.d_result, r->stream, &ar);
-            if (rc == EXG_E_PARSE)
-                return fail(r, EXG_E_PARSE, std::string(exg_parse_error_string(EXG_PE_GTF_ATTRIBUTES)) + " at byte " + std::to_string(ar.error_offset) +
-                                                " of the attributes of feature line " + std::to_string(ar.error_row) + " of the batch that ends at byte " +
-                                                std::to_string(in.batch_end) + " of " + r->files[r->file_idx - 1]);
-            if (rc) return fail(r, rc, exg_last_error_message());
-            if (!(ar.flags & EXG_RF_CAPACITY)) break;
-            if (attempt) return fail(r, EXG_E_CAPACITY, "internal: the attributes' entries do not fit the count of the pass before");
-            cap = ar.total_entries;
-        }
-        const uint64_t total = ar.total_entries;
-        void *h_entries = b->host.alloc(k * 16), *h_bases = b->host.alloc((n_chunks + 1) * 8);
-        void *h_keys = b->host.alloc(total * 16 + 16), *h_vals = b->host.alloc(total * 16 + 16);
-        if (!h_entries || !h_bases || !h_keys || !h_vals) return fail(r, EXG_E_HIP, "out of pinned host memory");
-        RD_HIP(r, hipMemcpyAsync(h_entries, d_entries, k * 16, hipMemcpyDeviceToHost, r->stream));
-        RD_HIP(r, hipMemcpyAsync(h_bases, d_bases, (n_chunks + 1) * 8, hipMemcpyDeviceToHost, r->stream));
-        if (total) {
-            RD_HIP(r, hipMemcpyAsync(h_keys, a.d_out_keys, total * 16, hipMemcpyDeviceToHost, r->stream));
-            RD_HIP(r, hipMemcpyAsync(h_vals, a.d_out_values, total * 16, hipMemcpyDeviceToHost, r->stream));
-        }
-        r->host_vector_bytes += k * 16 + (n_chunks + 1) * 8 + total * 32;
-        b->nested.resize((size_t)b->n_cols);
-        NVec &m = b->nested[8];
-        m.type = EXG_TYPE_MAP, m.data = h_entries, m.elem = 16, m.length = k, m.child_base = (const uint64_t *)h_bases;
-        m.children.resize(1);
-        NVec &st = m.children[0];
-        st.type = EXG_TYPE_STRUCT, st.length = total;
-        st.children.resize(2);
-        st.children[0].type = st.children[1].type = EXG_TYPE_VARCHAR;
-        st.children[0].elem = st.children[1].elem = 16;
-        st.children[0].length = st.children[1].length = total;
-        st.children[0].data = h_keys, st.children[1].data = h_vals;
-        return EXG_OK;
-    }
-    // FASTA: the joined sequences
-    int fasta_sequences(hipStream_t cs) {
-        Batch *b = in.b.get();
-        // by a kernel's stores, not by a copy engine: the next batch's upload (slices that each take whichever engine is free
-        // when they are enqueued) ended up behind this copy on ITS engine every other batch and landed 5 ms late
-        // (a decoded stream: no upload beside it, the engine is faster)
-        if (switches().fasta_d2h_engine || r->src || (((uintptr_t)b->payload | (uintptr_t)r->d_payload) & 15)) {
-            RD_HIP(r, hipMemcpyAsync(b->payload, r->d_payload, res.payload_bytes, hipMemcpyDeviceToHost, cs));
-        } else if (int prc = exg::stream_to_host(b->payload, r->d_payload, res.payload_bytes, cs)) {
-            return fail(r, prc, exg_last_error_message());
-        }
-        r->host_vector_bytes += res.payload_bytes;  // (the joined sequences: the strings' payload is made on the device)
-        return EXG_OK;
-    }
+    // ... or the batch's host vectors (exg_rd_rows_out.cpp)
+    int columns_to_host() { return RowsOut{in, r, scan_ctx(), row_map}.columns_to_host(); }
 
     // ---- 9: the position behind the batch
     void commit_position() {

@@ -16,6 +16,7 @@
 #include "exg_bcf.hpp"
 #include "exg_bcf_header.hpp"
 #include "exg_rd_source.hpp"
+#include "exg_rd_stages.hpp"
 
 namespace exg_rd {
 
@@ -56,32 +57,32 @@ private:
 
 int BcfProducer::read_header(DecodedSource &src, hipStream_t st, BcfHeader *h, std::string *err) {
     PinBuf host;
-    for (uint64_t want = 64u << 10;;) {
+    auto front = [&](uint64_t want, uint64_t *avail, bool *eof) {
         const uint8_t *d_at = nullptr;
-        uint64_t avail = 0;
-        bool eof = false;
-        int rc = src.acquire(0, want, &d_at, &avail, &eof, err);
+        int rc = src.acquire(0, want, &d_at, avail, eof, err);
         if (rc) {
             if (err->find(path_) == std::string::npos) *err += in_file(path_);
             return rc;
         }
-        const uint64_t len = std::min<uint64_t>(want, avail);
+        const uint64_t len = std::min<uint64_t>(want, *avail);
         if (!host.ensure((size_t)len + 64)) {
             *err = "out of pinned host memory for the BCF header";
-            return EXG_E_HIP;
+            return (int)EXG_E_HIP;
         }
         if (len) PRODUCER_HIP(hipMemcpyAsync(host.p, d_at, len, hipMemcpyDeviceToHost, st));
         PRODUCER_HIP(hipStreamSynchronize(st));
-        uint64_t need = 0;
+        return (int)EXG_OK;
+    };
+    auto inspect = [&](uint64_t len, bool ended, uint64_t *need) {
         std::string why;
-        const int prc = bcf_parse_header((const uint8_t *)host.p, len, eof && len == avail, h, &need, &why);
+        const int prc = bcf_parse_header((const uint8_t *)host.p, len, ended, h, need, &why);
         if (prc == kBcfHeaderBad) {
             *err = why + in_file(path_);
-            return EXG_E_PARSE;
+            return (int)EXG_E_PARSE;
         }
-        if (prc == kBcfHeaderOk) return EXG_OK;
-        want = std::max<uint64_t>(need, want * 2);
-    }
+        return prc == kBcfHeaderOk ? (int)kPrefixDone : (int)kPrefixMore;
+    };
+    return read_prefix(64u << 10, front, inspect, prefix_grow_need_or_double);
 }
 
 int BcfProducer::upload(SegmentSink &sink, hipStream_t st, const BcfHeader &h, Tables *t, std::string *err) {

@@ -116,8 +116,8 @@ inline constexpr FormatDesc kFormats[] = {
     // to declare ([RECALLED]).  The strings are produced into a side buffer (or point into the reference names):
     // none into the input
     // (32: segments as for the text formats, a workspace of ~0.8 B, a side buffer of ~1.25 B and ~2 B of vectors per decoded byte.
-    // Rows, workspace and buffers are BamState's own — exg_rd_bam.cpp —: the sizing fields behind the divisor are not read for
-    // BAM and hold 1, like a format there is none of)
+    // The workspace and the side buffer are BamState's own, and the reader's column vectors are provisioned with BAM's own sizing
+    // — exg_rd_bam.cpp —: the sizing fields behind the divisor are not read for BAM and hold 1, like a format there is none of)
     {EXG_FMT_BAM, "bam", "exg: scan bam batch", EXG_BAM_COLUMNS,
      {str("name", false, false), i32("flag", false), str("reference", true, false), i32("start", true), i32("end", true),
       str("mapping_quality", true, false), str("cigar", false, false), str("mate_reference", true, false), str("sequence", false, false),

@@ -7,9 +7,13 @@
 //   exg_rd_gzip.cpp    the gzip / BGZF producer;  exg_rd_zstd.cpp  the zstd producer;  exg_rd_bzip2.cpp  the bzip2 producer
 //   exg_zstd_index.cpp host only: the zstd frame / block walk and a round's block list (no HIP call; under ASan as above)
 //   exg_rd_fanout.cpp  host only: stripes of one input read by worker threads on N devices (exg_rd_fanout.hpp)
-//   exg_rd_batch.cpp   open_next_file, next_batch: one device batch -> host vectors, as a driver over named stages
+//   exg_rd_open.cpp    open_next_file: the mapping or the decoded stream, its header prefix, the shard's place in the file
+//   exg_rd_batch.cpp   next_batch: one device batch from the input to the scan's verdict, as a driver over named stages
+//   exg_rd_rows_out.cpp  the rows' way out: row selection, the side buffer, the columns -> the batch's host vectors (RowsOut);
+//                      what exg_rd_bam.cpp shares of it
+//   exg_rd_bam.cpp     read_bam_file_records: the header, and a batch loop of its own in front of the shared way out
 //   exg_rd_stages.hpp  host only: the stages' decisions that make no HIP call — attempt size and halo, the upload window, what a
-//                      scan's result means (under ASan as above)
+//                      scan's result means, the loop that reads a header's prefix (under ASan as above)
 //   exg_reader.cpp     the C entry points (exg_open ... exg_close) and the chunk slicing
 #pragma once
 #include <stdio.h>
@@ -22,7 +26,12 @@
 
 #include "exg_reader.hpp"
 
+namespace exg::arrow {
+struct FilterCols;  // exg_arrow.hpp
+}
 namespace exg_rd {
+
+struct HostMirror;  // exg_rd_source.hpp
 
 #define RD_HIP(r, expr)                                                                            \
     do {                                                                                           \
@@ -200,11 +209,97 @@ struct Stripe;
 int list_path(const std::string &path, std::vector<std::string> *files, std::string *err);
 int plan_stripes(const std::vector<std::string> &files, Compression compression, const exg_open_args *args, std::vector<Stripe> *out, unsigned *n_workers);
 
+// The A/B switches of the reader level, read once per process.  (EXG_NO_VCF_INDEX and EXG_VCF_ONE_STREAM are not here: they are read
+// per batch, where they are used — the tests switch them inside one process.)
+struct Switches {
+    const bool fasta_whole_text = getenv("EXG_FASTA_WHOLE_TEXT") != nullptr;      // a decoded FASTA: the decoded text behind the scan, no side buffer
+    const bool no_payload_compact = getenv("EXG_NO_PAYLOAD_COMPACT") != nullptr;  // a projection of a decoded input: no side buffer
+    const bool no_host_mirror = getenv("EXG_NO_HOST_MIRROR") != nullptr;          // (and tests) a decoded input: the copy behind the scan
+    const bool no_ramp = getenv("EXG_NO_RAMP") != nullptr;                        // a text file's first batch is a full one
+    const bool no_fasta_prefetch = getenv("EXG_NO_FASTA_PREFETCH") != nullptr;    // FASTA: one input slot, no upload beside the way back
+    const bool no_prefetch = getenv("EXG_NO_PREFETCH") != nullptr;                // no upload ahead of the scan
+    const bool fastq_one_stream = getenv("EXG_FASTQ_ONE_STREAM") != nullptr;      // a text FASTQ's vectors on the scan's stream
+    const bool vcf_eager_landing = getenv("EXG_VCF_EAGER_LANDING") != nullptr;    // read_vcf waits for its vectors inside next_batch
+    const bool fasta_d2h_engine = getenv("EXG_FASTA_D2H_ENGINE") != nullptr;      // FASTA: the joined sequences by a copy engine
+};
+inline const Switches &switches() {
+    static const Switches s;
+    return s;
+}
+
+// One word from a kernel: `launch(d_word)` enqueues on r->stream what writes a u32 / u64 to d_word (the reader's d_phase, taken
+// when first needed) and returns an EXG code; the word comes back into *out and the stream is idle on return.
+template <class Word, class Launch>
+int fetch_word(exg_reader *r, Word *out, Launch launch) {
+    static_assert(sizeof(Word) == 4 || sizeof(Word) == 8, "a device word is 4 or 8 bytes");
+    if (!r->d_phase && !(r->d_phase = dev_pool()->take(r->device, 4096))) return fail(r, EXG_E_HIP, "out of device memory");
+    if (int rc = launch(r->d_phase)) return fail(r, rc, exg_last_error_message());
+    RD_HIP(r, hipMemcpyAsync(out, r->d_phase, sizeof(Word), hipMemcpyDeviceToHost, r->stream));
+    RD_HIP(r, hipStreamSynchronize(r->stream));
+    return EXG_OK;
+}
+
+// ---- exg_rd_open.cpp (open_next_file: exg_reader.hpp)
+// How the bytes a decoded input's strings point into reach the host when chunks are handed out (never for COUNT(*) or the Arrow
+// stream): kPayloadCompact — a projection that leaves payload-bearing columns out: the selected columns' out-of-line strings are
+// closed up into a side buffer behind the scan; kPayloadMirror — the decoded segments themselves, sent ahead by the producer
+// (HostMirror; a segment without one is copied behind its scan); kPayloadNone — no string column is selected.  FASTA (round 6):
+// always the side buffer for id / description — its sequences are joined on the device and travel as that, so the decoded text is
+// needed for the definition lines' strings alone, 2 % of it (the whole text went along until then: a bgzip FASTA into DataChunks
+// sent every byte back twice, 92 ms for 1.96 GB).
+enum PayloadRoute { kPayloadNone, kPayloadCompact, kPayloadMirror };
+PayloadRoute payload_route(const exg_reader *r);
+// Newlines in the decoded bytes of the members / frames in front of a shard's own (file bytes [0, own_c_begin)), by a decoder
+// of their own: a segment is counted on the device and dropped, nothing but it is resident (the phase of a shard of a
+// compressed FASTQ when the bytes around the cut do not tell it: a memchr over the page cache in the text case).
+int count_newlines_in_front(exg_reader *r, uint64_t *out);
+
 // ---- exg_rd_batch.cpp
+// the reader's vectors of the columns in `produce` (bit c: schema column c), for r->cap_records rows (the reader's dev_alloc)
+int alloc_columns(exg_reader *r, uint64_t produce);
 // the next device batch with rows -> r->batch (false + *end: every file is exhausted); what exg_next_chunk and a fan-out
 // worker both do between two batches: pending parse errors, the end of a file, the next file
 int advance_batch(exg_reader *r, bool *end);
 // the mapping of the current file lost pages to a truncation (exg_map_guard.hpp): EXG_E_IO
 int truncated_while_read(exg_reader *r);
+
+// ---- exg_rd_rows_out.cpp: the rows' way out of a scanned batch (chunk boundary)
+// Rows where the predicate is TRUE — and whose bit in d_keep is set, when there are keep words — -> the reader's row map; the
+// columns are gathered through it on their way out.  The caller says where each column's strings live (fc->d_base, fc->payload_base);
+// kinds, data and validity come from the format table and the reader's column vectors.  *k: the scan's rows in, the rows that leave out.
+int select_rows(exg_reader *r, exg::arrow::FilterCols *fc, const uint64_t *d_keep, uint64_t *k, const uint32_t **row_map);
+// ... and its buffers, for r->cap_records rows (the reader's dev_alloc): the row map, one column of gather scratch, the scan's scratch
+int alloc_row_selection(exg_reader *r);
+struct SideBuf;
+// The flat columns the projection wants -> b, each with its validity words, gathered through the row map and copied back on `cs`
+// (side: the compact route's side buffer, whose string columns are repointed first; NULL: none)
+int flat_columns_to_host(exg_reader *r, Batch *b, uint64_t k, const uint32_t *row_map, hipStream_t cs, const SideBuf *side);
+// the batch is whole (or carries the event that says when): it becomes r->batch
+void publish_batch(exg_reader *r, const std::shared_ptr<Batch> &b);
+// What the way out reads of one attempt at a batch (the rest of it — BatchIn, exg_rd_batch.cpp — is the input half's alone)
+struct BatchOut {
+    uint64_t n = 0;          // bytes of the attempt: behind file_pos until the input is bound, then all the scan is given (`lead` included)
+    uint64_t batch_end = 0;  // file offset one past the bytes of this batch
+    std::shared_ptr<PinnedBlock> gz_payload;  // gzip: this batch's inflated bytes on the host (string_t payload)
+    std::shared_ptr<HostMirror> gz_mirror;    // ... when the producer sent them ahead (exg_rd_source.hpp); then only
+    uint64_t gz_front = 0;                    // ... the first gz_front bytes of the batch (the carried tail) are copied here
+    bool compact = false;                     // ... or: only the selected columns' out-of-line strings travel (a side buffer)
+    std::shared_ptr<Batch> b;  // FASTA: made in front of the scan (its pinned block takes the joined sequences); else by columns_to_host
+};
+// The way out of a text format's batch, and everything it depends on: that of the attempt, the reader, what the scan left in HBM
+// and the rows that leave.  BAM has no use for it: its side buffer is the scan's own and travels whole (exg_rd_bam.cpp).
+struct RowsOut : BatchOut {
+    exg_reader *r;
+    ScanCtx scan;             // d_input, h, the rows that leave (n_records), the scan's result, FASTA's payload base
+    const uint32_t *row_map;  // NULL: every row of the scan leaves
+    int columns_to_host();                    // -> r->batch
+
+private:
+    int side_buffer(SideBuf *side, SideScratch *scratch);
+    int columns_stream(hipStream_t *cs, ColDrain *col_drain);
+    int vcf_nested_columns(hipStream_t cs, ColDrain *col_drain);
+    int gtf_attributes(SideScratch *scratch);
+    int fasta_sequences(hipStream_t cs);
+};
 
 }  // namespace exg_rd

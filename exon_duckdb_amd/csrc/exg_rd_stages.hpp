@@ -1,5 +1,6 @@
 // exg_rd_stages.hpp — the decisions of next_batch (exg_rd_batch.cpp) that make no HIP call: how large an attempt is and how
-// far its halo reaches back, which file bytes the next upload carries, what a scan's result means for the attempt.  Host
+// far its halo reaches back, which file bytes the next upload carries, what a scan's result means for the attempt; and the loop
+// that reads a header from the front of a decoded stream (exg_rd_open.cpp, exg_rd_bam.cpp, exg_rd_bcf.cpp).  Host
 // only and free of any HIP include: under ASan + UBSan in tests/host_asan_driver.cpp.
 #pragma once
 #include <stdint.h>
@@ -57,6 +58,30 @@ inline PrefetchWindow prefetch_window(uint64_t begin, uint64_t end, uint64_t max
     const uint64_t slack = std::min<uint64_t>(max_slack, (end - begin) / 2);
     return {(end - slack) & ~15ull, slack};
 }
+
+// ---- a header at the front of a decoded stream ----------------------------------------------------------------------------------
+// A growing prefix of the stream comes to the host until a parser is satisfied (the VCF / SAM header lines, the BAM and the BCF
+// header).  `front(want, &avail, &eof)` brings min(want, avail) bytes of the stream's front to the host (avail: what the stream
+// holds from its first byte on, eof: it ends there) and returns an error code or 0.  `inspect(len, ended, &need)` looks at those
+// len bytes — ended: the stream ends with them, there will be no more — and answers kPrefixDone, kPrefixMore (need: how many
+// bytes it knows it wants, 0 when it cannot tell) or an error code (negative, EXG_E_*: the reason is the caller's to keep).
+// `grow(want, need)` is the next size to ask for.  What the first error says, and to whom, is the callables' business.
+enum { kPrefixDone = 0, kPrefixMore = 1 };
+template <class Front, class Inspect, class Grow>
+int read_prefix(uint64_t first, Front front, Inspect inspect, Grow grow) {
+    for (uint64_t want = first;;) {
+        uint64_t avail = 0, need = 0;
+        bool eof = false;
+        if (int rc = front(want, &avail, &eof)) return rc;
+        const uint64_t len = std::min<uint64_t>(want, avail);
+        const int answer = inspect(len, eof && len == avail, &need);
+        if (answer != kPrefixMore) return answer;
+        want = grow(want, need);
+    }
+}
+// the growth rules: text headers (lines: the parser cannot say how much it needs) and the binary ones (it can)
+inline uint64_t prefix_grow_times8(uint64_t want, uint64_t) { return want * 8; }
+inline uint64_t prefix_grow_need_or_double(uint64_t want, uint64_t need) { return std::max<uint64_t>(need, want * 2); }
 
 // ---- stage 6: what a scan's result means for the attempt --------------------------------------------------------------------
 enum BatchVerdict {

@@ -448,7 +448,7 @@ struct exg_reader {
     uint64_t preset_pos = 0;    // ... first owned inflated byte (what is in front of it is the halo)
     uint64_t data_base = 0;           // first data byte in the coordinates of file_pos (behind the VCF header; 0 in a BGZF shard's own buffer)
     bool data0_is_line_start = true;  // byte 0 of the data (behind the header) begins a line (not so for a BGZF shard's halo)
-    void *d_phase = nullptr;  // device u32 for exg_fastq_guess_phase
+    void *d_phase = nullptr;  // a device word a kernel answers in (fetch_word, exg_rd_internal.hpp: exg_fastq_guess_phase and the like)
     uint64_t gz_header_prefix = 0;  // gzip + VCF: bytes of the inflated file's start held in file->p (header parse)
     bool worst_case_rows = false;
     bool ws_full = false;  // under EXG_DEVICE_MEM_CAP_MB: a batch overflowed the budgeted line index, the workspace is at full size
@@ -519,7 +519,8 @@ struct exg_reader {
     std::shared_ptr<void> arrow_state;
     // chunk mode, VCF: the INFO / FORMAT keys of the header, the schema trees, the emitter's device arena
     std::shared_ptr<void> nested_state;
-    // read_bam_file_records: the header's reference names (host + device) and the scan's buffers (exg_rd_bam.cpp)
+    // read_bam_file_records: the header, its reference names (host + device), the scan's workspace and side buffer (exg_rd_bam.cpp;
+    // the columns, validity words and row-selection buffers are the fields above)
     std::shared_ptr<void> bam_state;
     bool bcf = false;  // file_format "bcf": the records become VCF lines in the decoded stream (exg_rd_bcf.cpp); format is EXG_FMT_VCF
 

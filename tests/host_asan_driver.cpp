@@ -375,6 +375,87 @@ int main(int argc, char **argv) {
                     if (flen && (f.start + flen > range_hi || flen + 16 > d_in_cap || flen > step)) return 16;
                     runs++;
                 }
+        // read_prefix: a header at the front of a decoded stream, here a stream of `size` bytes in memory that hands out whole
+        // segments of `seg` bytes (so `avail` may exceed what was asked for) and a parser whose header is `header` bytes long, that
+        // knows after its first look that it needs `need` (0: it cannot tell) and answers EXG_E_PARSE when the stream ends inside
+        // the header (`text`: a header of lines, which then is complete) or at its `bad_at`-th look.  What is pinned: the sizes
+        // asked for — 64 KiB, 128 KiB, ... or `need` (BAM, BCF); 4 MiB, 32 MiB, ... (VCF, SAM) —, that the parser is told "the
+        // stream ends here" exactly once and only with all the stream's bytes in hand, and that the first error ends the loop.
+        struct PrefixRun {
+            int rc;
+            std::vector<uint64_t> asked;
+            int looks, told_ended;
+            uint64_t ended_len;
+        };
+        auto prefix_run = [](uint64_t first, uint64_t size, uint64_t seg, uint64_t header, uint64_t need, bool times8, bool text, int bad_at, int front_fails_at) {
+            PrefixRun o = {0, {}, 0, 0, 0};
+            auto front = [&](uint64_t want, uint64_t *avail, bool *eof) {
+                o.asked.push_back(want);
+                if ((int)o.asked.size() == front_fails_at) return (int)EXG_E_IO;
+                *avail = std::min<uint64_t>(size, (want + seg - 1) / seg * seg);
+                *eof = *avail == size;
+                return (int)EXG_OK;
+            };
+            auto inspect = [&](uint64_t len, bool ended, uint64_t *need_out) {
+                o.looks++;
+                if (ended) o.told_ended++, o.ended_len = len;
+                if (o.looks == bad_at) return (int)EXG_E_PARSE;
+                if (len >= header) return (int)kPrefixDone;
+                if (ended) return text ? (int)kPrefixDone : (int)EXG_E_PARSE;
+                *need_out = need;
+                return (int)kPrefixMore;
+            };
+            o.rc = times8 ? read_prefix(first, front, inspect, prefix_grow_times8) : read_prefix(first, front, inspect, prefix_grow_need_or_double);
+            return o;
+        };
+        typedef std::vector<uint64_t> Asked;
+        const uint64_t K = 1024, M = 1024 * K, big = 1ull << 40;
+        {   // complete in the first ask, under both rules
+            const PrefixRun a = prefix_run(64 * K, big, 64 * K, 1000, 0, false, false, 0, 0), b = prefix_run(4 * M, big, M, 4 * M, 0, true, true, 0, 0);
+            if (a.rc || a.asked != Asked{64 * K} || a.looks != 1 || a.told_ended || b.rc || b.asked != Asked{4 * M} || b.looks != 1 || b.told_ended) return 18;
+        }
+        {   // one, two and three growth steps: doubling (the parser cannot tell what it needs) and times eight
+            const Asked dbl = {64 * K, 128 * K, 256 * K, 512 * K}, x8 = {4 * M, 32 * M, 256 * M, 2048 * M};
+            for (size_t steps = 1; steps <= 3; steps++) {
+                const PrefixRun a = prefix_run(dbl[0], big, 64 * K, dbl[steps - 1] + 1, 0, false, false, 0, 0);
+                const PrefixRun b = prefix_run(x8[0], big, M, x8[steps - 1] + 1, 0, true, true, 0, 0);
+                if (a.rc || a.asked != Asked(dbl.begin(), dbl.begin() + steps + 1) || a.looks != (int)steps + 1 || a.told_ended) return 18;
+                if (b.rc || b.asked != Asked(x8.begin(), x8.begin() + steps + 1) || b.looks != (int)steps + 1 || b.told_ended) return 18;
+                runs += 2;
+            }
+            // (a reader whose device batch is smaller than 4 MiB starts there: 1 MiB, 8 MiB, 64 MiB)
+            if (prefix_run(M, big, 64 * K, 8 * M + 1, 0, true, true, 0, 0).asked != Asked{M, 8 * M, 64 * M}) return 18;
+        }
+        {   // the parser knows what it needs: more than twice the ask is taken as it stands, less is the doubling's
+            const PrefixRun a = prefix_run(64 * K, big, 64 * K, 5 * M + 3, 5 * M + 3, false, false, 0, 0), b = prefix_run(64 * K, big, 64 * K, 70 * K, 70 * K, false, false, 0, 0);
+            if (a.rc || a.asked != Asked{64 * K, 5 * M + 3} || b.rc || b.asked != Asked{64 * K, 128 * K}) return 18;
+            // ... and times eight does not listen to it
+            if (prefix_run(4 * M, big, M, 5 * M, 5 * M, true, true, 0, 0).asked != Asked{4 * M, 32 * M}) return 18;
+        }
+        {   // the stream ends inside the header: told once, with every byte of the stream in hand — not while a segment that
+            // reaches the end is only partly asked for (avail 100 KiB, eof, but 64 KiB taken)
+            for (const uint64_t seg : {64 * K, M}) {
+                const PrefixRun a = prefix_run(64 * K, 100 * K, seg, 200 * K, 0, false, false, 0, 0);
+                if (a.rc != EXG_E_PARSE || a.asked != Asked{64 * K, 128 * K} || a.looks != 2 || a.told_ended != 1 || a.ended_len != 100 * K) return 18;
+                const PrefixRun t = prefix_run(64 * K, 100 * K, seg, 200 * K, 0, true, true, 0, 0);  // a header of lines: the stream's end completes it
+                if (t.rc || t.asked != Asked{64 * K, 512 * K} || t.told_ended != 1 || t.ended_len != 100 * K) return 18;
+                runs += 2;
+            }
+            // a stream that is exactly the first ask long ends with it
+            const PrefixRun e = prefix_run(64 * K, 64 * K, 64 * K, 200 * K, 0, false, false, 0, 0);
+            if (e.rc != EXG_E_PARSE || e.asked != Asked{64 * K} || e.told_ended != 1 || e.ended_len != 64 * K) return 18;
+        }
+        {   // "bad" at the second look ends the loop there; an error of the stream's is passed on without a look
+            const PrefixRun a = prefix_run(64 * K, big, 64 * K, big, 0, false, false, 2, 0), b = prefix_run(64 * K, big, 64 * K, big, 0, false, false, 0, 3);
+            if (a.rc != EXG_E_PARSE || a.asked != Asked{64 * K, 128 * K} || a.looks != 2) return 18;
+            if (b.rc != EXG_E_IO || b.asked != Asked{64 * K, 128 * K, 256 * K} || b.looks != 2) return 18;
+        }
+        {   // an empty stream: one ask, one look at no bytes, told that this is all
+            const PrefixRun a = prefix_run(64 * K, 0, 64 * K, 12, 0, false, false, 0, 0), t = prefix_run(4 * M, 0, M, 1, 0, true, true, 0, 0);
+            if (a.rc != EXG_E_PARSE || a.asked != Asked{64 * K} || a.looks != 1 || a.told_ended != 1 || a.ended_len != 0) return 18;
+            if (t.rc || t.asked != Asked{4 * M} || t.looks != 1 || t.told_ended != 1 || t.ended_len != 0) return 18;
+        }
+        runs += 12;
     }
     // the format table (exg_rd_format.hpp) against every format's columns written out: name, type, nullable, bytes per row at the
     // chunk boundary (0: a nested column), and the masks and sizing constants the reader's stages take from it

@@ -116,6 +116,36 @@ def test_short_reads_any_segmentation(gpu, illumina, monkeypatch, batch):
     r.close()
 
 
+# ---------------------------------------------------------------- 2b. more rows in a segment than the vectors are provisioned for
+@pytest.fixture(scope="module")
+def smallest_records(tmp_path_factory):
+    """60 000 records as small as a record can be with a name: one character, no CIGAR, no sequence, no aux — 38 bytes each,
+    2.3 MB decoded.  Position and flag differ from row to row, so a row out of place is seen."""
+    recs = [B.record(name=b"ACGT"[i % 4:i % 4 + 1], flag=(i * 37) % 256, ref=0, pos=i, mapq=i % 61) for i in range(60_000)]
+    assert all(len(rec) == 38 for rec in recs)
+    raw = B.header([(b"c", 1 << 28)]) + b"".join(recs)
+    path = tmp_path_factory.mktemp("bam") / "smallest.bam"
+    path.write_bytes(B.bgzf(raw, level=1))
+    return path, B.parse_decoded(raw).rows
+
+
+@pytest.mark.parametrize("filters", [None, "flag>=128"])
+def test_smallest_records_overflow_the_provisioned_rows(gpu, smallest_records, monkeypatch, filters):
+    """With 1 MiB batches the reader provisions 1 445 888 bytes of input and 1 445 888 / 64 + 4096 = 26 688 rows; a full segment
+    of 38-byte records holds about 27 600.  The batch that says so frees every device buffer of the reader — the column vectors,
+    the row map and the gather scratch among them — provisions them for the worst case and is scanned again: the rows of that batch
+    and of those behind it must be the file's, unfiltered and through the row map."""
+    path, want = smallest_records
+    monkeypatch.setenv("EXG_DEVICE_BATCH_BYTES", str(1 << 20))
+    rows, err, st = read_all(path, filters=filters)
+    exp = [r for r in want if filters is None or r[1] >= 128]
+    assert err is None and len(rows) == len(exp)
+    assert rows == exp
+    if filters:
+        assert 0.4 < len(exp) / len(want) < 0.6
+    print(f"filters {filters}: batches {st['device_batches']} segments {st.get('decoded_segments')}")
+
+
 # ---------------------------------------------------------------- 3. edge records
 def edge_records():
     all_ops = [(1, "M"), (2, "I"), (3, "D"), (4, "N"), (5, "S"), (6, "H"), (7, "P"), (8, "="), ((1 << 28) - 1, "X")]

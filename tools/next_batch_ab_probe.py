@@ -1,16 +1,32 @@
-"""The legs that pass through next_batch (exg_rd_batch.cpp), for an A/B of two builds of libexon_gpu.so inside one session on one
+"""The legs that pass through next_batch (exg_rd_batch.cpp, exg_rd_rows_out.cpp, exg_rd_bam.cpp), for an A/B of two builds of libexon_gpu.so inside one session on one
 box (profiles/next_batch_refactor_ab.md).  `make`: the inputs, once, into /dev/shm/exg_ab.  `measure LABEL`: one process = one
 library (whatever exon_duckdb_amd/lib/libexon_gpu.so is at that moment): every leg once to warm, then RUNS (5) timed; prints ms.
 The caller copies the variants over libexon_gpu.so in turn (as tools/ab_zst.sh does) and removes /dev/shm/exg_ab at the end."""
 import os, struct, sys, time, zlib
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))  # the BAM / SAM / GTF writers of the tests
 import torch  # noqa: E402
 import bench  # noqa: E402
 from exon_duckdb_amd import device, load_library  # noqa: E402
 
 D = "/dev/shm/exg_ab"
 FQ, VCF, FA, FQGZ, VCFGZ = D + "/a.fastq", D + "/a.vcf", D + "/a.fasta", D + "/a.fastq.gz", D + "/b.vcf.gz"
+BAM, SAM, GTF = D + "/a.bam", D + "/a.sam", D + "/a.gtf"
+
+
+def make_rows_out_inputs():
+    """BAM (400 MB decoded), SAM and GTF text (300 MB each): a block of the test writers' records, repeated"""
+    import bam_files, gtf_files, sam_files
+    refs = [(b"chr%d" % i, 250_000_000) for i in range(1, 23)]
+    run = b"".join(bam_files.illumina_pairs(10_000, refs, seed=5))
+    bam_files.write_repeated(BAM, bam_files.header(refs), run, int(4e8) // len(run))
+    for path, head, block in ((SAM, sam_files.header(), sam_files.mixed(sam_files.rng(5), 20_000, read_len=150)),
+                              (GTF, b"", gtf_files.mixed(gtf_files.rng(5), 20_000))):
+        with open(path, "wb") as f:
+            f.write(head)
+            for _ in range(int(3e8) // len(block)):
+                f.write(block)
 
 
 def make():
@@ -43,6 +59,7 @@ def make():
     from exon_duckdb_amd.testing.bgzf import bgzip
     bgzip(D + "/b.vcf", VCFGZ)
     os.unlink(D + "/b.vcf")
+    make_rows_out_inputs()
     print("inputs:", {p: os.path.getsize(os.path.join(D, p)) for p in os.listdir(D)}, flush=True)
 
 
@@ -72,6 +89,10 @@ def measure(label):
         ("bgzf fastq -> Arrow", lambda: arrow(FQGZ, "fastq")[1]),
         ("bgzf vcf all columns", lambda: bench.reader_chunks(lib, VCFGZ, "vcf")[2]),
         ("bgzf vcf -> Arrow", lambda: arrow(VCFGZ, "vcf")[1]),
+        ("bam all columns", lambda: bench.reader_chunks(lib, BAM, "bam")[2]),
+        ("bam filtered flag<128, all columns", lambda: bench.reader_chunks(lib, BAM, "bam", filters="flag<128")[2]),
+        ("sam all columns", lambda: bench.reader_chunks(lib, SAM, "sam")[2]),
+        ("gtf all columns with attributes", lambda: bench.reader_chunks(lib, GTF, "gtf")[2]),
     ]
     for name, fn in legs:
         fn()
