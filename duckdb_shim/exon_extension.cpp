@@ -550,8 +550,54 @@ static void ExtractFromCigarFunction(DataChunk &args, ExpressionState &, Vector 
 	}
 }
 
-// exon_extension.cpp:62-73, :81-93: the sequence scalars, the flag predicates, the alignment scores and strings and the two
-// CIGAR scalars (gff_parse_attributes is not registered: INTEGRATION.md)
+// gff_functions/module.cpp:29-84: gff_parse_attributes(VARCHAR) -> MAP(VARCHAR, VARCHAR) on the host scalar
+// exon_scan::GffParseAttributes over the rules of csrc/exg_gffattr.hpp.  A MAP is a LIST(STRUCT(key, value)) physically: the list
+// entries and the two children are written directly, as ParseCigarFunction writes its list.  Entries stay in field order and a
+// repeated key stays a second entry.  NULL in, NULL out; a segment that is not key=value throws with the reference's text.
+static void GffParseAttributesFunction(DataChunk &args, ExpressionState &, Vector &result) {
+	const idx_t count = args.size();
+	UnifiedVectorFormat in;
+	args.data[0].ToUnifiedFormat(count, in);
+	auto strings = reinterpret_cast<const string_t *>(in.data);
+	result.SetVectorType(VectorType::FLAT_VECTOR);
+	auto entries = FlatVector::GetData<list_entry_t>(result);
+	struct Slice {
+		idx_t row; // of `strings`
+		exon_scan::GffAttribute at;
+	};
+	std::vector<Slice> all;
+	std::vector<exon_scan::GffAttribute> row;
+	for (idx_t i = 0; i < count; i++) {
+		const idx_t k = in.sel->get_index(i);
+		entries[i].offset = all.size();
+		entries[i].length = 0;
+		if (!in.validity.RowIsValid(k)) {
+			FlatVector::SetNull(result, i, true);
+			continue;
+		}
+		const exon_scan::GffAttributeStatus st = exon_scan::GffParseAttributes(strings[k].GetData(), strings[k].GetSize(), &row);
+		if (st.code) {
+			throw InvalidInputException(exon_scan::GffAttributeErrorText(strings[k].GetData(), st));
+		}
+		entries[i].length = row.size();
+		for (const auto &at : row) {
+			all.push_back(Slice {k, at});
+		}
+	}
+	ListVector::Reserve(result, all.size());
+	auto &fields = StructVector::GetEntries(ListVector::GetEntry(result));
+	auto keys = FlatVector::GetData<string_t>(*fields[0]);
+	auto values = FlatVector::GetData<string_t>(*fields[1]);
+	for (idx_t j = 0; j < all.size(); j++) {
+		const char *field = strings[all[j].row].GetData();
+		keys[j] = StringVector::AddString(*fields[0], field + all[j].at.key_start, (idx_t)all[j].at.key_len);
+		values[j] = StringVector::AddString(*fields[1], field + all[j].at.value_start, (idx_t)all[j].at.value_len);
+	}
+	ListVector::SetListSize(result, all.size());
+}
+
+// exon_extension.cpp:62-73, :81-93: the sequence scalars, the flag predicates, the alignment scores and strings, the two
+// CIGAR scalars and gff_parse_attributes
 static void RegisterScalars(DatabaseInstance &db) {
 	RegisterAlignmentScore(db, "alignment_score");
 	RegisterAlignmentScore(db, "alignment_score_wfa_gap_affine");
@@ -579,6 +625,10 @@ static void RegisterScalars(DatabaseInstance &db) {
 	    db, ScalarFunction("extract_from_cigar", {LogicalType::VARCHAR, LogicalType::VARCHAR},
 	                       LogicalType::STRUCT({{"sequence_start", LogicalType::INTEGER}, {"sequence_end", LogicalType::INTEGER}, {"sequence", LogicalType::VARCHAR}}),
 	                       ExtractFromCigarFunction));
+	// exon_extension.cpp:63-64; the return type through RealDuck::MakeMap, as read_gtf's attributes column gets it
+	ExtensionUtil::RegisterFunction(db, ScalarFunction("gff_parse_attributes", {LogicalType::VARCHAR},
+	                                                   RealDuck::MakeMap<LogicalType>(LogicalType::VARCHAR, LogicalType::VARCHAR, 0),
+	                                                   GffParseAttributesFunction));
 	for (uint32_t which = 0; which < (uint32_t)exg::seqfn::kSamFlagCount; which++) {
 		ExtensionUtil::RegisterFunction(
 		    db, ScalarFunction(exg::seqfn::kSamFlagNames[which], {LogicalType::INTEGER}, LogicalType::BOOLEAN,

@@ -70,6 +70,7 @@ EXG_PE_GTF_SCORE = 60
 EXG_PE_GTF_STRAND = 61
 EXG_PE_GTF_FRAME = 62
 EXG_PE_GTF_ATTRIBUTES = 63
+EXG_PE_GFF_ATTRIBUTES = 65    # (64 stays unassigned)
 
 EXG_FMT_FASTA, EXG_FMT_FASTQ, EXG_FMT_VCF, EXG_FMT_BAM, EXG_FMT_BED, EXG_FMT_SAM = 1, 2, 3, 4, 5, 6
 EXG_FMT_BCF = 7
@@ -427,6 +428,24 @@ class GtfAttributesArgs(C.Structure):
     ]
 
 
+class GffAttributesResult(C.Structure):
+    _fields_ = [
+        ("total_entries", C.c_uint64),
+        ("error_row", C.c_uint64),
+        ("error_offset", C.c_uint64),
+        ("n_rows", C.c_uint64),
+        ("error_code", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("error_length", C.c_uint32),
+        ("pad", C.c_uint8 * 20),
+    ]
+
+
+class GffAttributesArgs(C.Structure):
+    """exg_gff_attributes_args: exg_gtf_attributes_args field for field"""
+    _fields_ = list(GtfAttributesArgs._fields_)
+
+
 class CigarResult(C.Structure):
     _fields_ = [
         ("total_ops", C.c_uint64),
@@ -510,6 +529,9 @@ SIGNATURES = {
     "exg_gtf_attributes_workspace_bytes": (C.c_uint64, [C.c_uint64]),
     "exg_gtf_attributes": (C.c_int, [C.POINTER(GtfAttributesArgs)]),
     "exg_gtf_attributes_result": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(GtfAttributesResult)]),
+    "exg_gff_attributes_workspace_bytes": (C.c_uint64, [C.c_uint64]),
+    "exg_gff_attributes": (C.c_int, [C.POINTER(GffAttributesArgs)]),
+    "exg_gff_attributes_result": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(GffAttributesResult)]),
     "exg_bcf_workspace_bytes": (C.c_uint64, [C.c_uint64, C.c_uint32]),
     "exg_bcf_to_vcf": (C.c_int, [C.POINTER(BcfToVcfArgs)]),
     "exg_bcf_result": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(BcfToVcfResult)]),
@@ -582,6 +604,8 @@ TEST_SIGNATURES = {
                                       C.POINTER(C.c_uint64), C.c_char_p, C.c_uint64]),
     "exon_tf_extract_from_cigar": (C.c_int, [C.c_uint64, C.c_char_p, C.c_uint64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_uint32),
                                              C.POINTER(C.c_uint64), C.c_char_p, C.c_uint64]),
+    "exon_tf_gff_parse_attributes": (C.c_int, [C.c_char_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32),
+                                               C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_char_p, C.c_uint64]),
     "exon_tf_parse_cigar_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "exon_tf_link_probe": (C.c_int, [C.c_int, C.c_uint64, C.c_int, C.POINTER(C.c_double)]),
     "exon_tf_host_pipeline_probe": (C.c_double, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double]),

@@ -111,6 +111,7 @@ extern "C" const char *exg_parse_error_string(uint32_t code) {
         case EXG_PE_GTF_STRAND: return "invalid GTF strand";
         case EXG_PE_GTF_FRAME: return "invalid GTF frame";
         case EXG_PE_GTF_ATTRIBUTES: return "invalid GTF attributes";
+        case EXG_PE_GFF_ATTRIBUTES: return "invalid GFF attribute";
         default: return "unknown parse error";
     }
 }

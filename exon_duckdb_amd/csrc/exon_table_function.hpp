@@ -48,6 +48,7 @@
 #include "exon_gpu.h"
 #include "exg_alignfn.hpp"
 #include "exg_cigarfn.hpp"
+#include "exg_gffattr.hpp"
 #include "exg_seqfn.hpp"
 
 namespace exon_scan {
@@ -590,6 +591,38 @@ static inline CigarStatus ExtractFromCigar(size_t sequence_length, const char *c
 static inline std::string ParseCigarErrorText(const char *s, size_t n) { return std::string(exg::cigarfn::kInvalidText) + ": " + std::string(s, n); }
 static inline std::string ExtractFromCigarErrorText(const CigarStatus &st) {
     return st.code == EXG_PE_CIGAR_RANGE ? exg::cigarfn::kRangeText : exg::cigarfn::kInvalidText;
+}
+
+// gff_parse_attributes (exon/src/exon/gff_functions/module.cpp:29-84): the per-row work of the SQL scalar the shim registers, on
+// the rules of exg_gffattr.hpp (exg_gff_attributes is the same on a column that is still in HBM).  Keys and values are slices
+// of the field: offsets and lengths.  A status instead of an exception, like ParseCigar.
+struct GffAttribute {
+    uint64_t key_start, key_len, value_start, value_len;
+};
+struct GffAttributeStatus {
+    uint32_t code = EXG_PE_NONE;  // EXG_PE_GFF_ATTRIBUTES (EXG_PE_FIELD_TOO_LONG: a field of 2^32 - 1 bytes and more)
+    uint64_t offset = 0;          // of the failing segment behind its trim (exg_gffattr.hpp, R6)
+    uint64_t length = 0;          // its length behind the trim
+};
+// the entries of s[0, n) into *out (emptied first), in field order
+static inline GffAttributeStatus GffParseAttributes(const char *s, size_t n, std::vector<GffAttribute> *out) {
+    namespace ga = exg::gffattr;
+    GffAttributeStatus st;
+    out->clear();
+    if (n >= 0xFFFFFFFFull) {
+        st.code = EXG_PE_FIELD_TOO_LONG;
+        return st;
+    }
+    const ga::Verdict v = ga::parse_field(reinterpret_cast<const uint8_t *>(s), (uint32_t)n, [out](uint32_t k, uint32_t kn, uint32_t val, uint32_t vn) {
+        out->push_back(GffAttribute{k, kn, val, vn});
+    });
+    if (v.kind == ga::kError) st.code = EXG_PE_GFF_ATTRIBUTES, st.offset = v.a, st.length = v.b;
+    return st;
+}
+// the exception's text: the reference's (module.cpp:61), around the segment behind its trim
+static inline std::string GffAttributeErrorText(const char *s, const GffAttributeStatus &st) {
+    if (st.code != EXG_PE_GFF_ATTRIBUTES) return "gff_parse_attributes: the field is longer than 2^32 - 2 bytes";
+    return std::string(exg::gffattr::kInvalidHead) + std::string(s + st.offset, (size_t)st.length) + exg::gffattr::kInvalidTail;
 }
 
 // exon/src/exon_extension.cpp:47-58: the registrations of the path (+ the read_vcf alias the north star names)

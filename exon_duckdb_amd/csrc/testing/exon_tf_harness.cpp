@@ -369,6 +369,31 @@ extern "C" int exon_tf_parse_cigar_batch(const char *bytes, const uint64_t *off,
     *total_ops = total, *len_sum = sum;
     return EXG_OK;
 }
+// gff_parse_attributes as the shim registers it (gff_functions/module.cpp:29-84): entry k of the field as spans[4 k ..] =
+// (key_start, key_len, value_start, value_len), *n_entries of them.  0; EXG_E_CAPACITY when cap (entries) is too small
+// (*n_entries = what it takes); EXG_E_PARSE with *code, the failing segment's *offset and *length and the exception's text in err
+extern "C" int exon_tf_gff_parse_attributes(const char *s, uint64_t n, uint64_t *spans, uint64_t cap, uint64_t *n_entries, uint32_t *code,
+                                            uint64_t *offset, uint64_t *length, char *err, uint64_t err_cap) {
+    if (err_cap) err[0] = 0;
+    *code = 0, *offset = 0, *length = 0, *n_entries = 0;
+    std::vector<exon_scan::GffAttribute> list;
+    const exon_scan::GffAttributeStatus st = exon_scan::GffParseAttributes(s, (size_t)n, &list);
+    if (st.code) {
+        *code = st.code, *offset = st.offset, *length = st.length;
+        const std::string text = exon_scan::GffAttributeErrorText(s, st);
+        if (err_cap) {
+            const size_t take = text.size() < (size_t)err_cap - 1 ? text.size() : (size_t)err_cap - 1;  // (the segment may hold NUL bytes)
+            memcpy(err, text.data(), take);
+            err[take] = 0;
+        }
+        return EXG_E_PARSE;
+    }
+    *n_entries = list.size();
+    if (list.size() > cap) return EXG_E_CAPACITY;
+    for (size_t k = 0; k < list.size(); k++)
+        spans[4 * k] = list[k].key_start, spans[4 * k + 1] = list[k].key_len, spans[4 * k + 2] = list[k].value_start, spans[4 * k + 3] = list[k].value_len;
+    return EXG_OK;
+}
 // is_segmented .. is_supplementary (which = 0 .. 11) of an INTEGER flag; -1 for an unknown predicate
 extern "C" int exon_tf_sam_flag(uint32_t which, int32_t flag) {
     return which < (uint32_t)exg::seqfn::kSamFlagCount ? (exon_scan::SamFlag(which, flag) ? 1 : 0) : -1;

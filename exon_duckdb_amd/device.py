@@ -734,6 +734,52 @@ def gtf_attributes(strings, n_rows, payload, payload_base, entries_capacity=None
     return entries[:n_rows], keys[:k], values[:k], bases, r
 
 
+def gff_attributes(strings, n_rows, payload, payload_base, entries_capacity=None, row_map=None, chunk_rows=0):
+    """exg_gff_attributes (gff_parse_attributes, reference gff_functions/module.cpp:29-84) on a column of GFF3 ninth fields that
+    is still in HBM: arguments and return value are gtf_attributes' — (entries [n_rows, 2] int64 = list_entry_t {offset, length},
+    keys [total, 2] int64, values [total, 2] int64 — string_t slices of the same payload —, chunk_base or None, result).
+    entries_capacity=None is the two-call form.  An invalid row raises ExgError; the result block rides on it as .result
+    (error_row, error_offset and error_length: the failing segment behind its trim)."""
+    torch = _torch()
+    lib = load_library()
+    dev = strings.device
+    a = abi.GffAttributesArgs()
+    a.d_strings = strings.data_ptr()
+    a.d_payload = payload.data_ptr() if payload is not None else None
+    a.payload_base = payload_base
+    a.d_row_map = row_map.data_ptr() if row_map is not None else None
+    a.n_rows = n_rows
+    ws_bytes = int(lib.exg_gff_attributes_workspace_bytes(n_rows))
+    ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.int64, device=dev)
+    result = torch.empty(8, dtype=torch.int64, device=dev)
+    a.d_workspace, a.workspace_bytes, a.d_result, a.stream = ws.data_ptr(), ws_bytes, result.data_ptr(), stream_ptr().value
+
+    def call():
+        check(lib.exg_gff_attributes(C.byref(a)))
+        r = abi.GffAttributesResult()
+        rc = lib.exg_gff_attributes_result(C.c_void_p(result.data_ptr()), stream_ptr(), C.byref(r))
+        if rc != 0:
+            try:
+                check(rc)
+            except ExgError as e:
+                e.result = r
+                raise
+        return r
+
+    if entries_capacity is None:
+        entries_capacity = int(call().total_entries)
+    cap = int(entries_capacity)
+    entries = torch.zeros((max(n_rows, 1), 2), dtype=torch.int64, device=dev)
+    keys = torch.zeros((max(cap, 1), 2), dtype=torch.int64, device=dev)
+    values = torch.zeros((max(cap, 1), 2), dtype=torch.int64, device=dev)
+    bases = torch.zeros(((n_rows + chunk_rows - 1) // chunk_rows + 1,), dtype=torch.int64, device=dev) if chunk_rows else None
+    a.d_out_entries, a.d_out_keys, a.d_out_values, a.entries_capacity = entries.data_ptr(), keys.data_ptr(), values.data_ptr(), cap
+    a.chunk_rows, a.d_out_chunk_base = chunk_rows, bases.data_ptr() if chunk_rows else None
+    r = call()
+    k = min(int(r.total_entries), cap) if not (r.flags & abi.EXG_RF_CAPACITY) else 0
+    return entries[:n_rows], keys[:k], values[:k], bases, r
+
+
 class BcfToVcf:
     """exg_bcf_to_vcf on decoded BCF records resident in HBM (d_input[0] is a record start): the two dictionaries as lists indexed
     by dictionary index (bytes, or None where no ID has that index), the header's sample count, an output buffer of

@@ -496,6 +496,27 @@ def extract_from_cigar(sequence, cigar):
     return {"sequence_start": start.value, "sequence_end": end.value, "sequence": sequence[start.value:end.value]}
 
 
+def gff_parse_attributes(s):
+    """the SQL scalar gff_parse_attributes(VARCHAR) -> MAP(VARCHAR, VARCHAR) as the DuckDB shim registers it (reference
+    gff_functions/module.cpp:29-84) -> list of (key, value) in field order, a repeated key being a second entry; NULL in, NULL
+    out; a segment that is not key=value raises ExgError with the reference's text `Invalid attribute: '<segment>' expected
+    'key=value;key2=value2'` (.parse_code, .offset, .length: the rule of csrc/exg_gffattr.hpp)"""
+    if s is None:
+        return None
+    cap = max(1, len(s) // 3 + 1)
+    spans = (C.c_uint64 * (4 * cap))()
+    n, code, offset, length = C.c_uint64(0), C.c_uint32(0), C.c_uint64(0), C.c_uint64(0)
+    err = C.create_string_buffer(len(s) + 64)
+    rc = _lib().exon_tf_gff_parse_attributes(s, len(s), spans, cap, C.byref(n), C.byref(code), C.byref(offset), C.byref(length), err, len(err))
+    if rc != 0:
+        # (a segment may hold NUL bytes: the text is 20 bytes, the segment, 34 bytes)
+        text = err.raw[:20 + length.value + 34] if code.value == abi.EXG_PE_GFF_ATTRIBUTES else err.value
+        e = ExgError(rc, text.decode("latin-1"))
+        e.parse_code, e.offset, e.length = code.value, offset.value, length.value
+        raise e
+    return [(s[spans[4 * k]:spans[4 * k] + spans[4 * k + 1]], s[spans[4 * k + 2]:spans[4 * k + 2] + spans[4 * k + 3]]) for k in range(n.value)]
+
+
 #: the SAM flag predicates in the reference's order (sam_functions/module.cpp:143-154): bit k of (uint16_t)flag
 SAM_FLAG_FUNCTIONS = ("is_segmented", "is_properly_aligned", "is_unmapped", "is_mate_unmapped", "is_reverse_complemented",
                       "is_mate_reverse_complemented", "is_first_segment", "is_last_segment", "is_secondary",

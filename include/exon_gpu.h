@@ -46,7 +46,8 @@ extern "C" {
 /* 9 still: read_bed_file (EXG_FMT_BED, exg_bed_scan, EXG_PE_BED_*), the sequence scalars (exg_sequence_op,
  * EXG_SEQ_*, EXG_PE_SEQ_*), the alignment scores (exg_align_score, EXG_PE_ALIGN_TOO_LONG) and read_sam_file_records
  * (EXG_FMT_SAM, exg_sam_scan, EXG_PE_SAM_*), the CIGAR scalars (exg_cigar_op, EXG_CIGAR_*, EXG_PE_CIGAR_*) and the alignment
- * strings (exg_align_string; no new error code) are pure additions — no existing struct, constant or entry point changed. */
+ * strings (exg_align_string; no new error code) and the GFF attributes (exg_gff_attributes, EXG_PE_GFF_ATTRIBUTES) are pure
+ * additions — no existing struct, constant or entry point changed. */
 #define EXG_ABI_VERSION 9
 
 /* DuckDB v0.8.1 STANDARD_VECTOR_SIZE; the reference asks the Rust side for
@@ -132,6 +133,9 @@ extern "C" {
 #define EXG_PE_GTF_FRAME 62           /* GTF: frame is not `0`, `1`, `2` or `.` */
 #define EXG_PE_GTF_ATTRIBUTES 63      /* GTF (exg_gtf_attributes): an entry without a value, an unterminated quote, a quote that does
                                        * not begin a value, or bytes behind a closing quote other than spaces and `;` */
+/* (64 stays unassigned, like 29, 34, 43, 46 and 56: callers probe it to see "unknown parse error") */
+#define EXG_PE_GFF_ATTRIBUTES 65      /* GFF (exg_gff_attributes, gff_parse_attributes): a segment between `;` that is not
+                                       * key=value behind its trim — no `=`, no key, no value, a third piece — or an empty field */
 
 /* ---- duckdb::string_t, bit-for-bit (v0.8.1 duckdb/common/types/string_type.hpp)
  * length <= 12: bytes inlined, zero padded.  Otherwise 4-byte prefix + pointer.
@@ -842,6 +846,58 @@ int exg_gtf_attributes(const exg_gtf_attributes_args *args);
 /* Synchronising copy of the 64-byte result to the host.  error_code != 0: EXG_E_PARSE, and the thread's last error message is
  * `Invalid GTF attributes in row <r> at byte <k>`; *out is filled either way. */
 int exg_gtf_attributes_result(const struct exg_gtf_attributes_result *d_result, void *stream, struct exg_gtf_attributes_result *out);
+
+/* ---- GFF attributes on a device-resident column -------------------------------------------------------------
+ * gff_parse_attributes(VARCHAR) -> MAP(VARCHAR, VARCHAR) (reference exon/src/exon/gff_functions/module.cpp:29-84) on a column
+ * of GFF3 ninth fields (column 8 of exg_gtf_scan over a GFF3 file — the eight leading columns are the same —, or any
+ * exg_string_t column): for row j of the call (row d_row_map[j] of the column when a row map is given) the entries key=value of
+ * the field in field order, a repeated key being a second entry.  The grammar is INTEGRATION.md's (GFF attributes): the field is
+ * cut at every `;` and segments of zero bytes are dropped; a segment loses its leading and trailing ' ' \t \n \v \f \r, is cut
+ * at every `=`, pieces of zero bytes are dropped, and exactly two pieces must remain — neither trimmed on its own, nothing
+ * percent-decoded.  Keys and values are zero-copy slices of the input's bytes under the same payload_base (up to 12 bytes
+ * inlined; a token of an inlined row is inlined): there is no output payload.
+ * The arguments are exg_gtf_attributes_args' field for field — d_out_entries, chunk_rows / d_out_chunk_base, the capacity
+ * protocol (total_entries > entries_capacity: EXG_RF_CAPACITY, neither child is touched, total_entries is exact when no row
+ * fails and the rows are validated all the same; entries_capacity = 0 with NULL children is the counting call) — so a reader
+ * can feed either op.
+ * Errors: the lowest failing row wins, in it the leftmost failing segment: error_offset = the offset in the field of the
+ * segment's first byte behind the trim (of the segment's first byte when the trim leaves nothing), error_length = its length
+ * behind the trim; a field without any segment (empty, or `;` only) fails as a whole: offset 0, its length.  With an error the
+ * result block is exact and the outputs are unspecified.  A wavefront takes a row, 64 bytes a step.
+ * Deterministic; no host round trip between the passes; n_rows = 0 is valid; n_rows < 2^32 - 1. */
+struct exg_gff_attributes_result { /* 64 bytes, written by the device */
+    uint64_t total_entries; /* entries of all rows */
+    uint64_t error_row;     /* lowest failing row (an index of the call's rows) */
+    uint64_t error_offset;  /* byte offset in that row's field */
+    uint64_t n_rows;
+    uint32_t error_code;    /* 0 or EXG_PE_GFF_ATTRIBUTES */
+    uint32_t flags;         /* EXG_RF_CAPACITY: total_entries > entries_capacity, no child was written */
+    uint32_t error_length;  /* bytes of the failing segment behind its trim */
+    uint8_t pad[20];
+};
+typedef struct exg_gff_attributes_args {
+    const exg_string_t *d_strings;   /* device, 16-byte aligned */
+    const void *d_payload;           /* device bytes the non-inlined strings point into */
+    uint64_t payload_base;           /* string_t.ptr - payload_base = byte offset in d_payload */
+    const uint32_t *d_row_map;       /* optional: device, n_rows row numbers of d_strings (NULL: rows 0 .. n_rows - 1) */
+    uint64_t n_rows;
+    uint64_t chunk_rows;             /* 0, or rows per chunk (list offsets relative to the chunk's first entry) */
+    exg_list_entry_t *d_out_entries; /* out: device, 8-byte aligned, n_rows entries (may be NULL in the counting call) */
+    uint64_t *d_out_chunk_base;      /* out: device, ceil(n_rows / chunk_rows) + 1 words; NULL when chunk_rows is 0 */
+    exg_string_t *d_out_keys;        /* out: device, 16-byte aligned, entries_capacity entries */
+    exg_string_t *d_out_values;      /* out: device, 16-byte aligned, entries_capacity entries */
+    uint64_t entries_capacity;
+    void *d_workspace;               /* device, 8-byte aligned, exg_gff_attributes_workspace_bytes(n_rows) */
+    uint64_t workspace_bytes;
+    struct exg_gff_attributes_result *d_result; /* device, 64 bytes, 8-byte aligned */
+    void *stream;
+} exg_gff_attributes_args;
+uint64_t exg_gff_attributes_workspace_bytes(uint64_t n_rows);
+/* Enqueue on args->stream; asynchronous. */
+int exg_gff_attributes(const exg_gff_attributes_args *args);
+/* Synchronising copy of the 64-byte result to the host.  error_code != 0: EXG_E_PARSE, and the thread's last error message is
+ * `Invalid GFF attribute in row <r> at byte <k>`; *out is filled either way. */
+int exg_gff_attributes_result(const struct exg_gff_attributes_result *d_result, void *stream, struct exg_gff_attributes_result *out);
 
 /* ---- device inflate (gzip / BGZF members; replaces flate2 behind rust/src/arrow_reader.rs:60-91) ---- */
 typedef struct exg_inflate_member {

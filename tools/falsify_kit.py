@@ -8,6 +8,7 @@ file itself) and the SCHEMA rules (column names and types: `DESCRIBE SELECT * FR
     python tools/falsify_kit.py kit/              # here (needs only the oracle): kit/cases/*, kit/expected/*, kit/run.sh
     cd kit && DUCKDB=/path/to/duckdb ./run.sh     # on a machine with DuckDB v0.8.1 + the reference's exon.duckdb_extension
     python compare.py                             # -> one line per case: SAME / DIFFERENT (+ what differs); exit 1 on any
+    python compare_scalars.py                     # the same for the scalar cases (gff_parse_attributes: scalar_cases.json)
 
 Nothing of the reference travels anywhere: the kit holds inputs made by this repository's tests and this repository's oracle's
 rows.  A DIFFERENT line names a rule of tests/test_oracle_rules.py to fix in the oracle (the GPU path follows the oracle
@@ -108,6 +109,34 @@ def expected_of(o, fmt, data, compression=None):
     return jsonable(rows), err
 
 
+#: gff_parse_attributes: the rules of INTEGRATION.md (GFF attributes) that no test of the reference pins — [RECALLED] from DuckDB's
+#: StringUtil (Split pushes the input when it finds nothing; Trim leaves bytes >= 0x80) or [DECIDED] here — beside two that are
+#: pinned.  The arguments are SQL string literals: no quote, `$`, backslash or backtick in them.
+GFF_ATTRIBUTE_CASES = [("empty_field", ""), ("semicolon_only", ";"), ("double_equals", "a==b"), ("inner_blanks_stay", " a = b "),
+                       ("repeated_key", "a=1;a=2"), ("nbsp_at_segment_end", "a=b\u00a0"), ("nbsp_at_segment_start", "\u00a0a=b\u00a0;c=d"),
+                       ("blank_segment", "a=b; ;c=d"), ("trailing_equals", "a=b="), ("pinned_trailing_semicolon", "key=value;"),
+                       ("pinned_no_equals", "ID")]
+
+
+def gff_attribute_cases(out):
+    """scalar cases: no input file, one statement each; map_keys / map_values keep the order of the entries and print as JSON lists"""
+    import gff_attr_ref as R
+    scalars = []
+    for name, arg in GFF_ATTRIBUTE_CASES:
+        case = f"gff_parse_attributes_{name}"
+        res = R.outcome(arg.encode("utf-8"))
+        rows, err = [], None
+        if res[0] == "ok":
+            rows = [{"keys": [k.decode("utf-8") for k, _ in res[1]], "values": [v.decode("utf-8") for _, v in res[1]]}]
+        else:
+            err = R.error_text(arg.encode("utf-8")[res[1]:res[1] + res[2]])
+        with open(os.path.join(out, "expected", f"{case}.json"), "w") as f:
+            json.dump({"rows": rows, "error": err}, f, indent=1, sort_keys=True)
+        sql = f"SELECT map_keys(m) AS keys, map_values(m) AS \\\"values\\\" FROM (SELECT gff_parse_attributes('{arg}') AS m)"
+        scalars.append({"test": "gff_parse_attributes_rules", "case": case, "format": "scalar", "sql": sql})
+    return scalars
+
+
 def main():
     out = sys.argv[1] if len(sys.argv) > 1 else "kit"
     from oracle import pyoracle
@@ -167,6 +196,12 @@ def main():
         cases.append(sc)
     with open(os.path.join(out, "cases.json"), "w") as f:
         json.dump(cases, f, indent=1)
+    # scalar cases (no input file): a list and a compare script of their own beside the file cases'
+    scalars = gff_attribute_cases(out)
+    with open(os.path.join(out, "scalar_cases.json"), "w") as f:
+        json.dump(scalars, f, indent=1)
+    with open(os.path.join(out, "compare_scalars.py"), "w") as f:
+        f.write(COMPARE.replace('"cases.json"', '"scalar_cases.json"'))
     fn_of = {"fastq": "read_fastq", "fasta": "read_fasta", "vcf": "read_vcf_file_records"}
     with open(os.path.join(out, "run.sh"), "w") as f:
         f.write("#!/bin/sh\n# one DuckDB invocation per case (an error must not end the others); DUCKDB = the CLI of a build with the exon extension\n"
@@ -179,12 +214,15 @@ def main():
                 continue
             sql = (f"LOAD exon; COPY (SELECT * FROM {fn_of[c['format']]}({arg})) TO 'got/{c['case']}.json' (FORMAT JSON);")
             f.write(f"$DUCKDB -unsigned -c \"{sql}\" > got/{c['case']}.log 2>&1 || cp got/{c['case']}.log got/{c['case']}.err\n")
+        for c in scalars:
+            sql = f"LOAD exon; COPY ({c['sql']}) TO 'got/{c['case']}.json' (FORMAT JSON);"
+            f.write(f"$DUCKDB -unsigned -c \"{sql}\" > got/{c['case']}.log 2>&1 || cp got/{c['case']}.log got/{c['case']}.err\n")
     os.chmod(os.path.join(out, "run.sh"), 0o755)
     with open(os.path.join(out, "compare.py"), "w") as f:
         f.write(COMPARE)
     n_dec = sum(1 for c in cases if not c.get("schema") and c["file"].rsplit(".", 1)[-1] not in ("fastq", "fasta", "vcf") or c.get("compression"))
     print(f"{len(cases)} cases of {len(set(c['test'] for c in cases))} rule tests ({n_dec} decoder-level, {sum(1 for c in cases if c.get('schema'))} schema) "
-          f"-> {out}/ (cases/, expected/, run.sh, compare.py)")
+          f"+ {len(scalars)} scalar cases -> {out}/ (cases/, expected/, run.sh, compare.py, compare_scalars.py)")
 
 
 COMPARE = r'''#!/usr/bin/env python3
