@@ -196,7 +196,8 @@ STRINGS = [b"", b"a", b"ab", b"abc", b"b", b"B", b"\x80", b"a\xff", b"a\x7f", b"
 BIGINTS = [0, 1, -1, 5, 2 ** 31, -2 ** 31 - 1, 2 ** 53, 2 ** 53 + 1, 2 ** 53 - 1, -2 ** 63, 2 ** 63 - 1, 1000]
 INTS = [0, 1, -1, 5, 99, 2 ** 31 - 1, -2 ** 31, 1000]
 NAN = float("nan")
-FLOATS = [0.0, -0.0, fo.f32(0.1), 0.5, fo.f32(1e-45), fo.f32(3.4028235e38), float("inf"), float("-inf"), NAN, 16777216.0, 50.5, -1.5, fo.f32(0.3)]
+FLOATS = [0.0, -0.0, fo.f32(0.1), 0.5, fo.f32(1e-45), fo.f32(3.4028235e38), float("inf"), float("-inf"), NAN, 16777216.0, 50.5, -1.5, fo.f32(0.3),
+          fo.f32(-0.1), fo.f32(-1e-45), fo.f32(-3.4028235e38)]
 LITERALS = {
     "s": STRINGS,
     "n": [str(v) for v in BIGINTS] + ["0.5", "1e3", "9007199254740992.0", "9007199254740993.0", "5.", "-0.5", "2147483648.5"],

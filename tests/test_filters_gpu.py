@@ -158,20 +158,24 @@ def bam_raw():
 class Site:
     """one file and the ways to read it"""
 
-    def __init__(self, path, fmt, fn, names, flat, schema, rows, literals):
+    def __init__(self, path, fmt, fn, names, flat, schema, rows, literals, beside=()):
+        """flat: the filterable columns; beside: columns that are read and compared with them but never named in a filter (GTF's
+        `attributes`: the rows' dicts carry them)"""
         self.path, self.fmt, self.fn, self.flat, self.schema, self.rows, self.literals = str(path), fmt, fn, flat, schema, rows, literals
         self.names = list(names)                                       # every column of the format, in schema order
+        self.read = list(flat) + list(beside)                          # what a read without `columns` compares
         self.nullable = {c for c in flat if any(r[c] is None for r in rows)}
         self._rel = None
 
     def want(self, tree, columns=None):
-        cols = self.flat if columns is None else columns
+        cols = self.read if columns is None else columns
         return norm_rows([tuple(r[c] for c in cols) for r in self.rows if fo.keep(tree, r, self.schema)])
 
-    def shard_rows(self, text, columns=None):
+    def shard_rows(self, text, columns=None, **kw):
+        """kw: passed on to ShardReader (compression, shard_index, shard_count)"""
         from exon_duckdb_amd.reader import ShardReader
-        idx = [self.names.index(c) for c in (self.flat if columns is None else columns)]
-        r = ShardReader(self.path, self.fmt, filters=text, columns=idx)
+        idx = [self.names.index(c) for c in (self.read if columns is None else columns)]
+        r = ShardReader(self.path, self.fmt, filters=text, columns=idx, **kw)
         try:
             got = r.rows()
         finally:
@@ -179,9 +183,9 @@ class Site:
         at = [sorted(idx).index(i) for i in idx]                       # rows() yields the projected columns in schema order
         return norm_rows([tuple(row[k] for k in at) for row in got])
 
-    def shard_count(self, text):
+    def shard_count(self, text, **kw):
         from exon_duckdb_amd.reader import ShardReader
-        r = ShardReader(self.path, self.fmt, filters=text)
+        r = ShardReader(self.path, self.fmt, filters=text, **kw)
         try:
             return r.count()
         finally:
@@ -190,7 +194,7 @@ class Site:
     def arrow_rows(self, text):
         from exon_duckdb_amd.arrow import new_reader
         tab = new_reader(self.path, self.fmt, filters=text).read_all()
-        cols = [tab.column(c).to_pylist() for c in self.flat]
+        cols = [tab.column(c).to_pylist() for c in self.read]
         return norm_rows(list(zip(*cols)))
 
     @property
@@ -201,7 +205,7 @@ class Site:
         return self._rel
 
     def tf_rows(self, filters, columns=None):
-        return norm_rows(self.rel.fetchall(columns=self.flat if columns is None else columns, filters=filters))
+        return norm_rows(self.rel.fetchall(columns=self.read if columns is None else columns, filters=filters))
 
 
 def sql(tree):
@@ -319,7 +323,7 @@ def check_trees(site, trees, read, shard=True):
         text, named = sql(t), fo.columns_of(t)
         want = site.want(t)
         assert read(text) == want, text
-        proj = [c for c in site.flat if c not in named]
+        proj = [c for c in site.read if c not in named]
         if shard:
             assert site.shard_count(text) == len(want), text
             if proj:
