@@ -188,7 +188,9 @@ static unique_ptr<FunctionData> FileTypeBind(ClientContext &, TableFunctionBindI
 	}
 	std::vector<LogicalType> types;
 	std::vector<std::string> col_names;
-	auto result = TF::Bind(input.inputs[0].GetValue<string>(), compression, info.file_type, types, col_names);
+	// vcf_query(path, region): the second positional argument
+	const string region = input.inputs.size() > 1 ? input.inputs[1].GetValue<string>() : string();
+	auto result = TF::Bind(input.inputs[0].GetValue<string>(), compression, info.file_type, types, col_names, region);
 	for (auto &t : types) {
 		return_types.push_back(t);
 	}
@@ -229,10 +231,17 @@ static unique_ptr<NodeStatistics> Cardinality(ClientContext &, const FunctionDat
 }
 
 // module.cpp:296-318
-static void Register(const string &name, const string &file_type, DatabaseInstance &db) {
-	TableFunction scan(name, {LogicalType::VARCHAR}, Scan, FileTypeBind, InitGlobal, InitLocal);
+// region: the function takes (VARCHAR path, VARCHAR region) — exon_extension.cpp:75-77
+static void Register(const string &name, const string &file_type, DatabaseInstance &db, bool region = false) {
+	vector<LogicalType> arguments = {LogicalType::VARCHAR};
+	if (region) {
+		arguments.push_back(LogicalType::VARCHAR);
+	}
+	TableFunction scan(name, arguments, Scan, FileTypeBind, InitGlobal, InitLocal);
+	if (!region) {
+		scan.named_parameters["compression"] = LogicalType::VARCHAR;
+	}
 	scan.function_info = make_shared<WTArrowTableScanInfo>(file_type);
-	scan.named_parameters["compression"] = LogicalType::VARCHAR;
 	scan.cardinality = Cardinality;
 	scan.get_batch_index = GetBatchIndex;
 	scan.projection_pushdown = true;
@@ -640,6 +649,9 @@ static void RegisterScalars(DatabaseInstance &db) {
 static void LoadInternal(DatabaseInstance &db) {
 	for (const auto &reg : exon_scan::kRegistrations) {
 		Register(reg.name, reg.file_type, db);
+	}
+	for (const auto &reg : exon_scan::kRegionRegistrations) { // vcf_query(path, region)
+		Register(reg.name, reg.file_type, db, true);
 	}
 	RegisterScalars(db);
 	// exon_extension.cpp:60 (FastqFunctions::GetQualityScoreStringToList)

@@ -489,6 +489,23 @@ class OpenArgs(C.Structure):
                 ("shard_index", C.c_uint32), ("shard_count", C.c_uint32), ("columns", C.c_uint64), ("flags", C.c_uint64)]
 
 
+class VirtualChunk(C.Structure):
+    _fields_ = [("begin", C.c_uint64), ("end", C.c_uint64)]
+
+
+class Region(C.Structure):
+    _fields_ = [("start", C.c_int64), ("end", C.c_int64), ("ref_id", C.c_uint32), ("name_len", C.c_uint32), ("name", C.c_char * 256)]
+
+
+class VcfRegionArgs(C.Structure):
+    _fields_ = [("d_chrom", C.c_void_p), ("d_ref", C.c_void_p), ("d_pos", C.c_void_p), ("d_info", C.c_void_p), ("d_payload", C.c_void_p),
+                ("payload_base", C.c_uint64), ("n_rows", C.c_uint64), ("d_name", C.c_void_p), ("name_len", C.c_uint32), ("reserved", C.c_uint32),
+                ("start", C.c_int64), ("end", C.c_int64), ("d_keep", C.c_void_p), ("stream", C.c_void_p)]
+
+
+REGION_UNBOUNDED = (1 << 63) - 1
+
+
 class BcfToVcfResult(C.Structure):
     _fields_ = [("n_records", C.c_uint64), ("consumed_bytes", C.c_uint64), ("text_bytes_needed", C.c_uint64), ("text_bytes", C.c_uint64),
                 ("error_record", C.c_uint64), ("error_offset", C.c_uint64), ("error_code", C.c_uint32), ("flags", C.c_uint32),
@@ -557,6 +574,10 @@ SIGNATURES = {
     "exg_cigar_op": (C.c_int, [C.POINTER(CigarOpArgs)]),
     "exg_cigar_result": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(CigarResult)]),
     "exg_plan_shards": (C.c_int, [C.POINTER(OpenArgs), C.POINTER(C.c_uint32), C.POINTER(C.c_int), C.c_uint32]),
+    "exg_vcf_region_keep": (C.c_int, [C.POINTER(VcfRegionArgs)]),
+    "exg_tabix_query": (C.c_int, [C.c_char_p, C.c_uint64, C.c_char_p, C.POINTER(VirtualChunk), C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(Region)]),
+    "exg_open_region": (C.c_int, [C.POINTER(OpenArgs), C.c_char_p, C.POINTER(C.c_void_p)]),
+    "exg_vcf_query_reader": (C.c_void_p, [C.c_void_p, C.c_char_p, C.c_char_p, C.c_size_t]),
 }
 
 

@@ -14,6 +14,7 @@
 
 #include "exg_emit.hpp"
 #include "exg_filter.hpp"
+#include "exg_rd_region.hpp"
 #include "exg_vcf_header.hpp"
 
 namespace exg_rd {
@@ -198,7 +199,8 @@ ea::StrCol str_col(exg_reader *r, const ScanCtx &ctx, int c) {
     return sc;
 }
 
-// the `filters` program over the scan's rows: em.n becomes the rows that pass, em.d_row_map where they are
+// the `filters` program over the scan's rows: em.n becomes the rows that pass, em.d_row_map where they are.  A region reader
+// (vcf_query_reader): the rows that overlap the region, ANDed with the program when there is one
 int select_rows(Emit &em, const ScanCtx &ctx) {
     exg_reader *r = em.r;
     ea::FilterCols fc;
@@ -217,9 +219,12 @@ int select_rows(Emit &em, const ScanCtx &ctx) {
     uint32_t *d_map = (uint32_t *)em.dalloc(em.n * 4 + 4);
     if (em.rc) return em.rc;
     ea::FilterCols *d_fc = (ea::FilterCols *)em.dalloc(sizeof fc);
+    uint64_t *d_keep = r->region ? (uint64_t *)em.dalloc((em.n + 63) / 64 * 8) : nullptr;
     if (em.rc) return em.rc;
-    EM_HIP(ea::select_rows(fc, (const ea::FilterProgram *)em.st->d_prog, (const uint8_t *)em.st->d_consts, ctx.n_records, d_goff, d_tmp, d_map, d_fc,
-                           r->stream, &em.n));
+    if (d_keep)
+        if (int rc = exg_rd::region_keep(r, ctx.d_input, (uint64_t)(uintptr_t)ctx.h, ctx.n_records, d_keep)) return rc;
+    EM_HIP(ea::select_rows(fc, em.st->has_filter ? (const ea::FilterProgram *)em.st->d_prog : nullptr, (const uint8_t *)em.st->d_consts, ctx.n_records, d_goff,
+                           d_tmp, d_map, d_fc, r->stream, &em.n, d_keep));
     em.d_row_map = d_map;
     return EXG_OK;
 }
@@ -388,7 +393,7 @@ int arrow_emit(exg_reader *r, const ScanCtx &ctx) {
     batch->host.reserve(st->host_hint);
     Emit em(r, st, &batch->host, ctx.n_records, nullptr);
     em.lazy = lazy;
-    if (st->has_filter)
+    if (st->has_filter || r->region)
         if (int rc = select_rows(em, ctx)) return rc;
     if (em.n == 0) {
         st->produced.reset();
@@ -512,10 +517,11 @@ ReaderResult result_error(const std::string &msg) {
 }
 
 // A reader in Arrow mode + its stream state: schema (VCF: from the first file's header), the `filters` program, the
-// emitter.  shard_index / shard_count / device of `oa` make it the reader of one stripe of a fan-out.
-int build_stream(const exg_open_args &oa, const char *filters, std::shared_ptr<StreamState> *out, std::string *err) {
+// emitter.  shard_index / shard_count / device of `oa` make it the reader of one stripe of a fan-out.  region (NULL: none): the
+// reader is a region reader (exg_open_region)
+int build_stream(const exg_open_args &oa, const char *filters, std::shared_ptr<StreamState> *out, std::string *err, const char *region = nullptr) {
     exg_reader *r = nullptr;
-    int rc = exg_open(&oa, &r);
+    int rc = region ? exg_open_region(&oa, region, &r) : exg_open(&oa, &r);
     if (rc) {
         std::string m = exg_last_error_message();
         // arrow_reader.rs:93-102 / :118-123
@@ -696,4 +702,26 @@ extern "C" ReaderResult new_reader(ArrowArrayStream *stream_ptr, const char *uri
     ReaderResult ok;
     ok.error = nullptr;
     return ok;
+}
+
+// what vcf_query_reader (include/exon_gpu.h; exon/include/rust.hpp:60-63, rust/src/vcf_query_reader.rs:31-36) calls: new_reader's
+// VCF stream over a region reader.  One reader, one device: the members an index selects are not worth a fan-out
+extern "C" const char *exg_vcf_query_reader(ArrowArrayStream *stream_ptr, const char *uri, const char *query, uintptr_t batch_size) {
+    auto failed = [&](const std::string &msg) -> const char * { return strdup(msg.c_str()); };
+    if (!stream_ptr || !uri || !query) return failed("vcf_query_reader: null argument");
+    exg_open_args oa;
+    memset(&oa, 0, sizeof oa);
+    oa.path = uri;
+    oa.file_format = "vcf";
+    oa.batch_rows = batch_size;
+    oa.shard_count = 1;
+    std::shared_ptr<StreamState> st;
+    std::string err;
+    if (build_stream(oa, nullptr, &st, &err, query)) return failed(err.rfind("could not register table: ", 0) == 0 ? "could not read VCF file: " + err.substr(26) : err);
+    stream_ptr->get_schema = stream_get_schema;
+    stream_ptr->get_next = stream_get_next;
+    stream_ptr->get_last_error = stream_last_error;
+    stream_ptr->release = stream_release;
+    stream_ptr->private_data = st.get();
+    return nullptr;
 }

@@ -19,6 +19,7 @@
 #include "exg_filter.hpp"
 #include "exg_map_guard.hpp"
 #include "exg_rd_bam.hpp"
+#include "exg_rd_region.hpp"
 #include "exg_rd_source.hpp"
 #include "exg_rd_stages.hpp"
 
@@ -115,8 +116,9 @@ int ensure_device(exg_reader *r, uint64_t need_bytes) {
         if ((arc = r->dev_alloc(&r->d_valid_spare[k], validity_bytes))) return arc;
     if (r->format == EXG_FMT_FASTA && (arc = r->dev_alloc(&r->d_payload, cap + 64))) return arc;
     // GTF: which rows are feature lines, and — a batch with `#` lines is gathered like a filtered one — the row map's buffers
-    if (r->format == EXG_FMT_GTF && (arc = r->dev_alloc(&r->d_keep, validity_bytes))) return arc;
-    if ((r->has_filter || r->format == EXG_FMT_GTF) && (arc = alloc_row_selection(r))) return arc;
+    // (a region reader: which rows overlap the region — exg_rd_region.hpp)
+    if ((r->format == EXG_FMT_GTF || r->region) && (arc = r->dev_alloc(&r->d_keep, validity_bytes))) return arc;
+    if ((r->has_filter || r->format == EXG_FMT_GTF || r->region) && (arc = alloc_row_selection(r))) return arc;
     if (!r->d_res && !(r->d_res = exg_rd::dev_pool()->take(r->device, 4096))) return fail(r, EXG_E_HIP, "out of device memory");
     return EXG_OK;
 }
@@ -158,9 +160,11 @@ struct BatchRun {
     const uint32_t *row_map = nullptr;
     double t_scan = 0;
 
-    // (GTF: COUNT(*) counts feature lines, so the scan stores — d_keep alone: every column is a NULL pointer to it)
+    // (GTF: COUNT(*) counts feature lines, so the scan stores — d_keep alone: every column is a NULL pointer to it; a region reader
+    // counts the rows its predicate keeps, which reads chrom, pos, ref and info)
     BatchRun(exg_reader *reader, bool count)
-        : r(reader), count_only(count), no_store(count && !reader->has_filter && reader->format != EXG_FMT_GTF), want(reader->device_batch_bytes) {}
+        : r(reader), count_only(count), no_store(count && !reader->has_filter && reader->format != EXG_FMT_GTF && !reader->region),
+          want(reader->device_batch_bytes) {}
 
     // ---- 1: the size of the attempt, from `want`, the ramp and the range (in.n == 0: nothing of this reader's is left)
     void size_attempt() {
@@ -466,7 +470,7 @@ struct BatchRun {
             // whether or not its column is selected — from their text
             a.d_fields[1] = a.d_fields[5] = nullptr;
             for (int c : {0, 3})
-                if (!r->want(c) && !((r->filter_cols >> c) & 1ull)) a.d_fields[c] = nullptr;
+                if (!r->want(c) && !((r->filter_cols >> c) & 1ull) && !r->region) a.d_fields[c] = nullptr;  // (the region predicate reads both)
         }
         a.d_pos = (int64_t *)r->d_pos;
         a.d_qual = (float *)r->d_qual;
@@ -574,9 +578,13 @@ struct BatchRun {
     }
 
     // ---- 7: rows where the predicate is TRUE -> row map; the columns are gathered through it on their way out.  GTF: the rows
-    // that are feature lines (d_keep), ANDed with the predicate when there is one
+    // that are feature lines (d_keep), ANDed with the predicate when there is one.  A region reader: the rows that overlap the region
+    // (d_keep, written here by exg_vcf_region_keep), ANDed likewise
     bool rows_skipped() const { return r->format == EXG_FMT_GTF && (res.flags & EXG_RF_ROWS_SKIPPED); }
+    bool keep_words() const { return rows_skipped() || r->region; }
     int select_rows() {
+        if (r->region)
+            if (int rc = region_keep(r, in.d_input, (uint64_t)(uintptr_t)in.h, k, (uint64_t *)r->d_keep)) return rc;
         exg::arrow::FilterCols fc;
         memset(&fc, 0, sizeof fc);
         for (int c = 0; c < format_desc(r->format).n_columns; c++) {  // a text format's strings point into the input
@@ -587,7 +595,7 @@ struct BatchRun {
             fc.d_base[2] = (const uint8_t *)r->d_payload;
             fc.payload_base[2] = (uint64_t)(uintptr_t)(in.b ? in.b->payload : nullptr);
         }
-        return exg_rd::select_rows(r, &fc, rows_skipped() ? (const uint64_t *)r->d_keep : nullptr, &k, &row_map);
+        return exg_rd::select_rows(r, &fc, keep_words() ? (const uint64_t *)r->d_keep : nullptr, &k, &row_map);
     }
 
     // ---- 8: the rows leave.  new_reader: the columns stay in HBM and become Arrow buffers there (exg_arrow_stream.cpp)
@@ -664,7 +672,7 @@ int next_batch(exg_reader *r, bool count_only, uint64_t *n_records_out) {
         run.prefetch_next();
         TRACE("prefetch issue", t_pf);
         run.k = run.res.n_records;
-        if ((r->has_filter || run.rows_skipped()) && run.k && !r->arrow_emit && (rc = run.select_rows())) return rc;
+        if ((r->has_filter || run.keep_words()) && run.k && !r->arrow_emit && (rc = run.select_rows())) return rc;
         *n_records_out = run.k;
         if (r->arrow_emit && !count_only) rc = run.arrow_emit();
         else rc = run.k && !count_only ? run.columns_to_host() : EXG_OK;

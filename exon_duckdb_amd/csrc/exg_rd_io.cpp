@@ -272,6 +272,7 @@ exg_reader::~exg_reader() {
     exg_rd::MeterScope meter_scope(&meter);
     fan.reset();  // (its workers close their readers)
     src.reset();  // (its thread reads the file through fd_keep: before the descriptor closes)
+    region.reset();
     free_device();
     if (d_res) exg_rd::dev_pool()->give(device, d_res, 4096);
     if (d_phase) exg_rd::dev_pool()->give(device, d_phase, 4096);

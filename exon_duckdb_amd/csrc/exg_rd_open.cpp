@@ -15,6 +15,7 @@
 
 #include "exg_map_guard.hpp"
 #include "exg_rd_bam.hpp"
+#include "exg_rd_region.hpp"
 #include "exg_rd_source.hpp"
 #include "exg_rd_stages.hpp"
 #include "exg_sam_header.hpp"
@@ -175,7 +176,8 @@ static int open_source(exg_reader *r, std::shared_ptr<PinnedBlock> &blk, const s
     r->gz_header_prefix = 0;
     const size_t queued = getenv("EXG_SOURCE_QUEUE") ? (size_t)std::max(1, atoi(getenv("EXG_SOURCE_QUEUE"))) : r->mem_cap ? 1 : 2;
     auto make = [&](uint64_t c_begin, uint64_t c_end, bool bgzf_only, const uint64_t *marks) {
-        std::unique_ptr<SegmentProducer> prod = r->bcf ? make_bcf_producer(r, make_gzip_producer(r, fd, c_begin, c_end, bcf_input_target(target), path, true, bcf_input_reserve(target), nullptr),
+        std::unique_ptr<SegmentProducer> prod = r->region ? make_region_producer(r, fd, n, target, path, reserve)  // (the header + the index's member ranges)
+                                                : r->bcf  ? make_bcf_producer(r, make_gzip_producer(r, fd, c_begin, c_end, bcf_input_target(target), path, true, bcf_input_reserve(target), nullptr),
                                                                            bcf_input_reserve(target), target, path, reserve)  // (BGZF -> BCF records -> VCF text)
                                                 : r->compression == kGzip  ? make_gzip_producer(r, fd, c_begin, c_end, target, path, bgzf_only, reserve, marks)
                                                 : r->compression == kBzip2 ? make_bzip2_producer(r, fd, n, target, path, reserve)

@@ -16,6 +16,7 @@
 #include "exg_map_guard.hpp"
 #include "exg_rd_bam.hpp"
 #include "exg_rd_fanout.hpp"
+#include "exg_rd_region.hpp"
 #include "exg_rd_source.hpp"
 
 using namespace exg_rd;
@@ -238,6 +239,60 @@ extern "C" int exg_open(const exg_open_args *args, exg_reader **out) {
         }
     }
     *out = r.release();
+    return EXG_OK;
+}
+
+// vcf_query(path, region): a reader over the members of a BGZF VCF that its tabix index selects (exg_rd_region.hpp).  What can be
+// refused by name is refused before a device is asked for: the format, the shard count, a file that is not BGZF, a missing index
+extern "C" int exg_open_region(const exg_open_args *args, const char *region, exg_reader **out) {
+    if (!args || !out || !args->path || !args->file_format || !region) {
+        exg::set_error("exg_open_region: null argument");
+        return EXG_E_INVALID_ARG;
+    }
+    *out = nullptr;
+    if (strcasecmp(args->file_format, "vcf") != 0) {
+        exg::set_error("exg_open_region: file_format %s is not supported: region queries read VCF text behind a tabix index (vcf_query) only", args->file_format);
+        return EXG_E_UNSUPPORTED;
+    }
+    if (args->shard_count != 1) {
+        exg::set_error("exg_open_region: shard_count %u is not supported: a region reader is one shard (shard_count 1)", args->shard_count);
+        return EXG_E_UNSUPPORTED;
+    }
+    const std::string path = args->path, tbi = path + ".tbi";
+    struct stat sb;
+    if (stat(path.c_str(), &sb) != 0 || !S_ISREG(sb.st_mode)) {
+        exg::set_error("could not register table: cannot open '%s': a region query reads one regular file", path.c_str());
+        return EXG_E_IO;
+    }
+    unsigned char h[18] = {0};
+    FILE *fp = fopen(path.c_str(), "rb");
+    const size_t got = fp ? fread(h, 1, sizeof h, fp) : 0;
+    if (fp) fclose(fp);
+    if (!(got == 18 && h[0] == 0x1f && h[1] == 0x8b && h[2] == 8 && (h[3] & 4) && h[12] == 'B' && h[13] == 'C')) {
+        exg::set_error("a region query is not supported for '%s': it is not BGZF-compressed (bgzip it and index it with tabix -p vcf)", path.c_str());
+        return EXG_E_UNSUPPORTED;
+    }
+    if (stat(tbi.c_str(), &sb) != 0 || !S_ISREG(sb.st_mode)) {
+        exg::set_error("a region query needs the tabix index '%s', which does not exist (tabix -p vcf '%s')", tbi.c_str(), path.c_str());
+        return EXG_E_IO;
+    }
+    exg_open_args a = *args;
+    a.compression = "gzip";  // (BGZF whatever the name says)
+    exg_reader *r = nullptr;
+    if (int rc = exg_open(&a, &r)) return rc;
+    int rc;
+    {
+        DeviceGuard guard(r->device);
+        MeterScope meter_scope(&r->meter);
+        rc = region_open(r, region);
+    }
+    if (rc) {
+        const std::string why = r->error;
+        exg_close(r);
+        exg::set_error("%s", why.c_str());
+        return rc;
+    }
+    *out = r;
     return EXG_OK;
 }
 
@@ -468,6 +523,7 @@ extern "C" int exg_reader_stats_of(exg_reader *r, exg_reader_stats *out) {
     out->nested_ns = r->nested_ns.load();
     out->host_vector_bytes = r->host_vector_bytes.load();
     exg_rd::bam_stats(r, &out->bam_tiles, &out->bam_tiles_rewalked);
+    if (r->region) out->reserved[0] = r->region->members.load();  // region_members
     for (const std::string &f : r->files) {
         struct stat sb;
         if (stat(f.c_str(), &sb) == 0 && S_ISREG(sb.st_mode)) out->input_bytes += (uint64_t)sb.st_size;

@@ -25,6 +25,7 @@ int stream_to_host(void *h_dst, const void *d_src, uint64_t bytes, void *stream)
 namespace exg_rd {
 class DecodedSource;
 class FanOut;
+struct RegionPlan;
 
 // HIP's current device is per host thread: every entry point that touches a reader runs with the reader's device
 // current (the consumer may call from any thread — DuckDB binds on one thread and scans on others — and a process may
@@ -468,7 +469,7 @@ struct exg_reader {
     void *d_cols[exg_rd::kMaxColumns] = {};
     void *d_col_valid[exg_rd::kMaxColumns] = {};
     void *d_valid_spare[2] = {nullptr, nullptr};  // (FormatDesc::spare_validity)
-    void *d_keep = nullptr;  // GTF: the scan numbers rows by lines; bit r = row r is a feature line (exg_gtf_scan_args.d_keep)
+    void *d_keep = nullptr;  // GTF: the scan numbers rows by lines; bit r = row r is a feature line (exg_gtf_scan_args.d_keep); a region reader: row r overlaps the region
     void *d_pos = nullptr, *d_qual = nullptr, *d_payload = nullptr;  // VCF: the parsed POS / QUAL; FASTA: the joined sequences
     // the vector a column's parsed numbers go to, beside the field's text in d_cols (NULL: the column has none)
     void **parsed_vector(exg_rd::ParsedVector which) { return which == exg_rd::kParsedPos ? &d_pos : which == exg_rd::kParsedQual ? &d_qual : nullptr; }
@@ -523,6 +524,10 @@ struct exg_reader {
     // the columns, validity words and row-selection buffers are the fields above)
     std::shared_ptr<void> bam_state;
     bool bcf = false;  // file_format "bcf": the records become VCF lines in the decoded stream (exg_rd_bcf.cpp); format is EXG_FMT_VCF
+    // exg_open_region (vcf_query): the region, the index's chunks and the member ranges they come to (exg_rd_region.hpp).  The decoded
+    // stream holds the header and those ranges' lines only; behind every scan the region predicate's keep words (d_keep) go into
+    // the row selection, like GTF's
+    std::shared_ptr<exg_rd::RegionPlan> region;
 
     void free_device();
     exg_reader();  // (out of line: `src` is a pointer to a type this header only declares)

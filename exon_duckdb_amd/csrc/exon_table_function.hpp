@@ -75,6 +75,7 @@ struct ExonTableFunction {
         std::string file_type;
         std::string compression;  // "auto_detect" when the named parameter is absent (module.cpp:85)
         std::string file_name;
+        std::string region;  // vcf_query(path, region): the region text ("": not a region query); the reader is exg_open_region's
         std::vector<std::string> all_names;
         std::vector<LogicalType> all_types;
         uint64_t input_bytes = 0;        // size of the input files on disk (exg_reader_stats.input_bytes at bind)
@@ -119,15 +120,19 @@ struct ExonTableFunction {
         a.columns = columns;  // projection_pushdown (module.cpp:310): only these columns' vectors cross PCIe
         a.flags = flags;
         exg_reader *r = nullptr;
-        if (exg_open(&a, &r) != EXG_OK) throw std::runtime_error(exg_last_error_message());  // module.cpp:105-108
+        const int rc = d.region.empty() ? exg_open(&a, &r) : exg_open_region(&a, d.region.c_str(), &r);
+        if (rc != EXG_OK) throw std::runtime_error(exg_last_error_message());  // module.cpp:105-108
         return r;
     }
 
     // module.cpp:75-156.  The reference learns the schema by opening a reader; so does this (and closes it again).
+    // region (vcf_query's second argument): the bind opens with exg_open_region, so a missing index, a file that is not BGZF and a
+    // region the index does not hold all fail here
     static std::unique_ptr<BindData> Bind(const std::string &file_name, const std::string &compression, const std::string &file_type,
-                                          std::vector<LogicalType> &return_types, std::vector<std::string> &names) {
+                                          std::vector<LogicalType> &return_types, std::vector<std::string> &names, const std::string &region = "") {
         auto result = std::make_unique<BindData>();
         result->file_name = file_name;
+        result->region = region;
         result->compression = compression.empty() ? "auto_detect" : compression;
         result->file_type = file_type;
         exg_reader *r = OpenReader(*result, "", 0, 0, 0, 1, 0);
@@ -205,7 +210,8 @@ struct ExonTableFunction {
         a.compression = data.compression == "auto_detect" ? nullptr : data.compression.c_str();
         a.filters = gs->filter_clause.empty() ? nullptr : gs->filter_clause.c_str();
         uint32_t n = 1;
-        if (exg_plan_shards(&a, &n, gs->devices, 64) != EXG_OK) throw std::runtime_error(exg_last_error_message());
+        if (!data.region.empty()) gs->devices[0] = 0;  // a region reader is one shard: MaxThreads() == 1
+        else if (exg_plan_shards(&a, &n, gs->devices, 64) != EXG_OK) throw std::runtime_error(exg_last_error_message());
         gs->n_shards = n;
         return gs;
     }
@@ -633,5 +639,7 @@ static const Registration kRegistrations[] = {
     {"read_fasta", "fasta"}, {"read_fastq", "fastq"}, {"read_vcf_file_records", "vcf"}, {"read_vcf", "vcf"},
     {"read_bam_file_records", "bam"}, {"read_bed_file", "bed"}, {"read_sam_file_records", "sam"},
     {"read_bcf_file_records", "bcf"}, {"read_gtf", "gtf"}};
+// exon/src/exon_extension.cpp:75-77: the indexed region queries, (VARCHAR path, VARCHAR region); bcf_query and bam_query are not built
+static const Registration kRegionRegistrations[] = {{"vcf_query", "vcf"}};
 
 }  // namespace exon_scan

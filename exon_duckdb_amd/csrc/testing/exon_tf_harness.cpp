@@ -78,16 +78,19 @@ struct WTArrowTableScanInfo : public TableFunctionInfo {
 };
 
 // module.cpp:296-318
-static void Register(const std::string &name, const std::string &file_type, Catalog &catalog) {
+// region: the function takes (VARCHAR path, VARCHAR region) — vcf_query
+static void Register(const std::string &name, const std::string &file_type, Catalog &catalog, bool region = false) {
     TableFunction scan;
     scan.name = name;
     scan.arguments = {LogicalType(LogicalTypeId::VARCHAR)};
+    if (region) scan.arguments.push_back(LogicalType(LogicalTypeId::VARCHAR));
     scan.bind = [](TableFunctionBindInput &input, std::vector<LogicalType> &return_types, std::vector<std::string> &names) {
         auto &info = static_cast<const WTArrowTableScanInfo &>(*input.info);
         std::string compression;
         for (auto &kv : input.named_parameters)
             if (kv.first == "compression") compression = kv.second;
-        return std::unique_ptr<FunctionData>(TF::Bind(input.inputs.at(0), compression, info.file_type, return_types, names));
+        return std::unique_ptr<FunctionData>(
+            TF::Bind(input.inputs.at(0), compression, info.file_type, return_types, names, input.inputs.size() > 1 ? input.inputs.at(1) : std::string()));
     };
     scan.init_global = [](TableFunctionInitInput &input) {
         return std::unique_ptr<GlobalTableFunctionState>(
@@ -105,7 +108,7 @@ static void Register(const std::string &name, const std::string &file_type, Cata
         return TF::BatchIndex(static_cast<const TF::LocalState &>(*ls));
     };
     scan.function_info = std::make_shared<WTArrowTableScanInfo>(file_type);
-    scan.named_parameters["compression"] = LogicalType(LogicalTypeId::VARCHAR);
+    if (!region) scan.named_parameters["compression"] = LogicalType(LogicalTypeId::VARCHAR);
     scan.projection_pushdown = true;
     scan.filter_pushdown = true;  // module.cpp:311; the predicate is evaluated on the device
     catalog.CreateTableFunction(scan);
@@ -114,6 +117,7 @@ static void Register(const std::string &name, const std::string &file_type, Cata
 // exon/src/exon_extension.cpp:25-96, restricted to the path
 void LoadInternal(Catalog &catalog) {
     for (const auto &reg : exon_scan::kRegistrations) Register(reg.name, reg.file_type, catalog);
+    for (const auto &reg : exon_scan::kRegionRegistrations) Register(reg.name, reg.file_type, catalog, true);
 }
 
 }  // namespace exon_amd
@@ -183,17 +187,24 @@ static Catalog &the_catalog() {
 
 extern "C" int exon_tf_catalog_has(const char *name) { return the_catalog().GetTableFunction(name) != nullptr; }
 
-extern "C" int exon_tf_bind(const char *fn_name, const char *path, const char *compression, exon_tf_handle **out) {
+// region (NULL: none): the second positional argument of vcf_query
+extern "C" int exon_tf_bind_region(const char *fn_name, const char *path, const char *compression, const char *region, exon_tf_handle **out) {
     *out = nullptr;
     const TableFunction *fn = the_catalog().GetTableFunction(fn_name);
     if (!fn) {
         g_tf_error = std::string("Catalog Error: Table Function with name ") + fn_name + " does not exist!";
         return EXG_E_INVALID_ARG;
     }
+    if (fn->arguments.size() != (region ? 2u : 1u) || (compression && !fn->named_parameters.count("compression"))) {
+        g_tf_error = std::string("Binder Error: No function matches the given name and argument types '") + fn_name + "(VARCHAR" +
+                     (region ? ", VARCHAR" : "") + (compression ? ", compression := VARCHAR" : "") + ")'";
+        return EXG_E_INVALID_ARG;
+    }
     auto h = std::make_unique<exon_tf_handle>();
     h->fn = fn;
     TableFunctionBindInput in;
     in.inputs.push_back(path);
+    if (region) in.inputs.push_back(region);
     if (compression) in.named_parameters["compression"] = compression;
     in.info = fn->function_info.get();
     try {
@@ -204,6 +215,9 @@ extern "C" int exon_tf_bind(const char *fn_name, const char *path, const char *c
     }
     *out = h.release();
     return EXG_OK;
+}
+extern "C" int exon_tf_bind(const char *fn_name, const char *path, const char *compression, exon_tf_handle **out) {
+    return exon_tf_bind_region(fn_name, path, compression, nullptr, out);
 }
 
 // TableFunction::cardinality (module.cpp:307): the estimate the glue hands the planner; 0 = none

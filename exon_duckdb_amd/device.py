@@ -838,3 +838,63 @@ def read_bcf_file_records(path, columns=None, where=None, filters=None):
     and tests.  columns / where / filters are Relation.fetchall's."""
     from . import table_function
     return table_function.connect().table_function("read_bcf_file_records", path).fetchall(columns=columns, where=where, filters=filters)
+
+
+def tabix_query(index_bytes, region):
+    """exg_tabix_query (host only): the inflated bytes of a .tbi and a region -> ([(virtual begin, virtual end)], resolved region as
+    (ref_id, name, start, end)), by the two-call capacity protocol"""
+    lib = load_library()
+    enc = region.encode() if isinstance(region, str) else region
+    n = C.c_uint64(0)
+    resolved = abi.Region()
+    check(lib.exg_tabix_query(index_bytes, len(index_bytes), enc, None, 0, C.byref(n), C.byref(resolved)))
+    chunks = (abi.VirtualChunk * max(1, n.value))()
+    check(lib.exg_tabix_query(index_bytes, len(index_bytes), enc, chunks, n.value, C.byref(n), C.byref(resolved)))
+    return ([(int(chunks[i].begin), int(chunks[i].end)) for i in range(n.value)],
+            (int(resolved.ref_id), resolved.name[:resolved.name_len], int(resolved.start), int(resolved.end)))
+
+
+def vcf_region_keep(scan, n_rows, d_input, payload_base, name, start, end=abi.REGION_UNBOUNDED, guard=-1):
+    """exg_vcf_region_keep on the columns a VcfScan left in HBM -> the keep words (uint64 numpy array of (n_rows + 63) // 64 words;
+    the buffer behind them is filled with `guard` first and one word longer, so that a test sees a store out of place)"""
+    torch = _torch()
+    lib = load_library()
+    words = (n_rows + 63) // 64
+    keep = torch.full((words + 1,), guard, dtype=torch.int64, device=scan.pos.device)
+    d_name = upload(name)
+    a = abi.VcfRegionArgs()
+    a.d_chrom, a.d_ref, a.d_info = scan.cols[0].data_ptr(), scan.cols[3].data_ptr(), scan.cols[7].data_ptr()
+    a.d_pos = scan.pos.data_ptr()
+    a.d_payload = d_input.data_ptr()
+    a.payload_base = payload_base
+    a.n_rows = n_rows
+    a.d_name, a.name_len = d_name.data_ptr(), len(name)
+    a.start, a.end = start, end
+    a.d_keep = keep.data_ptr()
+    a.stream = stream_ptr().value
+    check(lib.exg_vcf_region_keep(C.byref(a)))
+    torch.cuda.synchronize()
+    host = keep.cpu().numpy().view(np.uint64)
+    assert host[words] == np.uint64(guard & 0xFFFFFFFFFFFFFFFF), "exg_vcf_region_keep wrote behind its last word"
+    return host[:words]
+
+
+def vcf_query(path, region, columns=None, where=None, filters=None):
+    """the rows of vcf_query(path, region) through the table function — a BGZF VCF with its tabix index beside it (path + ".tbi").
+    columns / where / filters are Relation.fetchall's."""
+    from . import table_function
+    return table_function.connect().table_function("vcf_query", path, region=region).fetchall(columns=columns, where=where, filters=filters)
+
+
+def vcf_query_reader(path, region, batch_size=abi.EXG_VECTOR_SIZE):
+    """vcf_query_reader — the reference's FFI entry behind vcf_query (exon/include/rust.hpp:60-63) — as a pyarrow.RecordBatchReader"""
+    import pyarrow as pa
+    lib = load_library()
+    stream = (C.c_uint64 * 8)()
+    enc = lambda s: s if isinstance(s, bytes) else s.encode()  # noqa: E731
+    err = lib.exg_vcf_query_reader(C.addressof(stream), enc(path), enc(region), batch_size)
+    if err:
+        msg = C.string_at(err).decode("utf-8", "replace")
+        C.CDLL(None).free(C.c_void_p(err))
+        raise ExgError(abi.EXG_E_INVALID_ARG, msg)
+    return pa.RecordBatchReader._import_from_c(C.addressof(stream))

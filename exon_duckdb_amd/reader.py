@@ -9,8 +9,9 @@ from .table_function import Chunk, Schema, decode_vector, type_tree
 
 class ShardReader:
     def __init__(self, path, file_format, shard_index=0, shard_count=1, compression=None, device=0, device_batch_bytes=0,
-                 filters=None, batch_rows=2048, columns=None, expect_chunks=False):
-        """columns: indices (exg_schema_of order) of the columns to copy back; None = all (exg_open_args.columns);
+                 filters=None, batch_rows=2048, columns=None, expect_chunks=False, region=None):
+        """region: a region reader (exg_open_region: a BGZF VCF behind its tabix index, str or bytes);
+        columns: indices (exg_schema_of order) of the columns to copy back; None = all (exg_open_args.columns);
         expect_chunks: exg_open_args.flags = EXG_OPEN_CHUNKS — chunks will be pulled (a compressed input mirrors its decoded segments from the first on)"""
         self._l = load_library()
         self._l.exg_open.argtypes = [C.POINTER(abi.OpenArgs), C.POINTER(C.c_void_p)]
@@ -27,7 +28,10 @@ class ShardReader:
                          sum(1 << int(c) for c in columns) if columns is not None else 0, abi.EXG_OPEN_CHUNKS if expect_chunks else 0)
         self.columns = None if columns is None else sorted(int(c) for c in columns)
         self._r = C.c_void_p()
-        rc = self._l.exg_open(C.byref(a), C.byref(self._r))
+        if region is None:
+            rc = self._l.exg_open(C.byref(a), C.byref(self._r))
+        else:
+            rc = self._l.exg_open_region(C.byref(a), enc(region), C.byref(self._r))
         if rc != 0:
             raise ExgError(rc, self._l.exg_last_error_message().decode("utf-8", "replace"))
         sch = Schema()
@@ -77,7 +81,9 @@ class ShardReader:
         rc = self._l.exg_reader_stats_of(self._r, C.byref(st))
         if rc != 0:
             self._fail(rc)
-        return {f: getattr(st, f) for f, _ in abi.ReaderStats._fields_ if f != "reserved"}
+        out = {f: getattr(st, f) for f, _ in abi.ReaderStats._fields_ if f != "reserved"}
+        out["region_members"] = int(st.reserved[0])  # (a region reader: the BGZF members its plan had inflated so far)
+        return out
 
     def digest(self, nested=False, per_column=False):
         """(rows, blake2b over the columns of every row in file order) without building Python rows for all of them: the

@@ -9,6 +9,7 @@ tests, which read like the reference's sqllogictests:
     con.from_path("x/test.fasta")                     # replacement scan
     con.table_function("read_bcf_file_records", "x/calls.bcf").fetchall()   # the VCF schema of the file's own header
     con.table_function("read_gtf", "x/genes.gtf").fetchall()    # attributes: MAP(VARCHAR, VARCHAR) -> [(key, value), ...]
+    con.table_function("vcf_query", "x/calls.vcf.gz", region="1:10000-20000").fetchall()   # behind x/calls.vcf.gz.tbi
 """
 import ctypes as C
 
@@ -172,6 +173,8 @@ def _lib():
         l.exon_tf_catalog_has.argtypes = [C.c_char_p]
         l.exon_tf_bind.restype = C.c_int
         l.exon_tf_bind.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_void_p)]
+        l.exon_tf_bind_region.restype = C.c_int
+        l.exon_tf_bind_region.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_void_p)]
         l.exon_tf_schema.argtypes = [C.c_void_p, C.POINTER(Schema)]
         l.exon_tf_init_global.restype = C.c_int
         l.exon_tf_init_global.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_int, C.POINTER(FilterNode), C.c_int, C.POINTER(C.c_uint64)]
@@ -215,11 +218,13 @@ def _decode_strings(ptr, validity_ptr, n):
 
 
 class Relation:
-    def __init__(self, fn_name, path, compression=None):
+    def __init__(self, fn_name, path, compression=None, region=None):
         self._l = _lib()
         self.fn_name, self.path, self.compression = fn_name, path, compression
+        #: vcf_query's second positional argument (str or bytes); None: a function of one argument
+        self.region = region.encode() if isinstance(region, str) else region
         h = C.c_void_p()
-        rc = self._l.exon_tf_bind(fn_name.encode(), path.encode(), compression.encode() if compression else None, C.byref(h))
+        rc = self._bind(h)
         if rc != 0:
             raise ExgError(rc, _err(self._l))          # bind-time error, e.g. read_fastq('')
         sch = Schema()
@@ -235,14 +240,17 @@ class Relation:
     #: `SET threads` is smaller or the pipeline is sequential — the tests set 1 (and other numbers below MaxThreads())
     scan_threads = None
 
+    def _bind(self, h):
+        return self._l.exon_tf_bind_region(self.fn_name.encode(), self.path.encode(), self.compression.encode() if self.compression else None,
+                                           self.region, C.byref(h))
+
     def _scan(self, column_ids, filters=None, decode=None):
         """Plays DuckDB: init_global once, init_local + the scan loop on up to MaxThreads() threads, every chunk handed
         to `decode` while it is alive.  -> [(batch_index, n_rows, decoded)] in batch order (stable: the chunks of one
         batch keep the order their thread produced them in)."""
         import threading
         h = C.c_void_p()
-        rc = self._l.exon_tf_bind(self.fn_name.encode(), self.path.encode(),
-                                  self.compression.encode() if self.compression else None, C.byref(h))
+        rc = self._bind(h)
         if rc != 0:
             raise ExgError(rc, _err(self._l))
         try:
@@ -337,10 +345,11 @@ class Connection:
     def has_table_function(self, name):
         return bool(_lib().exon_tf_catalog_has(name.encode()))
 
-    def table_function(self, name, path, compression=None):
+    def table_function(self, name, path, compression=None, region=None):
+        """region: the second positional argument of vcf_query(path, region)"""
         if not self.has_table_function(name):
             raise ExgError(abi.EXG_E_INVALID_ARG, f"Catalog Error: Table Function with name {name} does not exist!")
-        return Relation(name, path, compression)
+        return Relation(name, path, compression, region)
 
     def replacement_scan(self, table_name):
         buf = C.create_string_buffer(64)

@@ -899,6 +899,34 @@ int exg_gff_attributes(const exg_gff_attributes_args *args);
  * `Invalid GFF attribute in row <r> at byte <k>`; *out is filled either way. */
 int exg_gff_attributes_result(const struct exg_gff_attributes_result *d_result, void *stream, struct exg_gff_attributes_result *out);
 
+/* ---- region predicate on device-resident VCF columns --------------------------------------------------------
+ * Which rows of a scanned VCF batch overlap a region (the row rule of vcf_query; the rules live once in csrc/exg_vcf_region.hpp):
+ * row r is kept when its chrom equals the name byte for byte (the lengths are equal too: `1` is not `10`), pos <= end and
+ * row_end >= start, where row_end is the integer of the INFO key `END=` — at the start of INFO or right behind a `;`, digits up
+ * to the next `;` or the field's end (at most 18); `SVEND=` is not it; `END` without a value, `END=.`, anything that is not such
+ * an integer, or no END key at all: pos + len(ref) - 1.  A row whose pos lies in [start, end] is kept without a look at INFO.
+ * Coordinates are 1-based and closed; end = INT64_MAX is unbounded.
+ * d_chrom, d_ref, d_info: the columns 0, 3 and 7 exg_vcf_scan writes (d_info: the raw INFO text); d_pos: its parsed POS.
+ * d_keep: (n_rows + 63) / 64 whole words, bit r % 64 of word r / 64 = row r is kept, the tail bits of the last word zero — what
+ * the reader's row selection takes beside a `filters` predicate.  A lane takes a row; no workspace, no result block.
+ * Asynchronous on args->stream; n_rows = 0 is valid (nothing is written). */
+typedef struct exg_vcf_region_args {
+    const exg_string_t *d_chrom; /* device, 16-byte aligned */
+    const exg_string_t *d_ref;   /* device, 16-byte aligned */
+    const int64_t *d_pos;        /* device, 8-byte aligned */
+    const exg_string_t *d_info;  /* device, 16-byte aligned */
+    const void *d_payload;       /* device bytes the non-inlined strings point into */
+    uint64_t payload_base;       /* string_t.ptr - payload_base = byte offset in d_payload */
+    uint64_t n_rows;
+    const uint8_t *d_name;       /* device: the region's reference name, name_len bytes */
+    uint32_t name_len;
+    uint32_t reserved;           /* 0 */
+    int64_t start, end;          /* 1-based, closed; 1 <= start <= end */
+    uint64_t *d_keep;            /* out: device, 8-byte aligned, (n_rows + 63) / 64 words */
+    void *stream;
+} exg_vcf_region_args;
+int exg_vcf_region_keep(const exg_vcf_region_args *args);
+
 /* ---- device inflate (gzip / BGZF members; replaces flate2 behind rust/src/arrow_reader.rs:60-91) ---- */
 typedef struct exg_inflate_member {
     uint64_t comp_off;  /* offset of the member's DEFLATE stream (after the gzip header) in d_comp */
@@ -1139,9 +1167,38 @@ typedef struct exg_reader_stats {
                                   * what a scan INTO DataChunks pays on the D2H link next to a decoded input's own bytes */
     uint64_t bam_tiles;          /* read_bam_file_records: tiles of all device batches so far (exg_bam_scan_result.tiles) ... */
     uint64_t bam_tiles_rewalked; /* ... and those that were walked a second time (words that were reserved: the layout is ABI 9's) */
-    uint64_t reserved[1];
+    uint64_t reserved[1];        /* [0]: region_members — a region reader (exg_open_region): the BGZF members its plan had inflated so
+                                  * far, the leading members that hold the header and the members of its ranges both counted (a
+                                  * member in both counts twice: it is inflated twice); a member read behind a range only to
+                                  * complete that range's last line is not part of the plan and is not counted.  Else 0 */
 } exg_reader_stats;
 int exg_reader_stats_of(exg_reader *r, exg_reader_stats *out);
+
+/* ---- region queries: a tabix index, its planner, and a reader over the members it selects ------------------ */
+typedef struct exg_virtual_chunk {
+    uint64_t begin, end; /* BGZF virtual offsets: (offset of a member in the file << 16) | offset in its inflated bytes */
+} exg_virtual_chunk;
+typedef struct exg_region {
+    int64_t start, end; /* 1-based, closed; end = INT64_MAX: to the end of the sequence */
+    uint32_t ref_id;    /* the reference's number in the index */
+    uint32_t name_len;
+    char name[256];     /* the reference's name, NUL-terminated */
+} exg_region;
+/* Host only.  index_bytes: the INFLATED bytes of a .tbi (format 2, VCF; anything truncated or whose counts the bytes do not hold:
+ * EXG_E_PARSE, never a read outside [index_bytes, index_bytes + n)).  region: `name`, `name:start` or `name:start-end`, split at
+ * the LAST colon, the whole string first tried as a name (csrc/exg_tabix.hpp: G1 .. G5); empty, or a name the index does not
+ * hold: EXG_E_INVALID_ARG with a message that names it.  The chunks to read, sorted and merged (P1 .. P6), go to out[0 .. cap):
+ * *n_chunks is always their number; they are written only when all of them fit, else EXG_E_CAPACITY — except in the counting
+ * call (out = NULL, cap = 0), which returns EXG_OK.  resolved (optional): what the region came to. */
+int exg_tabix_query(const uint8_t *index_bytes, uint64_t n, const char *region, exg_virtual_chunk *out, uint64_t cap, uint64_t *n_chunks,
+                    exg_region *resolved);
+/* vcf_query(path, region): exg_open for a BGZF-compressed VCF with a tabix index beside it (<path>.tbi), reading only the members
+ * the index selects for `region`.  file_format must be "vcf", the path one BGZF file, shard_count 1 (0 or more: EXG_E_UNSUPPORTED);
+ * the index is inflated by the device inflater (no zlib), planned by exg_tabix_query's planner, and every chunk is checked against
+ * the file — a virtual offset outside it or not on a member header is a stale or foreign index: EXG_E_IO.  The rows that leave are
+ * those exg_vcf_region_keep keeps, ANDed with args->filters when there are any; projection, nested columns, the memory cap and
+ * exg_count_only are read_vcf's.  exg_reader_stats.reserved[0] counts the members inflated. */
+int exg_open_region(const exg_open_args *args, const char *region, exg_reader **out);
 /* Device buffers, pinned host blocks and HIP streams of closed readers are recycled process-wide (size classes, at most
  * EXG_POOL_MAX_GB = 64 GB of HBM): this gives them back (the extension's unload / idle path). */
 void exg_trim_pools(void);
@@ -1215,6 +1272,22 @@ typedef struct ReaderResult {
  *                with SQL precedence; it is applied as `SELECT * FROM exon_table WHERE <filters>` (:125-141). */
 ReaderResult new_reader(struct ArrowArrayStream *stream_ptr, const char *uri, uintptr_t batch_size,
                         const char *compression, const char *file_format, const char *filters);
+
+/* exon/include/rust.hpp:23-25, 60-63, rust/src/vcf_query_reader.rs:31-36 — the reference's entry point behind vcf_query, same
+ * name, same arguments: new_reader's VCF stream over a region reader (exg_open_region: uri is a BGZF VCF with <uri>.tbi beside
+ * it, query a region). */
+typedef struct VCFReaderResult {
+    const char *error; /* NULL on success; else a heap C string the caller may free() */
+} VCFReaderResult;
+/* the library's entry: the error string, or NULL */
+const char *exg_vcf_query_reader(struct ArrowArrayStream *stream_ptr, const char *uri, const char *query, uintptr_t batch_size);
+/* the reference's name and signature over it, for the glue that calls it (the library itself exports exg_* names, replacement_scan
+ * and new_reader only) */
+static inline VCFReaderResult vcf_query_reader(struct ArrowArrayStream *stream_ptr, const char *uri, const char *query, uintptr_t batch_size) {
+    VCFReaderResult res;
+    res.error = exg_vcf_query_reader(stream_ptr, uri, query, batch_size);
+    return res;
+}
 
 #ifdef __cplusplus
 }
